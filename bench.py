@@ -15,6 +15,17 @@ and the whole transition log (25 B per env-step, SoA [K][n]) is written to HBM. 
 bounded RCCL transition gather + 4-scalar stats all-reduce described in DESIGN.md.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up (W steps, then --settle-launches untimed launches), times the K steps and prints the
+line.  Everything else the line can carry -- the after-warm-up-only window, per-launch and steady-state launch
+distributions, the fill ceiling, the profiled traffic, the single-step API, the CPU baselines and the other BASELINE
+configurations (`other_configs`) -- runs only with --full:
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+--dump-outputs DIR writes what the last timed step computed (a fixed, seeded sample of 1024 envs of its transition log,
+the env state after it and the running statistics) as DIR/<name>.npy, float32 / float64, so that two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -31,6 +42,8 @@ CHUNK = 1024
 BYTES_PER_STEP = 25           # s[2] a r t(u8) s2[2]
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 GATHER_RECORDS = 1 << 20      # bounded gather: last G steps with G * N_total <= 2^20 records
+DUMP_ENVS = 1024              # --dump-outputs: envs sampled from the last timed step's log (~29 MB at K = 1024)
+DUMP_SEED = 20240             # ... chosen by this seed, the same in every run
 
 
 def cpu_baseline(budget_s=24.0):
@@ -729,6 +742,30 @@ def single_step_api(env, torch, steps=200):
             "note": "ssc_mc_step, one launch per env-step, actions pre-generated in HBM; launch/L2-bound (1.6 MB per step)"}
 
 
+def last_step_outputs(env, chunk, torch):
+    """What the last timed step handed its caller, copied to the host right after the timed region (before any other
+    launch): the transition log of DUMP_ENVS envs drawn with DUMP_SEED (fewer when the log would pass ~48 MB), those
+    envs' state after the step and the env's running statistics (f64[4])."""
+    import numpy as np
+    n, K, cols = chunk.N, chunk.K, 2 * chunk.obs_dim + 3
+    m = max(1, min(n, DUMP_ENVS, (48 << 20) // (4 * K * cols)))
+    ids = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    idx = torch.as_tensor(ids, dtype=torch.long, device=chunk.act.device)
+    take = lambda x: x.index_select(x.dim() - 1, idx).float().cpu().numpy()       # (.cpu() waits for the step)
+    return {"env_ids": ids.astype(np.float64), "obs": take(chunk.obs), "act": take(chunk.act), "rew": take(chunk.rew),
+            "obs2": take(chunk.obs2), "done": take(chunk.done), "state_pos": take(env.s0), "state_vel": take(env.s1),
+            "stats": env.stats.double().cpu().numpy()}
+
+
+def write_outputs(out_dir, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in outputs.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def free_port():
     import socket
     with socket.socket() as sk:
@@ -760,7 +797,15 @@ def main():
     ap.add_argument("--gather-every", type=int, default=8,
                     help="N > 1: exchange the newest transitions every M-th chunk (M x as many steps per message: the "
                          "same records per second in fewer, larger RCCL messages)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure everything else the line reports: after-warm-up-only "
+                         "window, per-launch / steady launch distributions, fill ceiling, profiled traffic, single-step "
+                         "API, CPU baselines and the other BASELINE configurations (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64): a seeded sample "
+                         "of %d envs of its transition log, the env state after it and the running statistics"
+                         % DUMP_ENVS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline legs")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and run the gather path even at world size 1 "
                          "(single-GPU rehearsal of the N>1 code path)")
@@ -770,18 +815,19 @@ def main():
                          "(rank -> env_id0, barriers, MAX-reduced timings, rank-0 JSON) that also runs with several ranks "
                          "on ONE GPU; its numbers are not RCCL numbers")
     ap.add_argument("--cpu-budget", type=float, default=10.0,
-                    help="seconds of CPU work in the cpu_baseline leg (a bounded sample of the same workload)")
+                    help="--full: seconds of CPU work in the cpu_baseline leg (a bounded sample of the same workload)")
     ap.add_argument("--steady-launches", type=int, default=400,
-                    help="extra untimed-for-`value` launches after the timed region whose per-launch distribution is "
-                         "reported as roofline.steady (N = 1 only; 0 disables)")
+                    help="--full: extra untimed-for-`value` launches after the timed region whose per-launch distribution "
+                         "is reported as roofline.steady (N = 1 only; 0 disables)")
     ap.add_argument("--settle-launches", type=int, default=1500,
                     help="untimed launches of the step between the W warm-up steps and the timed region, so that the "
                          "timed K steps run past the post-idle power/clock transient (0 disables)")
     ap.add_argument("--series-out", default=None,
-                    help="diagnostic: write (phase, start, duration) of every launch of the run to this CSV")
-    ap.add_argument("--no-single-step", action="store_true", help="skip the single-step-API (ssc_mc_step) line")
+                    help="diagnostic (--full): write (phase, start, duration) of every launch of the run to this CSV")
+    ap.add_argument("--no-single-step", action="store_true", help="--full: skip the single-step-API (ssc_mc_step) line")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="config 2, one GPU: skip the BASELINE configs[2] / configs[3] lines attached as `other_configs`")
+                    help="--full, config 2, one GPU: skip the BASELINE configs[2] / configs[3] lines attached as "
+                         "`other_configs`")
     ap.add_argument("--no-per-env", action="store_true", help="--config 4: skip the one-navigator-per-env leg")
     ap.add_argument("--per-env-only", action="store_true", help="--config 4: ONLY the one-navigator-per-env leg (profiling runs)")
     ap.add_argument("--no-h20", action="store_true", help="--config 4: skip the horizon-20 leg (profiling runs: its launches carry the same kernel name)")
@@ -793,6 +839,12 @@ def main():
                     help="launch rehearsal: parse, (self-)spawn the ranks, rendezvous (process group + barrier), print one "
                          "JSON line on rank 0 and exit before anything touches a GPU -- what the CPU suite runs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.series_out and not args.full:
+        ap.error("--series-out records the launches of the --full run: add --full")
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs writes the headline path's outputs (--config 2)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started as plain `python bench.py --gpus N` (the way the N = 1 line is started): become the launcher.  The N
@@ -911,8 +963,9 @@ def main():
     # then measure the state a rollout engine actually runs in.  The count is reported in the JSON line.
     # For the record, the SAME K-step window is also timed right after the W warm-up launches, before any settling
     # (`after_warmup_only` in the JSON line): that is the number a reader gets who wants W and nothing else.
+    # (--full only: a plain run goes from the warm-up straight to the settle launches)
     cold_elapsed, cold_steps = None, 0
-    if args.settle_launches > 0:
+    if args.full and args.settle_launches > 0:
         cold_steps = args.steps
         barrier()
         t0c = time.perf_counter()
@@ -942,13 +995,17 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = e_first.elapsed_time(e_last) / max(1, args.steps)
-    for i in range(args.steps):                                   # the per-launch window (untimed)
-        one_step(warm_total + args.steps + i, evs[i])
-    if gather is not None:
-        gather.finish()
-    barrier()
-    per_launch = [a.elapsed_time(b) for a, b in evs]
-    steps_done = warm_total + 2 * args.steps
+    steps_done = warm_total + args.steps
+    outputs = last_step_outputs(env, chunks[(steps_done - 1) & 1], torch) if args.dump_outputs and rank == 0 else None
+    per_launch = None
+    if args.full:
+        for i in range(args.steps):                               # the per-launch window (untimed)
+            one_step(steps_done + i, evs[i])
+        if gather is not None:
+            gather.finish()
+        barrier()
+        per_launch = [a.elapsed_time(b) for a, b in evs]
+        steps_done += args.steps
     if gather is not None:          # one last exchange (untimed), so that the statistics check below sees every step
         gather.submit(chunks[(steps_done - 1) & 1], (steps_done - 1) & 1, env.stats)
         gather.finish()
@@ -958,7 +1015,7 @@ def main():
     # power state and slow down as the chip settles; `steady` is the distribution over
     # --steady-launches further back-to-back launches of the same kernel.
     steady = None
-    if world == 1 and args.steady_launches > 0 and gather is None:
+    if args.full and world == 1 and args.steady_launches > 0 and gather is None:
         sev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steady_launches)]
         for i, ev in enumerate(sev):
             one_step(steps_done + i, ev)
@@ -1031,17 +1088,19 @@ def main():
                 "kernel": "ssc::rollout_kernel<McEnv, RandomPolicy<2>>",
                 "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": per_launch_bytes,
                 "kernel_ms_note": "HIP events bracketing the K timed launches on the launch stream, / K",
-                "kernel_ms_dist": dist_stats(per_launch),
-                "kernel_ms_dist_note": "a second window of K launches right after the timed one, one event pair per launch "
-                                       "(the pairs cost ~7 us of queue time per launch, so they stay out of the timed region)",
             },
         }
+        if per_launch is not None:
+            result["roofline"]["kernel_ms_dist"] = dist_stats(per_launch)
+            result["roofline"]["kernel_ms_dist_note"] = ("a second window of K launches right after the timed one, one event "
+                                                         "pair per launch (the pairs cost ~7 us of queue time per launch, so "
+                                                         "they stay out of the timed region)")
         if steady is not None:
             steady["frac_at_median"] = per_launch_bytes / (steady["median"] * 1e-3) / 1e9 / HBM_PEAK_GBS
             steady["frac_at_min"] = per_launch_bytes / (steady["min"] * 1e-3) / 1e9 / HBM_PEAK_GBS
             steady["frac_at_p90"] = per_launch_bytes / (steady["p90"] * 1e-3) / 1e9 / HBM_PEAK_GBS
             result["roofline"]["steady"] = steady
-        if world == 1:
+        if args.full and world == 1:
             # the write ceiling of THIS box, measured beside the kernel ("use the measured ceiling alongside
             # nominal"): a plain fill of a buffer of the chunk's size, median of 10 launches
             try:
@@ -1059,16 +1118,16 @@ def main():
                 del fill
             except Exception as e:           # noqa: BLE001
                 result["roofline"]["fill_ceiling"] = {"error": repr(e)}
-        tr = profiled_traffic()
+        tr = profiled_traffic() if args.full else None
         if tr is not None and n == N_ENVS_PER_GPU and K == CHUNK and gather is None:   # the PMC pass is the N = 1 kernel alone:
             # a run that also packs and ships transitions moves more bytes than it measured
             result["roofline"]["traffic"] = tr[0]
             result["roofline"]["traffic_source"] = tr[1]
-        if world == 1 and not args.no_single_step and n == N_ENVS_PER_GPU:
+        if args.full and world == 1 and not args.no_single_step and n == N_ENVS_PER_GPU:
             result["single_step_api"] = single_step_api(env, torch)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.cpu_budget)
-        if world == 1 and not use_dist and not args.no_other_configs and n == N_ENVS_PER_GPU:
+        if args.full and world == 1 and not use_dist and not args.no_other_configs and n == N_ENVS_PER_GPU:
             # BASELINE configs[2] (fused actor rollout) and configs[3] (forward simulation + MPC scoring) measured in the
             # same process AFTER the headline's timed region: the same functions `--config 3` / `--config 4` print as
             # lines of their own (without their CPU legs), so that the driver's run carries all three
@@ -1096,6 +1155,8 @@ def main():
             except Exception as e:               # noqa: BLE001
                 other["next_rows"] = {"error": "%s: %s" % (type(e).__name__, e)}
             result["other_configs"] = other
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         print(json.dumps(result), flush=True)
     if use_dist:
         if gather is not None and rank == 0:
@@ -1104,7 +1165,7 @@ def main():
             assert obs.shape == (env.obs_dim, gather.g_steps, n) and bool(torch.isfinite(act).all())
             # ... and the statistics that rode in the payloads add up to every rank's env-steps so far
             st = gather.global_stats.cpu().numpy()
-            assert st[2] == float(n) * K * world * (warm_total + 2 * args.steps), st
+            assert st[2] == float(n) * K * world * steps_done, st
         dist.barrier()
         dist.destroy_process_group()
 

@@ -1,5 +1,5 @@
 """bench.py's bookkeeping (CPU): launch-time statistics, the source stamp of the PMC traffic figure and its staleness
-rule -- the parts of the measurement contract that do not need a GPU."""
+rule, the --dump-outputs sample and the option checks -- the parts of the measurement contract that do not need a GPU."""
 import json
 import os
 import sys
@@ -89,3 +89,43 @@ def test_bench_starts_its_own_ranks_when_there_is_no_launcher():
     if not torch.cuda.is_available():
         r, lines = _run_bench([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--backend", "gloo"])
         assert r.returncode != 0 and not lines
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample_of_the_last_step(tmp_path):
+    """--dump-outputs: the same seeded env sample every run, float32 / float64 only, at most 64 MB for the headline shape,
+    and DIR/<name>.npy reads back what was taken."""
+    import numpy as np
+    import torch
+    from smartstartcontinuous_amd import TransitionChunk
+
+    n, K = bench.N_ENVS_PER_GPU, bench.CHUNK
+    chunk = TransitionChunk(2, K, n, "cpu")
+    chunk._buf.copy_(torch.arange(chunk._buf.numel(), dtype=torch.float32).view_as(chunk._buf))
+    chunk.done.copy_((torch.arange(K * n) % 3 == 0).view(K, n).to(torch.uint8))
+
+    class Env:
+        s0 = torch.linspace(-1.2, 0.6, n)
+        s1 = torch.linspace(-0.07, 0.07, n)
+        stats = torch.tensor([-1.5, 2.0, float(n * K), 0.0], dtype=torch.float64)
+
+    a, b = bench.last_step_outputs(Env, chunk, torch), bench.last_step_outputs(Env, chunk, torch)
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    ids = a["env_ids"].astype(np.int64)
+    assert len(ids) == bench.DUMP_ENVS and len(np.unique(ids)) == len(ids) and 0 <= ids.min() and ids.max() < n
+    assert a["obs"].shape == (2, K, len(ids)) and a["act"].shape == (K, len(ids)) and a["state_pos"].shape == (len(ids),)
+    assert np.array_equal(a["obs2"], chunk.obs2.numpy()[:, :, ids]) and np.array_equal(a["done"], chunk.done.numpy()[:, ids])
+    assert np.array_equal(a["state_vel"], Env.s1.numpy()[ids]) and np.array_equal(a["stats"], Env.stats.numpy())
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    bench.write_outputs(str(tmp_path / "out"), a)
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(k + ".npy" for k in a)
+    assert all(np.array_equal(np.load(tmp_path / "out" / (k + ".npy")), a[k]) for k in a)
+
+
+def test_plain_run_rejects_options_that_need_full_or_another_config():
+    """--series-out records the --full run's launches; --dump-outputs belongs to the headline path.  Both are refused
+    at argument parsing, before anything touches a GPU."""
+    r, lines = _run_bench([sys.executable, "bench.py", "--steps", "2", "--series-out", "x.csv"])
+    assert r.returncode == 2 and not lines and "--full" in r.stderr
+    r, lines = _run_bench([sys.executable, "bench.py", "--config", "3", "--dump-outputs", "d"])
+    assert r.returncode == 2 and not lines and "--dump-outputs" in r.stderr

@@ -4,7 +4,7 @@
 set -u
 export TMPDIR=/tmp
 O=gpurun_out/gather_ab; mkdir -p $O
-COMMON="--force-dist --steps 40 --warmup 5 --no-cpu-baseline --no-single-step --no-other-configs --steady-launches 0"
+COMMON="--full --force-dist --steps 40 --warmup 5 --no-cpu-baseline --no-single-step --no-other-configs --steady-launches 0"
 run() { local name=$1; shift; timeout -k 10 200 python3 bench.py $COMMON "$@" > $O/$name.json 2> $O/$name.err; python3 - "$name" "$O/$name.json" <<'PY'
 import json, sys
 for l in open(sys.argv[2]):

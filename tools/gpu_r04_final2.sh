@@ -20,4 +20,4 @@ step c5_kt 200 rocprofv3 --kernel-trace --stats --output-format csv -d $P/mpc_re
 step c5_pmc 200 rocprofv3 --pmc $SQV --output-format csv -d $P/mpc_ref/pmc_sq -- python3 bench.py --config 5 --steps 5 --warmup 2 --settle-launches 0 > $P/mpc_ref/pmc_sq.log 2>&1
 step ssvec_plain 200 bash -c "python3 tools/prof_smartstart_vec.py 40 2>&1 | tail -1 > $P/ssvec/unprofiled.txt; cut -c1-300 $P/ssvec/unprofiled.txt"
 step ssvec_kt 200 rocprofv3 --kernel-trace --stats --output-format csv -d $P/ssvec/kt -- python3 tools/prof_smartstart_vec.py 40 > $P/ssvec/out.txt 2>&1
-step default_bench 300 bash -c "python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; cut -c1-400 $O/bench_default.json"
+step default_bench 300 bash -c "python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cut -c1-400 $O/bench_default.json"
