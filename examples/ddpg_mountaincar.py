@@ -20,12 +20,12 @@ import smartstartcontinuous_amd as ssc  # noqa: E402
 from smartstartcontinuous_amd.agents import DDPG_Baselines_agent  # noqa: E402
 
 
-def make_agent(env, seed):
+def make_agent(env, seed, normalize_observations=False):
     return DDPG_Baselines_agent(env, None, buffer_size=100000, batch_size=64, num_train_iterations=50,
                                 num_steps_before_train=200, ou_epsilon=1.0, ou_min_epsilon=0.01,
                                 ou_epsilon_decay_factor=.99, ou_mu=0.4, ou_sigma=0.6, ou_theta=.15, actor_lr=0.001,
                                 actor_h1=64, actor_h2=32, critic_lr=0.001, critic_h1=64, critic_h2=32,
-                                lastLayerTanh=True, seed=seed)
+                                lastLayerTanh=True, normalize_observations=normalize_observations, seed=seed)
 
 
 def main():
@@ -39,17 +39,19 @@ def main():
                     help="vec: roll chunk i+1 on a second stream while the learner works on chunk i (one chunk stale)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--save-dir", default=None)
+    ap.add_argument("--normalize-observations", action="store_true",
+                    help="DDPG normalize_observations: networks see running-statistics-normalised observations")
     args = ap.parse_args()
     np.random.seed(args.seed)
     if args.mode == "single":
         env = ssc.Continuous_MountainCarEnv_Editted.make_timed_env(args.power_scalar, max_episode_steps=1000,
                                                                    seed=args.seed)
-        agent = make_agent(env, args.seed)
+        agent = make_agent(env, args.seed, args.normalize_observations)
         summary = ssc.rlTrain(agent, env, print_results=True, print_steps=False, num_episodes=args.episodes,
                               max_steps=1000)
     else:
         env = ssc.VecEnv("MountainCarContinuousActionX%s-v0" % args.power_scalar, args.envs, seed=args.seed)
-        agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed)
+        agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations)
         summary, losses, replay = ssc.rl_train_vec_ddpg(env, agent, num_chunks=args.chunks, chunk_steps=250,
                                                         replay_capacity=1 << 20, train_iters=50, overlap=args.overlap)
         goals = sum(1 for steps, ret in summary.episodes if ret > 0)

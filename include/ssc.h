@@ -600,6 +600,40 @@ int ssc_ddpg_train_ws(const ssc_ddpg_desc *ddpg, const ssc_replay_view *replay, 
                       int32_t n_iters, float *d_losses, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * normalize_observations (ddpg_editted.py:14-18, 100-109, 127-132, 281-285)
+ * -------------------------------------------------------------------------------------
+ * The running statistics of baselines 0.1.5 RunningMeanStd live in ONE device block of 2*obs_dim + 1 doubles,
+ *   d_rms = [sum[obs_dim] | sumsq[obs_dim] | count]      (caller-initialised: 0, 1e-2, 1e-2)
+ * Every network then sees clip((x - mean) / std, -obs_clip, obs_clip) with, in fp32,
+ *   mean = f32(sum / count),  std = sqrtf(max(f32(sumsq / count) - mean * mean, 1e-2f))   (no contraction).
+ * Kernels read the block when they start (never a host copy), so HIP graphs stay valid while it changes.
+ *
+ * ssc_obs_rms_update: adds sum(x), sum(x^2) and the row count (f64) of the obs0 columns of steps [k0, K) of a
+ * transition log of n envs (dense or packed row_stride) to d_rms.  ssc_obs_rms_update_rows: the same for a row-major
+ * [m][obs_dim] matrix.  Deterministic run to run (fixed-order reduction, no atomics); d_workspace holds
+ * ssc_obs_rms_update_workspace_bytes(obs_dim) bytes and may be reused once the call's work is done in stream order.
+ *
+ * The *_rms variants are the calls above plus a trailing d_rms; d_rms == NULL behaves exactly like the plain call.
+ * ssc_rollout_rms reads the block once per launch (the statistics are frozen for the chunk, like the weights); a
+ * random policy ignores it. */
+size_t ssc_obs_rms_update_workspace_bytes(int32_t obs_dim);
+int ssc_obs_rms_update(int32_t obs_dim, const ssc_transition_log *log, int32_t k0, int32_t K, int64_t n, double *d_rms,
+                       void *d_workspace, size_t workspace_bytes, ssc_stream_t stream);
+int ssc_obs_rms_update_rows(int32_t obs_dim, int64_t m, const float *d_x, double *d_rms, void *d_workspace,
+                            size_t workspace_bytes, ssc_stream_t stream);
+int ssc_actor_forward_rms(const ssc_actor_desc *actor, int64_t m, const float *d_obs, float *d_act, ssc_stream_t stream,
+                          const double *d_rms);
+int ssc_critic_forward_rms(const ssc_critic_desc *critic, int64_t m, const float *d_obs, const float *d_act, float *d_q,
+                           ssc_stream_t stream, const double *d_rms);
+int ssc_rollout_rms(const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n, int32_t K,
+                    const ssc_rollout_state *state, const ssc_transition_log *log,
+                    const ssc_episode_ring *ring, double *d_stats, uint64_t seed, uint64_t env_id0,
+                    uint64_t step0, ssc_stream_t stream, const double *d_rms);
+int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *ddpg, const ssc_replay_view *replay, const int32_t *d_batch_idx,
+                          int32_t n_iters, float *d_losses, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream,
+                          const double *d_rms);
+
+/* ---------------------------------------------------------------------------------------
  * Dynamics-model training step
  * ------------------------------------------------------------------------------------- */
 

@@ -185,6 +185,18 @@ _SIGNATURES = {
     "ssc_ddpg_train_workspace_bytes": (c_size_t, [POINTER(DdpgDesc)]),
     "ssc_ddpg_train_ws": (c_int, [POINTER(DdpgDesc), POINTER(ReplayView), c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),
+    # normalize_observations: the RunningMeanStd block and the *_rms variants (trailing const double *d_rms)
+    "ssc_obs_rms_update_workspace_bytes": (c_size_t, [c_int32]),
+    "ssc_obs_rms_update": (c_int, [c_int32, POINTER(TransitionLog), c_int32, c_int32, c_int64, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
+    "ssc_obs_rms_update_rows": (c_int, [c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ssc_actor_forward_rms": (c_int, [POINTER(ActorDesc), c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssc_critic_forward_rms": (c_int, [POINTER(CriticDesc), c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ssc_rollout_rms": (c_int, [POINTER(EnvParams), POINTER(PolicyDesc), c_int64, c_int32, POINTER(RolloutState),
+                                POINTER(TransitionLog), POINTER(EpisodeRing), c_void_p, c_uint64, c_uint64, c_uint64, c_void_p,
+                                c_void_p]),
+    "ssc_ddpg_train_ws_rms": (c_int, [POINTER(DdpgDesc), POINTER(ReplayView), c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
+                                      c_void_p, c_void_p]),
     "ssc_dataset_scan_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_dataset_scan": (c_int, [POINTER(TransitionLog), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),

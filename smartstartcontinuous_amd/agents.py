@@ -21,6 +21,7 @@ from . import _ffi, navigator
 from .numerical import (distances_left, elliptical_euclidean_distance_function_generator,
                         get_start_waypoints_final_states_steps, path_deltas_stds_and_means_per_dim,
                         path_shortcutter, radii_calc)
+from .obs_rms import ObsRms
 from .replay_buffer import ReplayBuffer
 from .vec_env import ActorPolicy
 
@@ -176,9 +177,9 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         args = dict(locals())
         self.param_dict = {k: (v if isinstance(v, (int, float, bool, str, type(None))) else "Not serializable")
                            for k, v in args.items() if k not in ("self", "__class__")}   # :135-137
-        if normalize_observations or normalize_returns or enable_popart:
-            raise NotImplementedError("observation & return normalisation / popart are not on the "
-                                      "accelerated path (every shipped run uses False)")
+        if normalize_returns or enable_popart:
+            raise NotImplementedError("return normalisation / popart are not on the accelerated path "
+                                      "(every shipped run uses False)")
         self.layer_norm = bool(layer_norm)      # models_editted.py:45-46, 50-51, 85-86, 91-92 (fp32 kernels)
         if self.layer_norm:
             precision = "f32"
@@ -208,6 +209,8 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         aw, cw = init_actor_weights(obs_dim, actor_h1, actor_h2, nb_actions, gen), init_critic_weights(obs_dim, critic_h1, critic_h2, nb_actions, gen)
         if self.layer_norm:
             aw, cw = with_layer_norm(aw), with_layer_norm(cw)
+        # normalize_observations (ddpg_editted.py:100-109): the running obs statistics every network input goes through
+        self.obs_rms = ObsRms(obs_dim, self.device) if normalize_observations else None
         self.set_weights(aw)
         self.set_critic_weights(cw)
         self.decaying_ou_action_noise = DecayingOrnsteinUhlenbeckActionNoise(
@@ -260,23 +263,40 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             c.ln1_g, c.ln1_b, c.ln2_g, c.ln2_b = (w[k].data_ptr() for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b"))
         self._critic_desc = c
 
-    def critic(self, obs, act):
-        """Critic_Editted forward: Q(obs [m, obs_dim], act [m, act_dim]) -> [m]."""
+    def _rms_block(self, obs_rms=None):
+        """The statistics block the networks read: ``obs_rms`` (an ObsRms or its f64 tensor), else the agent's own."""
+        r = self.obs_rms if obs_rms is None else obs_rms
+        return r.block if isinstance(r, ObsRms) else r
+
+    def critic(self, obs, act, obs_rms=None):
+        """Critic_Editted forward: Q(obs [m, obs_dim], act [m, act_dim]) -> [m].  With observation statistics (the
+        agent's, or ``obs_rms``) the network sees clip((obs - mean) / std)."""
         o = torch.as_tensor(obs, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
         a = torch.as_tensor(act, dtype=torch.float32, device=self.device).reshape(o.shape[0], -1).contiguous()
         q = torch.empty(o.shape[0], dtype=torch.float32, device=self.device)
+        rms = self._rms_block(obs_rms)
         with torch.cuda.device(self.device):
-            _ffi.check(self.lib.ssc_critic_forward(ctypes.byref(self._critic_desc), o.shape[0], _ffi.ptr(o),
-                                                   _ffi.ptr(a), _ffi.ptr(q), _stream()))
+            if rms is None:
+                _ffi.check(self.lib.ssc_critic_forward(ctypes.byref(self._critic_desc), o.shape[0], _ffi.ptr(o),
+                                                       _ffi.ptr(a), _ffi.ptr(q), _stream()))
+            else:
+                _ffi.check(self.lib.ssc_critic_forward_rms(ctypes.byref(self._critic_desc), o.shape[0], _ffi.ptr(o),
+                                                           _ffi.ptr(a), _ffi.ptr(q), _stream(), _ffi.ptr(rms)))
         return q
 
-    def actor(self, obs):
-        """Actor_Editted forward (models_editted.py:38-61) on a batch: obs [m, obs_dim] -> [m, act_dim]."""
+    def actor(self, obs, obs_rms=None):
+        """Actor_Editted forward (models_editted.py:38-61) on a batch: obs [m, obs_dim] -> [m, act_dim] (normalised
+        observations as in :meth:`critic`)."""
         o = torch.as_tensor(obs, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
         out = torch.empty((o.shape[0], self.act_dim), dtype=torch.float32, device=self.device)
+        rms = self._rms_block(obs_rms)
         with torch.cuda.device(self.device):
-            _ffi.check(self.lib.ssc_actor_forward(ctypes.byref(self._desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
-                                                  _stream()))
+            if rms is None:
+                _ffi.check(self.lib.ssc_actor_forward(ctypes.byref(self._desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
+                                                      _stream()))
+            else:
+                _ffi.check(self.lib.ssc_actor_forward_rms(ctypes.byref(self._desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
+                                                          _stream(), _ffi.ptr(rms)))
         return out
 
     # ---- RLAgent ---------------------------------------------------------------------------
@@ -294,16 +314,17 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         action = np.clip(action, -1.0, 1.0)                    # :271
         return self.scale(self.scale(action))
 
-    def as_policy(self, precision=None, device_epsilon=False):
+    def as_policy(self, precision=None, device_epsilon=False, obs_rms=None):
         """The same action path as a fused-rollout policy (current epsilon).  ``device_epsilon``: the kernel reads
-        epsilon from ``self.d_epsilon`` (kept current by a :class:`rl_train.DecaySchedule`) instead of the host value."""
+        epsilon from ``self.d_epsilon`` (kept current by a :class:`rl_train.DecaySchedule`) instead of the host value.
+        With observation statistics (the agent's, or ``obs_rms``) the rollout reads them once per launch."""
         n = self.decaying_ou_action_noise
         if "ln1_g" in self.weights:
             precision = "f32"                    # LayerNorm networks run on the fp32 kernels
         return ActorPolicy(self.weights, last_layer_tanh=self.lastLayerTanh, precision=precision or "bf16_mfma",
                            ou_mu=float(self.ou["mu"]), ou_sigma=float(self.ou["sigma"]), ou_theta=float(self.ou["theta"]),
                            ou_dt=n.dt, ou_epsilon=float(max(n.epsilon, 0)), obs_clip=float(self.observation_range[1]),
-                           d_ou_epsilon=self.d_epsilon if device_epsilon else None)
+                           d_ou_epsilon=self.d_epsilon if device_epsilon else None, d_obs_rms=self._rms_block(obs_rms))
 
     def get_state_value(self, state):
         """:197-204 -> DDPG_editted.get_q_value (ddpg_editted.py:274-279): Q(s, pi(s)) without noise.
@@ -316,11 +337,13 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         """Q(s, pi(s)) for a batch of states as a DEVICE tensor [m] (no host round trip: the SmartStart selection of the
         vectorised loop feeds candidate states gathered from the device replay ring)."""
         o = torch.as_tensor(state, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim)
-        return self.critic(o, self.actor(o)).reshape(-1)
+        return self.critic(o, self.actor(o)).reshape(-1)     # (both with the agent's observation statistics, if any)
 
     def observe(self, state, action, reward, new_state, done):
         """:242-247 (store_transition, ddpg_editted.py:281-285)"""
         self.replay_buffer.add(self, state, action, reward * self.reward_scale, done, new_state)
+        if self.obs_rms is not None:                            # store_transition: obs_rms.update(np.array([obs0]))
+            self.obs_rms.update_rows(np.asarray(state, np.float32).reshape(1, -1))
         self.remaining_steps_before_train -= 1
         if self.training_enabled and self.remaining_steps_before_train <= 0:
             self.train()
@@ -361,9 +384,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         d.critic_l2_reg, d.clip_norm = self.critic_l2_reg, 0.0 if self.clip_norm is None else float(self.clip_norm)
         return d
 
-    def train_on(self, s, a, r, t, s2, batch_idx, n_iters):
+    def train_on(self, s, a, r, t, s2, batch_idx, n_iters, obs_rms=None):
         """``n_iters`` x (DDPG_editted.train + update_target_net) on device replay arrays; ``batch_idx``
-        int32 [n_iters, batch_size].  Returns the (critic_loss, actor_loss) tensor [n_iters, 2]."""
+        int32 [n_iters, batch_size].  Returns the (critic_loss, actor_loss) tensor [n_iters, 2].  With observation
+        statistics (the agent's, or ``obs_rms``) the raw s / s2 enter the networks normalised."""
         rv = _ffi.ReplayView(s.data_ptr(), a.data_ptr(), r.data_ptr(), t.data_ptr(), s2.data_ptr(), s.shape[0])
         losses = torch.empty((n_iters, 2), dtype=torch.float32, device=self.device)
         d = self.ddpg_desc()
@@ -375,8 +399,13 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             ws = getattr(self, "_train_ws", None)
             if ws is None or ws.numel() < need:
                 ws = self._train_ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
-            _ffi.check(self.lib.ssc_ddpg_train_ws(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
-                                                  _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream()))
+            rms = self._rms_block(obs_rms)
+            if rms is None:
+                _ffi.check(self.lib.ssc_ddpg_train_ws(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
+                                                      _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream()))
+            else:
+                _ffi.check(self.lib.ssc_ddpg_train_ws_rms(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
+                                                          _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream(), _ffi.ptr(rms)))
         return losses
 
     def train_from(self, device_replay, n_iters=None):

@@ -33,6 +33,45 @@ struct ActorWeights {
 __device__ __forceinline__ float clip_obs(float x, float c) { return c > 0.0f ? fminf(fmaxf(x, -c), c) : x; }
 
 // ---------------------------------------------------------------------------------------
+// normalize_observations (ddpg_editted.py:100-109): every network input is clip((x - mean) / std, -c, c) with the
+// statistics of baselines' RunningMeanStd (common/mpi_running_mean_std.py, restated in DESIGN section 5).  The device
+// block is f64 [sum[D] | sumsq[D] | count]; the derived values follow TF's graph in fp32:
+//   mean = f32(sum / count),  std = sqrt(max(f32(sumsq / count) - mean * mean, 1e-2))
+// with a plain multiply and subtract (no contraction) and correctly rounded division / square root.
+// Kernels take the block as ONE extra trailing `const double *` argument, spelled as a parameter pack: with an empty
+// pack a kernel keeps its existing parameter list and code (normalisation is a compile-time choice).
+template <class... Rms> inline constexpr bool kObsNorm = sizeof...(Rms) > 0;
+template <class... Rms> __device__ __forceinline__ const double *rms_block(Rms... r) {
+    if constexpr (sizeof...(Rms) > 0) return (r, ...);
+    else return nullptr;
+}
+
+template <int N>
+struct ObsNorm {
+    float mean[N], std[N];
+    // every thread reads the block itself (wave-uniform addresses: scalar loads); obs_dim <= N
+    __device__ __forceinline__ void load(const double *__restrict__ rms, int obs_dim) {
+#pragma clang fp contract(off)
+        const double cnt = rms[2 * obs_dim];
+#pragma unroll
+        for (int c = 0; c < N; ++c) {
+            if (c < obs_dim) {
+                mean[c] = (float)(rms[c] / cnt);
+                const float sq = (float)(rms[obs_dim + c] / cnt);
+                std[c] = sqrtf(fmaxf(sq - mean[c] * mean[c], 1e-2f));   // (hipcc's default sqrtf / division: correctly rounded)
+            } else {
+                mean[c] = 0.0f;
+                std[c] = 1.0f;
+            }
+        }
+    }
+    // the network input of observation component c: normalised, then clipped like the raw one is without normalisation
+    __device__ __forceinline__ float apply(float x, int c, float clip) const {
+        return clip_obs((x - mean[c]) / std[c], clip);
+    }
+};
+
+// ---------------------------------------------------------------------------------------
 // fp32 VALU path
 // ---------------------------------------------------------------------------------------
 template <int OBS, int H1, int H2>

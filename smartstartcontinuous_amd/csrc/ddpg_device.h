@@ -37,13 +37,13 @@ struct AdamCfg {
 // ddpg_train_fixed.hip
 bool ddpg_fixed_shape(const ssc_ddpg_desc *d);
 int ddpg_train_fixed(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
-                     float *d_losses, hipStream_t stream);
+                     float *d_losses, hipStream_t stream, const double *d_rms);
 
 // the shipped shape at batches of 128, 192, ... (multiples of 64): the straight-line kernel on one 64-row tile per workgroup
 // (gradients only), then the multi-workgroup apply pass of ddpg_train_wide.hip
 bool ddpg_fixed_tiled_shape(const ssc_ddpg_desc *d);
 int ddpg_train_fixed_tiled(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
-                           float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream);
+                           float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms);
 
 // ddpg_train_wide.hip: any layer sizes / batch sizes, batch tiled over workgroups
 size_t ddpg_wide_workspace_bytes(const ssc_ddpg_desc *d);
@@ -54,7 +54,8 @@ struct WidePartials { float *gpart, *lpart; };
 WidePartials ddpg_wide_partials(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks);
 void ddpg_wide_apply(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks, int it, float *d_losses_it, hipStream_t stream);
 void ddpg_wide_finish(const ssc_ddpg_desc *d, int32_t n_iters, hipStream_t stream);
+// d_rms (all three): NULL, or the RunningMeanStd block of normalize_observations (actor_device.h)
 int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
-                    float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream);
+                    float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms);
 
 }  // namespace ssc

@@ -662,11 +662,21 @@ extern "C" size_t ssc_ddpg_train_workspace_bytes(const ssc_ddpg_desc *d) {
 // need a workspace.  SSC_DDPG_INTERPRETER=1 / SSC_DDPG_WIDE=1 force a path (A/B measurements, and the tests that
 // check every path against the oracle on the shipped shape).
 static int ddpg_train_any(const char *who, const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
-                          int32_t n_iters, float *d_losses, void *d_ws, size_t ws_bytes, bool have_ws, ssc_stream_t stream);
+                          int32_t n_iters, float *d_losses, void *d_ws, size_t ws_bytes, bool have_ws, ssc_stream_t stream,
+                          const double *d_rms = nullptr);
 
 extern "C" int ssc_ddpg_train_ws(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                                  float *d_losses, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream) {
     return ddpg_train_any("ssc_ddpg_train_ws", d, rp, d_batch_idx, n_iters, d_losses, d_workspace, workspace_bytes, true, stream);
+}
+
+// normalize_observations: obs0 / obs1 enter every network as clip((x - mean) / std) of the RunningMeanStd block d_rms
+// (actor_device.h); the replay keeps the raw observations
+extern "C" int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
+                                     float *d_losses, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream,
+                                     const double *d_rms) {
+    return ddpg_train_any("ssc_ddpg_train_ws_rms", d, rp, d_batch_idx, n_iters, d_losses, d_workspace, workspace_bytes, true, stream,
+                          d_rms);
 }
 
 extern "C" int ssc_ddpg_train(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
@@ -675,7 +685,8 @@ extern "C" int ssc_ddpg_train(const ssc_ddpg_desc *d, const ssc_replay_view *rp,
 }
 
 static int ddpg_train_any(const char *who, const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
-                          int32_t n_iters, float *d_losses, void *d_ws, size_t ws_bytes, bool have_ws, ssc_stream_t stream) {
+                          int32_t n_iters, float *d_losses, void *d_ws, size_t ws_bytes, bool have_ws, ssc_stream_t stream,
+                          const double *d_rms) {
     SSC_REQUIRE(d && rp, "%s: NULL descriptor", who);
     SSC_REQUIRE(n_iters >= 0, "%s: n_iters < 0", who);
     SSC_REQUIRE(d->batch_size >= 1, "%s: batch_size %d", who, d->batch_size);
@@ -699,9 +710,12 @@ static int ddpg_train_any(const char *who, const ssc_ddpg_desc *d, const ssc_rep
                 "%s: NULL replay pointer", who);
     // the shipped 64-32 networks at a batch of several 64-row tiles: the straight-line kernel per tile, then the apply pass
     if (have_ws && !want_wide && !want_interp && ddpg_fixed_tiled_shape(d))
-        return ddpg_train_fixed_tiled(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream));
-    if (!narrow || want_wide) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream));
-    if (ddpg_fixed_shape(d) && !want_interp) return ddpg_train_fixed(d, rp, d_batch_idx, n_iters, d_losses, as_stream(stream));
+        return ddpg_train_fixed_tiled(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), d_rms);
+    if (!narrow || want_wide) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), d_rms);
+    if (ddpg_fixed_shape(d) && !want_interp) return ddpg_train_fixed(d, rp, d_batch_idx, n_iters, d_losses, as_stream(stream), d_rms);
+    // the step interpreter below has no normalising build: with statistics its shapes run on the multi-workgroup kernels
+    // (d_rms comes only through ssc_ddpg_train_ws_rms, which has a workspace)
+    if (d_rms != nullptr) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), d_rms);
 
     const NetDims A{d->obs_dim, d->actor_h1, d->actor_h2, d->act_dim, 0};
     const NetDims C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim};
@@ -732,7 +746,7 @@ static int ddpg_train_any(const char *who, const ssc_ddpg_desc *d, const ssc_rep
     g.off_theta[0] = TA; g.off_theta[1] = TC; g.off_theta[2] = TTA; g.off_theta[3] = TTC;
     p = TTC + C.total();
     if ((size_t)p * sizeof(float) > 160 * 1024 - 128) { // 64 B of static LDS (loss partials, Adam step sizes)
-        if (have_ws) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream));
+        if (have_ws) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), nullptr);
         return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: these layer sizes need %zu B of LDS on the single-workgroup path; "
                                            "call ssc_ddpg_train_ws", (size_t)p * sizeof(float));
     }

@@ -31,6 +31,7 @@
 //   L7  critic layer-1 delta [MFMA]; actor layer-2 delta                                                           B
 //   L8  actor layer-1 delta [MFMA]; critic gradients + Adam + target update [MFMA + one small element per lane]   B
 //   L9  actor gradients + Adam + target update [MFMA + small]; losses out                                         B
+#include "actor_device.h"
 #include "ddpg_device.h"
 #include "ssc_host.h"
 
@@ -242,8 +243,11 @@ __device__ __forceinline__ float small_grad(const float *lds, const SmallElem &e
 
 // TILED: the same ten levels on rows [64 blockIdx.x, + 64) of a larger batch, up to the gradients -- which go to the tile's
 // slice of `gpart` instead of into MpiAdam (ddpg_wide_apply_kernel sums the slices in tile order and updates).
-template <int O, bool TANH2, bool TILED>
-__global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g) {
+//
+// Rms (normalize_observations): the RunningMeanStd block; its loads go out with the parameter images, mean / std are
+// derived once per launch, and obs0 / obs1 enter the networks as clip((x - mean) / std) (actor_device.h).
+template <int O, bool TANH2, bool TILED, class... Rms>
+__global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms... rms) {
     using NA = Net<O, H1>;
     using NC = Net<O, H1 + 1>;
     using R = Rows<O>;
@@ -349,6 +353,8 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g) {
         fetch_rows(rec0);
         if constexpr (!TILED) rec_next = idx_of(1);
     }
+    ObsNorm<O> nrm;
+    if constexpr (kObsNorm<Rms...>) nrm.load(rms_block(rms...), O);
     __syncthreads();   // parameter images complete
 
     float r_cur = 0.0f, t_cur = 0.0f;
@@ -366,8 +372,13 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g) {
         if (tid < kB) {
 #pragma unroll
             for (int k = 0; k < O; ++k) {   // obs0 / obs1 enter every network clipped (ddpg_editted.py:106-109)
-                row(R::S + k)[tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s[k], -d.obs_clip), d.obs_clip) : pf_s[k];
-                row(R::S2 + k)[tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s2[k], -d.obs_clip), d.obs_clip) : pf_s2[k];
+                if constexpr (kObsNorm<Rms...>) {
+                    row(R::S + k)[tid] = nrm.apply(pf_s[k], k, d.obs_clip);
+                    row(R::S2 + k)[tid] = nrm.apply(pf_s2[k], k, d.obs_clip);
+                } else {
+                    row(R::S + k)[tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s[k], -d.obs_clip), d.obs_clip) : pf_s[k];
+                    row(R::S2 + k)[tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s2[k], -d.obs_clip), d.obs_clip) : pf_s2[k];
+                }
             }
             row(R::X2 + H1)[tid] = pf_a;
             r_cur = pf_r;
@@ -568,16 +579,16 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g) {
     if (tid == 0) { d.adam_t[0] = tA; d.adam_t[1] = tC; }
 }
 
-template <int O, bool TANH2, bool TILED = false>
-int launch_fixed(const FixedArgs &g, hipStream_t stream, unsigned tiles = 1) {
+template <int O, bool TANH2, bool TILED = false, class... Rms>
+int launch_fixed(const FixedArgs &g, hipStream_t stream, unsigned tiles = 1, Rms... rms) {
     const size_t lds = ((size_t)Rows<O>::total * kP + 2 * (Net<O, H1>::size + Net<O, H1 + 1>::size)) * sizeof(float);
     static_assert(((size_t)Rows<O>::total * kP + 2 * (Net<O, H1>::size + Net<O, H1 + 1>::size)) * sizeof(float) <= 160 * 1024 - 256,
                   "activation rows + parameter images must fit the LDS");
-    int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_train_fixed_kernel<O, TANH2, TILED>),
+    int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_train_fixed_kernel<O, TANH2, TILED, Rms...>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
                        "hipFuncSetAttribute(ddpg_train_fixed_kernel)");
     if (rc) return rc;
-    hipLaunchKernelGGL((ddpg_train_fixed_kernel<O, TANH2, TILED>), dim3(tiles), dim3(kT), lds, stream, g);
+    hipLaunchKernelGGL((ddpg_train_fixed_kernel<O, TANH2, TILED, Rms...>), dim3(tiles), dim3(kT), lds, stream, g, rms...);
     return check_launch("ssc_ddpg_train");
 }
 
@@ -600,7 +611,7 @@ bool ddpg_fixed_tiled_shape(const ssc_ddpg_desc *d) {
 // arguments already validated by ssc_ddpg_train_ws; the workspace is sized by ddpg_wide_workspace_bytes (16-row partials:
 // four times what the 64-row tiles write)
 int ddpg_train_fixed_tiled(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
-                           float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream) {
+                           float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms) {
     const size_t need = ddpg_wide_workspace_bytes(d);
     SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= need,
                 "ssc_ddpg_train_ws: workspace %zu < %zu bytes (ssc_ddpg_train_workspace_bytes)", workspace_bytes, need);
@@ -611,7 +622,10 @@ int ddpg_train_fixed_tiled(const ssc_ddpg_desc *d, const ssc_replay_view *rp, co
     for (int it = 0; it < n_iters; ++it) {
         g.batch_idx = d_batch_idx + (int64_t)it * d->batch_size;
         int rc;
-        if (d->obs_dim == 2) rc = t2 ? launch_fixed<2, true, true>(g, stream, tiles) : launch_fixed<2, false, true>(g, stream, tiles);
+        if (d_rms != nullptr) {
+            if (d->obs_dim == 2) rc = t2 ? launch_fixed<2, true, true>(g, stream, tiles, d_rms) : launch_fixed<2, false, true>(g, stream, tiles, d_rms);
+            else rc = t2 ? launch_fixed<3, true, true>(g, stream, tiles, d_rms) : launch_fixed<3, false, true>(g, stream, tiles, d_rms);
+        } else if (d->obs_dim == 2) rc = t2 ? launch_fixed<2, true, true>(g, stream, tiles) : launch_fixed<2, false, true>(g, stream, tiles);
         else rc = t2 ? launch_fixed<3, true, true>(g, stream, tiles) : launch_fixed<3, false, true>(g, stream, tiles);
         if (rc) return rc;
         ddpg_wide_apply(d, d_workspace, tiles, it, d_losses ? d_losses + 2 * it : nullptr, stream);
@@ -622,9 +636,13 @@ int ddpg_train_fixed_tiled(const ssc_ddpg_desc *d, const ssc_replay_view *rp, co
 
 // arguments already validated by ssc_ddpg_train
 int ddpg_train_fixed(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
-                     float *d_losses, hipStream_t stream) {
+                     float *d_losses, hipStream_t stream, const double *d_rms) {
     FixedArgs g{*d, *rp, d_batch_idx, d_losses, n_iters, 1.0f / (float)kB, nullptr, nullptr};
     const bool t2 = d->last_layer_tanh != 0;
+    if (d_rms != nullptr) {
+        if (d->obs_dim == 2) return t2 ? launch_fixed<2, true>(g, stream, 1, d_rms) : launch_fixed<2, false>(g, stream, 1, d_rms);
+        return t2 ? launch_fixed<3, true>(g, stream, 1, d_rms) : launch_fixed<3, false>(g, stream, 1, d_rms);
+    }
     if (d->obs_dim == 2) return t2 ? launch_fixed<2, true>(g, stream) : launch_fixed<2, false>(g, stream);
     return t2 ? launch_fixed<3, true>(g, stream) : launch_fixed<3, false>(g, stream);
 }

@@ -21,6 +21,7 @@
 // Two launches per training iteration (the iterations are a serial chain through the parameters); the Adam step
 // counters are read-only during the launch sequence (iteration index added on the fly) and advanced by one
 // one-thread launch at the end.
+#include "actor_device.h"
 #include "ddpg_device.h"
 #include "ssc_host.h"
 
@@ -331,7 +332,9 @@ __device__ __forceinline__ void ln_level(const WideTables *T, int first, int end
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a) {
+// Rms (normalize_observations): the RunningMeanStd block; obs0 / obs1 enter the networks as clip((x - mean) / std)
+template <class... Rms>
+__global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a, Rms... rms) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef SSC_WIDE_DIAG
     const uint64_t t_entry = __builtin_amdgcn_s_memtime();
@@ -408,14 +411,25 @@ __global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a) {
     // last record and carry zero weight in every loss ----
     if (row_thread) {
         const int r = tid;
-        for (int k = 0; k < a.obs_dim; ++k) {   // obs0 / obs1 enter every network clipped (ddpg_editted.py:106-109)
-            float s = a.rp.s[rec * a.obs_dim + k], s2 = a.rp.s2[rec * a.obs_dim + k];
-            if (a.obs_clip > 0.0f) {
-                s = fminf(fmaxf(s, -a.obs_clip), a.obs_clip);
-                s2 = fminf(fmaxf(s2, -a.obs_clip), a.obs_clip);
+        if constexpr (kObsNorm<Rms...>) {
+            ObsNorm<SSC_MAX_STATE> nrm;
+            nrm.load(rms_block(rms...), a.obs_dim);
+#pragma unroll
+            for (int k = 0; k < SSC_MAX_STATE; ++k)
+                if (k < a.obs_dim) {
+                    lds[a.off_S + k * kWR + r] = nrm.apply(a.rp.s[rec * a.obs_dim + k], k, a.obs_clip);
+                    lds[a.off_S2 + k * kWR + r] = nrm.apply(a.rp.s2[rec * a.obs_dim + k], k, a.obs_clip);
+                }
+        } else {
+            for (int k = 0; k < a.obs_dim; ++k) {   // obs0 / obs1 enter every network clipped (ddpg_editted.py:106-109)
+                float s = a.rp.s[rec * a.obs_dim + k], s2 = a.rp.s2[rec * a.obs_dim + k];
+                if (a.obs_clip > 0.0f) {
+                    s = fminf(fmaxf(s, -a.obs_clip), a.obs_clip);
+                    s2 = fminf(fmaxf(s2, -a.obs_clip), a.obs_clip);
+                }
+                lds[a.off_S + k * kWR + r] = s;
+                lds[a.off_S2 + k * kWR + r] = s2;
             }
-            lds[a.off_S + k * kWR + r] = s;
-            lds[a.off_S2 + k * kWR + r] = s2;
         }
         for (int k = 0; k < a.act_dim; ++k) lds[a.off_ACT + k * kWR + r] = a.rp.a[rec * a.act_dim + k];
         lds[a.off_RT + RT_R * kWR + r] = a.rp.r[rec];
@@ -744,7 +758,7 @@ void ddpg_wide_finish(const ssc_ddpg_desc *d, int32_t n_iters, hipStream_t strea
 }
 
 int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
-                    float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream) {
+                    float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms) {
     if (d->batch_size < 1 || d->batch_size > 4096)
         return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: batch_size %d not in 1..4096", d->batch_size);
     const size_t need = ddpg_wide_workspace_bytes(d);
@@ -912,14 +926,16 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     g.gpart = static_cast<float *>(d_workspace);
     g.lpart = ddpg_wide_partials(d, d_workspace, nb).lpart;
     if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_wide_grad_kernel),
+        int rc = check_hip(hipFuncSetAttribute(d_rms != nullptr ? reinterpret_cast<const void *>(ddpg_wide_grad_kernel<const double *>)
+                                                                : reinterpret_cast<const void *>(ddpg_wide_grad_kernel<>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
                            "hipFuncSetAttribute(ddpg_wide_grad_kernel)");
         if (rc) return rc;
     }
     for (int it = 0; it < n_iters; ++it) {
         g.batch_idx = d_batch_idx + (int64_t)it * d->batch_size;
-        hipLaunchKernelGGL(ddpg_wide_grad_kernel, dim3(nb), dim3(kWThreads), lds, stream, g);
+        if (d_rms != nullptr) hipLaunchKernelGGL(ddpg_wide_grad_kernel<const double *>, dim3(nb), dim3(kWThreads), lds, stream, g, d_rms);
+        else hipLaunchKernelGGL(ddpg_wide_grad_kernel<>, dim3(nb), dim3(kWThreads), lds, stream, g);
         ddpg_wide_apply(d, d_workspace, nb, it, d_losses ? d_losses + 2 * it : nullptr, stream);
     }
     ddpg_wide_finish(d, n_iters, stream);

@@ -131,8 +131,12 @@ struct RandomPolicy {
 // OU [third-party baselines 0.1.5 ddpg/noise.py]: x += theta*(mu-x)*dt + sigma*sqrt(dt)*N(0,1).
 // One Philox call serves the gaussians of 4 consecutive steps (counter t >> 2, both Box-Muller outputs of both
 // word pairs: ou_gaussian_from_words).
-template <class Net, int OBS>
-struct ActorPolicy {
+// the statistics of a NORM policy; an empty base otherwise, so that the plain policy's layout (and code) stays as it was
+template <int OBS, bool NORM> struct PolicyNorm {};
+template <int OBS> struct PolicyNorm<OBS, true> { ObsNorm<OBS> nrm; };
+
+template <class Net, int OBS, bool NORM = false>
+struct ActorPolicy : PolicyNorm<OBS, NORM> {
     static constexpr bool kPipelined = false;
     static constexpr bool kFusedActor = false;
     static constexpr int kLanesPerEnv = Net::kLanesPerEnv;
@@ -162,7 +166,10 @@ struct ActorPolicy {
     __device__ float act(const float (&obs)[OBS], uint64_t seed, uint64_t env_id, uint64_t t, bool first) {
         float oc[OBS];   // the network sees the clipped observation (ddpg_editted.py:106-109); the log keeps the raw one
 #pragma unroll
-        for (int c = 0; c < OBS; ++c) oc[c] = clip_obs(obs[c], obs_clip);
+        for (int c = 0; c < OBS; ++c) {
+            if constexpr (NORM) oc[c] = this->nrm.apply(obs[c], c, obs_clip);   // the statistics of this launch
+            else oc[c] = clip_obs(obs[c], obs_clip);
+        }
         float a = net.forward(oc);
         if (noisy) {  // wave-uniform
             if (first || (t & 3) == 0) cache = rng_words(seed, env_id, t >> 2, TAG_OU);
@@ -178,6 +185,7 @@ struct ActorPolicy {
     __device__ void store(const RolloutArgs &ra, int64_t i) const {
         if (ra.st.ou_x != nullptr) ra.st.ou_x[i] = ou_x;
     }
+    __device__ void init_norm(const double *rms) { this->nrm.load(rms, OBS); }
 };
 
 // The same policy for the shape BASELINE config 3 runs (MountainCar: 2 observations, actor h1 <= 64 / h2 <= 32 on the
@@ -187,13 +195,19 @@ struct ActorPolicy {
 // that can run under the MFMAs and in the bubbles of the dependent action -> env.step chain is independent work of
 // the same wave, and the scheduler only moves code inside a basic block: the noise generation (half a Philox
 // evaluation + Box-Muller per step) is that work.
-template <bool LAST_TANH>
+//
+// NORM (normalize_observations): the network input is clip((obs - mean) / std); the statistics are read once per launch,
+// and the division is a multiply by 1 / std plus one residual correction (q = d r; q += (d - q std) r) -- the step body
+// is VALU-issue-bound, and the correctly rounded division is ~10 instructions more per component.  The corrected
+// quotient can differ from the correctly rounded one in the last bit.
+template <bool LAST_TANH, bool NORM = false>
 struct ActorPolicyFused {
     static constexpr bool kPipelined = false;
     static constexpr bool kFusedActor = true;
     static constexpr int kLanesPerEnv = 1;
     ActorMfma2<LAST_TANH> net;
     float ou_x, mu, sig_sqrt_dt, theta_dt, eps;
+    float n_mean[2], n_std[2], n_rstd[2], n_clip;   // NORM only
 
     __device__ void init(const PolicyArgs &pa, const RolloutArgs &ra, int64_t i) {
         net.init(pa.actor);
@@ -202,6 +216,7 @@ struct ActorPolicyFused {
         theta_dt = pa.ou_theta * pa.ou_dt;
         eps = pa.d_eps != nullptr ? fmaxf(*pa.d_eps, 0.0f) : pa.ou_eps;  // host value: > 0 (dispatch)
         ou_x = ra.st.ou_x[i];
+        if constexpr (NORM) n_clip = pa.actor.obs_clip;
     }
     // Box-Muller like gaussian_f32 in three pieces, so that the radius and the sin output of a word pair computed in
     // the even step are reused by the odd one.  -2 ln(u1) = (-2 ln 2) log2(u1) on the bare v_log_f32: u1 >= 2^-24 is
@@ -221,7 +236,19 @@ struct ActorPolicyFused {
     // spelled out: the step body exists in several copies (head, the four bodies of the main loop, tail) and
     // hipcc decides contraction per copy -- a rollout must not depend on how it was cut into chunks.
     __device__ __forceinline__ float act(const float (&obs)[2], float g) {
-        const float pre = net.forward_pre(obs[0], obs[1]);
+        float pre;
+        if constexpr (NORM) {
+            float o[2];
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const float d = obs[c] - n_mean[c];
+                const float q = d * n_rstd[c];
+                o[c] = clip_obs(fmaf(fmaf(-q, n_std[c], d), n_rstd[c], q), n_clip);
+            }
+            pre = net.forward_pre(o[0], o[1]);
+        } else {
+            pre = net.forward_pre(obs[0], obs[1]);
+        }
         ou_x = fmaf(sig_sqrt_dt, g, fmaf(theta_dt, mu - ou_x, ou_x));
         const float a = fmaf(ou_x, eps, tanh_fast(pre));  // ddpg_editted.py:267-270
         // clip (:271); scale(scale(.)) (DDPG_Baselines_agent.py:236-240) is the identity on a clipped action for
@@ -231,6 +258,12 @@ struct ActorPolicyFused {
     __device__ float from_word(uint32_t) const { return 0.0f; }
     __device__ void on_reset() { ou_x = 0.0f; }
     __device__ void store(const RolloutArgs &ra, int64_t i) const { ra.st.ou_x[i] = ou_x; }
+    __device__ void init_norm(const double *rms) {
+        ObsNorm<2> nrm;
+        nrm.load(rms, 2);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) { n_mean[c] = nrm.mean[c]; n_std[c] = nrm.std[c]; n_rstd[c] = 1.0f / nrm.std[c]; }
+    }
 };
 
 // (wave-uniform row pointer) + (32-bit per-lane byte offset) as the SGPR-base form of global_store: the row pointer
@@ -353,8 +386,8 @@ struct Rollout {
     }
 };
 
-template <class EnvT, class PolT, bool LOG, bool ONEBASE = false>
-__global__ __launch_bounds__(kBlock) void rollout_kernel(typename EnvT::Const ec, PolicyArgs pa, RolloutArgs ra) {
+template <class EnvT, class PolT, bool LOG, bool ONEBASE = false, class... Rms>
+__global__ __launch_bounds__(kBlock) void rollout_kernel(typename EnvT::Const ec, PolicyArgs pa, RolloutArgs ra, Rms... rms) {
     constexpr int LPE = PolT::kLanesPerEnv;
     constexpr int kEnvsPerBlock = kBlock / LPE;
     // LPE == 2: a wave covers 32 envs, env j of the wave lives on lanes j and j+32
@@ -377,6 +410,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(typename EnvT::Const ec
     r.el = ra.st.steps[i];
     r.ep_ret = ra.st.ep_ret[i];
     r.pol.init(pa, ra, i);
+    if constexpr (kObsNorm<Rms...>) r.pol.init_norm(rms_block(rms...));
     r.env.observe(r.obs);
     r.sum_r = 0.0f;
     r.n_goal = 0;
@@ -492,9 +526,9 @@ static void set_one_base(RolloutArgs &ra, int obs_dim) {
     }
 }
 
-template <class EnvT, class PolT>
+template <class EnvT, class PolT, class... Rms>
 static int launch_rollout(const typename EnvT::Const &ec, const PolicyArgs &pa, const RolloutArgs &ra,
-                          hipStream_t stream) {
+                          hipStream_t stream, Rms... rms) {
     const dim3 grid(blocks_for(ra.n, kBlock / PolT::kLanesPerEnv));
     // One running row pointer + per-column lane offsets (ONEBASE) takes ~30 scalar address instructions out of every
     // step: 12 % faster for the actor policies, whose step is instruction-bound (0.254 -> 0.224 ms per 65 536 x 256).
@@ -504,30 +538,32 @@ static int launch_rollout(const typename EnvT::Const &ec, const PolicyArgs &pa, 
     // of per-step jitter, fell into step with each other.  It keeps the per-column pointers.
     constexpr bool kOneBase = !PolT::kPipelined;
     if (ra.has_log && ra.one_base && kOneBase)
-        hipLaunchKernelGGL((rollout_kernel<EnvT, PolT, true, kOneBase>), grid, dim3(kBlock), 0, stream, ec, pa, ra);
+        hipLaunchKernelGGL((rollout_kernel<EnvT, PolT, true, kOneBase, Rms...>), grid, dim3(kBlock), 0, stream, ec, pa, ra, rms...);
     else if (ra.has_log)
-        hipLaunchKernelGGL((rollout_kernel<EnvT, PolT, true>), grid, dim3(kBlock), 0, stream, ec, pa, ra);
+        hipLaunchKernelGGL((rollout_kernel<EnvT, PolT, true, false, Rms...>), grid, dim3(kBlock), 0, stream, ec, pa, ra, rms...);
     else
-        hipLaunchKernelGGL((rollout_kernel<EnvT, PolT, false>), grid, dim3(kBlock), 0, stream, ec, pa, ra);
+        hipLaunchKernelGGL((rollout_kernel<EnvT, PolT, false, false, Rms...>), grid, dim3(kBlock), 0, stream, ec, pa, ra, rms...);
     return check_launch("ssc_rollout");
 }
 
 int validate_mc_params(const ssc_env_params *p, const char *who);  // env_step.hip
 
-template <class EnvT>
+// Rms: empty, or the RunningMeanStd block of normalize_observations (every actor policy then has a NORM instantiation)
+template <class EnvT, class... Rms>
 static int dispatch_policy(const typename EnvT::Const &ec, const ssc_policy_desc *pol, const PolicyArgs &pa,
-                           const RolloutArgs &ra, hipStream_t stream) {
+                           const RolloutArgs &ra, hipStream_t stream, Rms... rms) {
     constexpr int OBS = EnvT::OBS;
-    if (pol->kind == SSC_POLICY_RANDOM) return launch_rollout<EnvT, RandomPolicy<OBS>>(ec, pa, ra, stream);
+    constexpr bool N = kObsNorm<Rms...>;
+    if (pol->kind == SSC_POLICY_RANDOM) return launch_rollout<EnvT, RandomPolicy<OBS>>(ec, pa, ra, stream);   // (no network: no statistics)
     const ssc_actor_desc &a = pol->actor;
     if (a.obs_dim != OBS)
         return set_error(SSC_EINVAL, "ssc_rollout: actor obs_dim %d != env obs_dim %d", a.obs_dim, OBS);
     if (a.act_dim != 1) return set_error(SSC_EUNSUPPORTED, "ssc_rollout: act_dim %d (only 1)", a.act_dim);
     if (a.precision == SSC_PREC_F32) {
         if (a.h1 == 64 && a.h2 == 32)
-            return launch_rollout<EnvT, ActorPolicy<ActorF32<OBS, 64, 32>, OBS>>(ec, pa, ra, stream);
+            return launch_rollout<EnvT, ActorPolicy<ActorF32<OBS, 64, 32>, OBS, N>>(ec, pa, ra, stream, rms...);
         if (a.h1 == 64 && a.h2 == 64)      // Actor_Editted's own default sizes (models_editted.py:23)
-            return launch_rollout<EnvT, ActorPolicy<ActorF32<OBS, 64, 64>, OBS>>(ec, pa, ra, stream);
+            return launch_rollout<EnvT, ActorPolicy<ActorF32<OBS, 64, 64>, OBS, N>>(ec, pa, ra, stream, rms...);
         return set_error(SSC_EUNSUPPORTED,
                          "ssc_rollout: fused fp32 actor supports h1-h2 = 64-32 and 64-64 (got %d-%d); use the bf16 MFMA "
                          "path or step the env with ssc_actor_forward + ssc_*_step",
@@ -537,21 +573,22 @@ static int dispatch_policy(const typename EnvT::Const &ec, const ssc_policy_desc
         if constexpr (OBS == 2) {
             // the shipped shape on unit action bounds with exploration noise on: the straight-line fused policy
             // (MountainCar observations are bounded by the env's own clamps: an observation clip at or beyond them
-            // -- DDPG's (-5, 5) against |pos| <= 1.2, |vel| <= 0.07 -- never acts, so the fused policy skips it)
+            // -- DDPG's (-5, 5) against |pos| <= 1.2, |vel| <= 0.07 -- never acts, so the fused policy skips it; a normalised
+            // observation has no such bound, and the NORM instantiation clips)
             const float obs_bound = fmaxf(fmaxf(fabsf(ec.min_position), fabsf(ec.max_position)), fabsf(ec.max_speed));
             const bool clip_inert = !(a.obs_clip > 0.0f) || a.obs_clip >= obs_bound;
-            if (a.h1 <= 64 && a.h2 <= 32 && pa.act_low == -1.0f && pa.act_high == 1.0f && (pa.ou_eps > 0.0f || pa.d_eps != nullptr) && clip_inert) {
-                if (a.last_layer_tanh) return launch_rollout<EnvT, ActorPolicyFused<true>>(ec, pa, ra, stream);
-                return launch_rollout<EnvT, ActorPolicyFused<false>>(ec, pa, ra, stream);
+            if (a.h1 <= 64 && a.h2 <= 32 && pa.act_low == -1.0f && pa.act_high == 1.0f && (pa.ou_eps > 0.0f || pa.d_eps != nullptr) && (clip_inert || N)) {
+                if (a.last_layer_tanh) return launch_rollout<EnvT, ActorPolicyFused<true, N>>(ec, pa, ra, stream, rms...);
+                return launch_rollout<EnvT, ActorPolicyFused<false, N>>(ec, pa, ra, stream, rms...);
             }
         }
         if (a.h1 <= 64 && a.h2 <= 32)
-            return launch_rollout<EnvT, ActorPolicy<ActorMfma<OBS, 2, 1, 2>, OBS>>(ec, pa, ra, stream);
+            return launch_rollout<EnvT, ActorPolicy<ActorMfma<OBS, 2, 1, 2>, OBS, N>>(ec, pa, ra, stream, rms...);
         if (a.h1 <= 128 && a.h2 <= 64)
-            return launch_rollout<EnvT, ActorPolicy<ActorMfma<OBS, 4, 2, 2>, OBS>>(ec, pa, ra, stream);
+            return launch_rollout<EnvT, ActorPolicy<ActorMfma<OBS, 4, 2, 2>, OBS, N>>(ec, pa, ra, stream, rms...);
         // the wide shapes of the reference's grid (200-100): W2 fragments staged in LDS (ActorMfmaLds)
         if (a.h1 <= 224 && a.h2 <= 128)
-            return launch_rollout<EnvT, ActorPolicy<ActorMfmaLds<OBS, 7, 4, SSC_WIDE_ACTOR_ET>, OBS>>(ec, pa, ra, stream);
+            return launch_rollout<EnvT, ActorPolicy<ActorMfmaLds<OBS, 7, 4, SSC_WIDE_ACTOR_ET>, OBS, N>>(ec, pa, ra, stream, rms...);
         return set_error(SSC_EUNSUPPORTED, "ssc_rollout: MFMA actor supports h1 <= 224, h2 <= 128 (got %d-%d)",
                          a.h1, a.h2);
     }
@@ -773,10 +810,11 @@ __global__ __launch_bounds__(kBlock) void mpc_rollout_step_kernel(typename EnvT:
 
 using namespace ssc;
 
-extern "C" int ssc_rollout(const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n, int32_t K,
-                           const ssc_rollout_state *state, const ssc_transition_log *log,
-                           const ssc_episode_ring *ring, double *d_stats, uint64_t seed, uint64_t env_id0,
-                           uint64_t step0, ssc_stream_t stream) {
+template <class... Rms>
+static int rollout(const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n, int32_t K,
+                   const ssc_rollout_state *state, const ssc_transition_log *log,
+                   const ssc_episode_ring *ring, double *d_stats, uint64_t seed, uint64_t env_id0,
+                   uint64_t step0, ssc_stream_t stream, Rms... rms) {
     SSC_REQUIRE(p && policy && state, "ssc_rollout: NULL descriptor");
     SSC_REQUIRE(n >= 0 && K >= 0, "ssc_rollout: n = %lld, K = %d", (long long)n, K);
     SSC_REQUIRE(n <= ((int64_t)1 << 30), "ssc_rollout: n = %lld > 2^30 envs per launch", (long long)n);
@@ -843,11 +881,28 @@ extern "C" int ssc_rollout(const ssc_env_params *p, const ssc_policy_desc *polic
     }
     if (p->kind == SSC_ENV_MOUNTAINCAR) {
         if (int rc = validate_mc_params(p, "ssc_rollout")) return rc;
-        return dispatch_policy<McEnv>(make_mc_const(*p), policy, pa, ra, as_stream(stream));
+        return dispatch_policy<McEnv>(make_mc_const(*p), policy, pa, ra, as_stream(stream), rms...);
     }
     if (p->kind == SSC_ENV_PENDULUM)
-        return dispatch_policy<PendEnv>(make_pend_const(*p), policy, pa, ra, as_stream(stream));
+        return dispatch_policy<PendEnv>(make_pend_const(*p), policy, pa, ra, as_stream(stream), rms...);
     return set_error(SSC_EINVAL, "ssc_rollout: unknown env kind %d", p->kind);
+}
+
+extern "C" int ssc_rollout(const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n, int32_t K,
+                           const ssc_rollout_state *state, const ssc_transition_log *log,
+                           const ssc_episode_ring *ring, double *d_stats, uint64_t seed, uint64_t env_id0,
+                           uint64_t step0, ssc_stream_t stream) {
+    return rollout(p, policy, n, K, state, log, ring, d_stats, seed, env_id0, step0, stream);
+}
+
+// normalize_observations: the actor sees clip((obs - mean) / std) of the RunningMeanStd block d_rms, read once per
+// launch (frozen for the chunk, like the weights); a random policy ignores it
+extern "C" int ssc_rollout_rms(const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n, int32_t K,
+                               const ssc_rollout_state *state, const ssc_transition_log *log,
+                               const ssc_episode_ring *ring, double *d_stats, uint64_t seed, uint64_t env_id0,
+                               uint64_t step0, ssc_stream_t stream, const double *d_rms) {
+    if (d_rms == nullptr) return rollout(p, policy, n, K, state, log, ring, d_stats, seed, env_id0, step0, stream);
+    return rollout(p, policy, n, K, state, log, ring, d_stats, seed, env_id0, step0, stream, d_rms);
 }
 
 // argument checks and packing shared by ssc_mpc_rollout_step and ssc_smartstart_rollout_step

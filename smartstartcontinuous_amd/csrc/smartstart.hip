@@ -7,7 +7,7 @@
 // the latency spike the author timed (:354-360).  Here: one block per 8 query points, the data
 // set streamed from L2 (0.8 MB at |D| = 1e5, d = 2), fp32 exp on the transcendental pipe, f64
 // block reduction.
-#include "ssc_device.h"
+#include "actor_device.h"
 #include "ssc_host.h"
 
 namespace ssc {
@@ -20,8 +20,9 @@ struct CriticW {
 };
 
 // one row per lane; layer-1 activations (+ the action, models_editted.py:89) parked in LDS as [unit][lane]
+template <class... Rms>
 __global__ __launch_bounds__(64) void critic_kernel(CriticW w, int64_t m, const float *__restrict__ obs,
-                                                    const float *__restrict__ act, float *__restrict__ q) {
+                                                    const float *__restrict__ act, float *__restrict__ q, Rms... rms) {
     extern __shared__ float hs[];  // [(h1 + act_dim)][64] (+ [h2][64] with LayerNorm)
     const bool ln = w.ln1_g != nullptr;
     const int lane = threadIdx.x;
@@ -29,10 +30,17 @@ __global__ __launch_bounds__(64) void critic_kernel(CriticW w, int64_t m, const 
     const bool active = gi < m;
     const int64_t i = active ? gi : m - 1;
     float o[SSC_MAX_STATE];
+    if constexpr (kObsNorm<Rms...>) {   // normalize_observations (ddpg_editted.py:100-109; actor_device.h)
+        ObsNorm<SSC_MAX_STATE> nrm;
+        nrm.load(rms_block(rms...), w.obs_dim);
 #pragma unroll
-    for (int c = 0; c < SSC_MAX_STATE; ++c) {   // ddpg_editted.py:106-109
-        const float v = (c < w.obs_dim) ? obs[i * w.obs_dim + c] : 0.0f;
-        o[c] = w.obs_clip > 0.0f ? fminf(fmaxf(v, -w.obs_clip), w.obs_clip) : v;
+        for (int c = 0; c < SSC_MAX_STATE; ++c) o[c] = (c < w.obs_dim) ? nrm.apply(obs[i * w.obs_dim + c], c, w.obs_clip) : 0.0f;
+    } else {
+#pragma unroll
+        for (int c = 0; c < SSC_MAX_STATE; ++c) {   // ddpg_editted.py:106-109
+            const float v = (c < w.obs_dim) ? obs[i * w.obs_dim + c] : 0.0f;
+            o[c] = w.obs_clip > 0.0f ? fminf(fmaxf(v, -w.obs_clip), w.obs_clip) : v;
+        }
     }
     for (int j = 0; j < w.h1; ++j) {
         float acc = w.b1[j];
@@ -201,10 +209,9 @@ __global__ __launch_bounds__(256) void ucb_kernel(int64_t m, const float *__rest
 
 using namespace ssc;
 
-extern "C" {
-
-int ssc_critic_forward(const ssc_critic_desc *c, int64_t m, const float *d_obs, const float *d_act, float *d_q,
-                       ssc_stream_t stream) {
+template <class... Rms>
+static int critic_forward(const ssc_critic_desc *c, int64_t m, const float *d_obs, const float *d_act, float *d_q,
+                          ssc_stream_t stream, Rms... rms) {
     SSC_REQUIRE(c != nullptr, "ssc_critic_forward: critic NULL");
     SSC_REQUIRE(m >= 0, "ssc_critic_forward: m < 0");
     SSC_REQUIRE(c->obs_dim >= 1 && c->obs_dim <= SSC_MAX_STATE && c->act_dim >= 1 && c->act_dim <= SSC_MAX_ACT,
@@ -221,15 +228,30 @@ int ssc_critic_forward(const ssc_critic_desc *c, int64_t m, const float *d_obs, 
     const size_t lds = (size_t)(c->h1 + c->act_dim + (ln ? c->h2 : 0)) * 64 * sizeof(float);
     if (lds > 160 * 1024) return set_error(SSC_EUNSUPPORTED, "ssc_critic_forward: h1 %d + h2 %d too wide for the LayerNorm kernel", c->h1, c->h2);
     if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(critic_kernel),
+        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(critic_kernel<Rms...>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
                            "hipFuncSetAttribute(critic_kernel)");
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(critic_kernel, dim3(blocks_for(m, 64)), dim3(64), lds, as_stream(stream), w, m, d_obs, d_act,
-                       d_q);
+    hipLaunchKernelGGL(critic_kernel<Rms...>, dim3(blocks_for(m, 64)), dim3(64), lds, as_stream(stream), w, m, d_obs, d_act,
+                       d_q, rms...);
     return check_launch("ssc_critic_forward");
 }
+
+extern "C" {
+
+int ssc_critic_forward(const ssc_critic_desc *c, int64_t m, const float *d_obs, const float *d_act, float *d_q,
+                       ssc_stream_t stream) {
+    return critic_forward(c, m, d_obs, d_act, d_q, stream);
+}
+
+// normalize_observations: Q of clip((obs - mean) / std) with the RunningMeanStd block d_rms (actor_device.h)
+int ssc_critic_forward_rms(const ssc_critic_desc *c, int64_t m, const float *d_obs, const float *d_act, float *d_q,
+                           ssc_stream_t stream, const double *d_rms) {
+    if (d_rms == nullptr) return critic_forward(c, m, d_obs, d_act, d_q, stream);
+    return critic_forward(c, m, d_obs, d_act, d_q, stream, d_rms);
+}
+
 
 int ssc_kde_evaluate(int32_t d, int64_t n, const float *d_data, int64_t m, const float *d_points,
                      const float *whitening, double norm, float *d_pdf, ssc_stream_t stream) {

@@ -1,0 +1,94 @@
+"""normalize_observations: the running observation statistics of DDPG_editted (ddpg_editted.py:14-18, 100-109).
+
+The statistics object of the reference is baselines 0.1.5 ``common/mpi_running_mean_std.RunningMeanStd`` (third-party,
+restated in DESIGN section 5): f64 ``sum`` (starts at 0), ``sumsq`` (1e-2) and ``count`` (1e-2); ``update(x)`` adds
+sum(x), sum(x^2) and len(x) in f64; the networks see, in fp32 (TF ``to_float``),
+
+    mean = f32(sum / count),  std = sqrt(max(f32(sumsq / count) - mean * mean, 1e-2))
+    x_hat = clip((x - mean) / std, -obs_clip, obs_clip)
+
+On the device the three live in ONE f64 block ``[sum[D] | sumsq[D] | count]`` (baselines' own Allreduce vector layout),
+which every kernel reads when it starts: HIP graphs and the overlapped loop stay valid while it changes.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _ffi
+
+RMS_EPSILON = 1e-2
+
+
+def rms_initial(obs_dim):
+    """The f64 block of a fresh RunningMeanStd: sum 0, sumsq 1e-2, count 1e-2."""
+    b = np.zeros(2 * obs_dim + 1, np.float64)
+    b[obs_dim:] = RMS_EPSILON
+    return b
+
+
+def mean_std_f32(block, obs_dim=None):
+    """The fp32 mean / std the networks use, from a host copy of the f64 block (numpy float32 arithmetic: one rounding
+    per operation, no fused multiply-add -- the kernels' derivation)."""
+    b = np.asarray(block, np.float64)
+    d = (b.size - 1) // 2 if obs_dim is None else int(obs_dim)
+    cnt = b[2 * d]
+    mean = (b[:d] / cnt).astype(np.float32)
+    sq = (b[d:2 * d] / cnt).astype(np.float32)
+    var = sq - mean * mean                                    # float32 multiply, then float32 subtract
+    std = np.sqrt(np.maximum(var, np.float32(RMS_EPSILON)))
+    return mean, std.astype(np.float32)
+
+
+def normalize_f32(x, block, obs_clip):
+    """x_hat = clip((x - mean) / std, -obs_clip, obs_clip) in fp32 (numpy), for x [..., obs_dim]."""
+    mean, std = mean_std_f32(block)
+    xh = (np.asarray(x, np.float32) - mean) / std
+    if obs_clip > 0:
+        xh = np.clip(xh, np.float32(-obs_clip), np.float32(obs_clip))
+    return xh.astype(np.float32)
+
+
+class ObsRms:
+    """The device block plus its update entry points (ssc_obs_rms_update / ssc_obs_rms_update_rows)."""
+
+    def __init__(self, obs_dim, device="cuda"):
+        self.obs_dim = int(obs_dim)
+        if not 1 <= self.obs_dim <= _ffi.SSC_MAX_STATE:
+            raise ValueError(f"obs_dim {obs_dim} out of range")
+        self.device = torch.device(device)
+        self.lib = _ffi.lib()
+        self.block = torch.as_tensor(rms_initial(self.obs_dim), device=self.device)
+        nbytes = int(self.lib.ssc_obs_rms_update_workspace_bytes(self.obs_dim))
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def update_chunk(self, chunk, k0=0, K=None):
+        """RunningMeanStd.update with the obs0 of steps [k0, K) of a TransitionChunk (every env)."""
+        K = chunk.K if K is None else int(K)
+        log = chunk.as_struct()
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_obs_rms_update(self.obs_dim, ctypes.byref(log), int(k0), K, chunk.N,
+                                                   _ffi.ptr(self.block), _ffi.ptr(self._ws), self._ws.numel(),
+                                                   self._stream()))
+
+    def update_rows(self, x):
+        """RunningMeanStd.update with the rows of x [m, obs_dim] (a host array or a tensor)."""
+        t = torch.as_tensor(x, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_obs_rms_update_rows(self.obs_dim, t.shape[0], _ffi.ptr(t), _ffi.ptr(self.block),
+                                                        _ffi.ptr(self._ws), self._ws.numel(), self._stream()))
+
+    def mean_std(self):
+        """Host fp32 (mean, std): the values the kernels derive from the block."""
+        return mean_std_f32(self.block.cpu().numpy(), self.obs_dim)
+
+    def snapshot_into(self, other):
+        """Stream-ordered copy of the block into ``other`` (an ObsRms or a tensor of the same shape)."""
+        dst = other.block if isinstance(other, ObsRms) else other
+        dst.copy_(self.block)
+        return other

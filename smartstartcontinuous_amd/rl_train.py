@@ -295,6 +295,19 @@ def default_drain_every(ring_capacity, n_envs, chunk_steps, shortest_episode=64)
     return int(max(1, min(16, ring_capacity // max(per_chunk, 1))))
 
 
+def update_obs_rms(agent, chunk, last_steps=None):
+    """store_transition's ``obs_rms.update(obs0)`` (ddpg_editted.py:281-285) for exactly the records
+    ``DeviceReplayBuffer.append_chunk(chunk, last_steps=...)`` stored; nothing for an agent without
+    normalize_observations.  Stream-ordered after the append, before the learner iterations of the chunk."""
+    rms = getattr(agent, "obs_rms", None)
+    if rms is None:
+        return
+    k = chunk.K if last_steps is None else min(int(last_steps), chunk.K)
+    if k <= 0:                                    # append_chunk stored nothing
+        return
+    rms.update_chunk(chunk, chunk.K - k, chunk.K)
+
+
 def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
                       replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
                       drain_every=None, on_chunk=None):
@@ -357,6 +370,8 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             act = torch.cuda.Stream(env.device)          # the rollouts' stream
         chunks = [chunk, TransitionChunk(env.obs_dim, chunk_steps, env.n, env.device)]
         snap = agent.actor_flat.clone()                  # the weights the NEXT rollout acts with
+        rms = getattr(agent, "obs_rms", None)
+        rms_snap = rms.block.clone() if rms is not None else None   # ... and the observation statistics (normalize_observations)
         views, o = {}, 0
         for k, v in agent.weights.items():               # same order and shapes as the flat array (flatten_params)
             views[k] = snap[o:o + v.numel()].view(v.shape)
@@ -367,7 +382,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         live = agent.as_policy(device_epsilon=True)
         pd = env.policy_desc(ActorPolicy(views, last_layer_tanh=live.last_layer_tanh, precision=live.precision, ou_mu=live.ou_mu,
                                          ou_sigma=live.ou_sigma, ou_theta=live.ou_theta, ou_dt=live.ou_dt,
-                                         obs_clip=live.obs_clip, d_ou_epsilon=agent.d_epsilon))
+                                         obs_clip=live.obs_clip, d_ou_epsilon=agent.d_epsilon, d_obs_rms=rms_snap))
         act.wait_stream(cur)
 
         drained = torch.cuda.Event()
@@ -386,8 +401,11 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             b = i & 1
             cur.wait_event(rolled2[b])
             replay.append_chunk(chunks[b], reward_scale=agent.reward_scale, last_steps=replay_last_steps)
+            update_obs_rms(agent, chunks[b], replay_last_steps)
             appended[b].record(cur)
             snap.copy_(agent.actor_flat)                 # behind train i-1 on this stream, in front of train i
+            if rms_snap is not None:
+                rms_snap.copy_(rms.block)                # (the side-stream rollout must not read the block while it is updated)
             snap_ready.record(cur)
             l = agent.train_from(replay, train_iters)
             if l is not None:
@@ -410,6 +428,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         out = env.rollout(chunk_steps, out=chunk, ring=ring, policy_desc=pd)
         after_rollout()
         replay.append_chunk(out, reward_scale=agent.reward_scale, last_steps=replay_last_steps)
+        update_obs_rms(agent, out, replay_last_steps)
         l = agent.train_from(replay, train_iters)
         if l is not None:
             losses.append(l)
@@ -474,6 +493,7 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
                 smart.refresh_plans(replay)
             out = smart.rollout(chunk_steps, chunk, ring=ring, graph=graph)
         replay.append_chunk(out, reward_scale=agent.reward_scale, last_steps=replay_last_steps)
+        update_obs_rms(agent, out, replay_last_steps)
         l = agent.train_from(replay, train_iters)
         if overlap_selection:
             learned.record(main)

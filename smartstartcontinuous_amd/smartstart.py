@@ -360,8 +360,13 @@ class VecSmartStart:
         fb = b._fused_buffers(env.device)
         with torch.cuda.device(env.device):
             _ffi.check(lib.ssc_nav_compact(env.n, _ffi.ptr(self.mode), _ffi.ptr(self.live_list), _ffi.ptr(self.n_live), _stream()))
-            _ffi.check(lib.ssc_actor_forward(ctypes.byref(self.agent._desc), env.n, _ffi.ptr(fb["plan"]),
-                                             _ffi.ptr(self.actor_out), _stream()))
+            rms = getattr(self.agent, "obs_rms", None)
+            if rms is None:
+                _ffi.check(lib.ssc_actor_forward(ctypes.byref(self.agent._desc), env.n, _ffi.ptr(fb["plan"]),
+                                                 _ffi.ptr(self.actor_out), _stream()))
+            else:   # normalize_observations: the kernel reads the block at launch (valid inside the captured graph)
+                _ffi.check(lib.ssc_actor_forward_rms(ctypes.byref(self.agent._desc), env.n, _ffi.ptr(fb["plan"]),
+                                                     _ffi.ptr(self.actor_out), _stream(), _ffi.ptr(rms.block)))
         sp = nav.mpc_sampling(b.N, b.low, b.high, b.seed, b.problem_id0, 0, t_base=fb["t"], active=self.mode,
                               live_list=self.live_list, n_live=self.n_live)
         S = self.model.do_forward_sim_sampled(fb["plan"], sp, b.P * b.N, b.H, out=b._S, A_out=fb["A"])

@@ -74,6 +74,8 @@ class ActorPolicy:
     obs_clip: float = 0.0              # > 0: the actor sees clip(obs, -obs_clip, obs_clip) (ddpg_editted.py:106-109: 5.0)
     d_ou_epsilon: object = None        # a 1-element fp32 device tensor: the kernel reads epsilon from it (ou_epsilon is
                                        # ignored) -- rl_train.DecaySchedule keeps it current without the host
+    d_obs_rms: object = None           # normalize_observations: the f64 RunningMeanStd block [sum | sumsq | count] on the
+                                       # env's device (obs_rms.ObsRms.block); the actor sees clip((obs - mean) / std)
 
 
 @dataclass
@@ -335,6 +337,11 @@ class VecEnv:
                 raise ValueError("d_ou_epsilon must be ONE fp32 value on the env's device")
             pd.ou.d_epsilon = d.data_ptr()
             w["_d_eps"] = d
+        if policy.d_obs_rms is not None:
+            r = policy.d_obs_rms
+            if r.dtype != torch.float64 or r.numel() != 2 * obs_dim + 1 or not r.is_cuda or r.device.index != self.s0.device.index:
+                raise ValueError("d_obs_rms must be the f64 [2 * obs_dim + 1] statistics block on the env's device")
+            w["_d_obs_rms"] = r
         return pd, w  # keep the tensors alive for the duration of the launch
 
     def rollout(self, K, policy=None, out=None, ring=None, log=True, policy_desc=None):
@@ -360,12 +367,16 @@ class VecEnv:
                                self.ep_ret.data_ptr(), self.ou_x.data_ptr())
         log_s = chunk.as_struct() if chunk is not None else None
         ring_s = ring.as_struct() if ring is not None else None
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.ssc_rollout(
-                ctypes.byref(self.params), ctypes.byref(pd), self.n, K, ctypes.byref(st),
+        rms = keep.get("_d_obs_rms") if keep else None
+        args = (ctypes.byref(self.params), ctypes.byref(pd), self.n, K, ctypes.byref(st),
                 ctypes.byref(log_s) if log_s is not None else None,
                 ctypes.byref(ring_s) if ring_s is not None else None,
-                _ffi.ptr(self.stats), self._seed, self.env_id0, self.t, _stream()))
+                _ffi.ptr(self.stats), self._seed, self.env_id0, self.t, _stream())
+        with torch.cuda.device(self.device):
+            if rms is None:
+                _ffi.check(self.lib.ssc_rollout(*args))
+            else:                                 # normalize_observations: statistics read once per launch
+                _ffi.check(self.lib.ssc_rollout_rms(*args, _ffi.ptr(rms)))
         self.t += K
         del keep
         return chunk
