@@ -95,23 +95,57 @@ def test_argument_validation_of_the_dataset_and_training_entry_points(built):
         b"n_layers" in lib.ssc_last_error()
 
 
+def header_structs():
+    """every `typedef struct ssc_x { ... } ssc_x;` of include/ssc.h"""
+    text = open(os.path.join(ROOT, "include", "ssc.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    names = re.findall(r"typedef\s+struct\s+(ssc_[a-z_0-9]+)\s*\{", text)
+    for n in names:
+        assert re.search(r"\}\s*%s\s*;" % n, text), n
+    return names
+
+
+# C struct -> its ctypes mirror in _ffi.py.  A struct added to ssc.h without a line here fails the test below.
+STRUCT_MIRRORS = {
+    "ssc_env_params": "EnvParams", "ssc_actor_desc": "ActorDesc", "ssc_ou_desc": "OuDesc", "ssc_policy_desc": "PolicyDesc",
+    "ssc_rollout_state": "RolloutState", "ssc_transition_log": "TransitionLog", "ssc_episode_ring": "EpisodeRing",
+    "ssc_mlp_desc": "MlpDesc", "ssc_norm": "Norm", "ssc_mpc_problems": "MpcProblems", "ssc_mpc_sampling": "MpcSampling",
+    "ssc_mpc_nav_state": "MpcNavState", "ssc_smartstart_step": "SmartStartStep", "ssc_critic_desc": "CriticDesc",
+    "ssc_ddpg_desc": "DdpgDesc", "ssc_replay_view": "ReplayView", "ssc_replay_ring": "ReplayRing",
+    "ssc_mlp_train_desc": "MlpTrainDesc",
+}
+# passed by pointer on every MPC step, pointers and 64-bit fields: every field's offset is compared as well
+OFFSET_CHECKED = ("ssc_mpc_sampling", "ssc_mpc_nav_state")
+
+
 def test_struct_layouts_match_header(built, tmp_path):
-    """sizeof() of every descriptor struct as the C compiler sees it == ctypes.sizeof."""
+    """sizeof() of every descriptor struct as the C compiler sees it == ctypes.sizeof, for EVERY struct the header
+    declares (the list is parsed from ssc.h); offsetof() of every field of the MPC sampling / navigator-state structs."""
     import subprocess
     from smartstartcontinuous_amd import _ffi
+    structs = header_structs()
+    assert len(structs) >= 18 and len(set(structs)) == len(structs)
+    missing = [n for n in structs if n not in STRUCT_MIRRORS or not hasattr(_ffi, STRUCT_MIRRORS[n])]
+    assert not missing, f"structs of ssc.h without a ctypes mirror in the comparison: {missing}"
+    assert sorted(STRUCT_MIRRORS) == sorted(structs), "STRUCT_MIRRORS names a struct the header does not declare"
+    lines = [f'printf("%zu\\n", sizeof({n}));' for n in structs]
+    fields = [(n, f) for n in OFFSET_CHECKED for f, _ in getattr(_ffi, STRUCT_MIRRORS[n])._fields_]
+    lines += [f'printf("%zu\\n", offsetof({n}, {f}));' for n, f in fields]
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "ssc.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
-                   'sizeof(ssc_env_params),sizeof(ssc_actor_desc),sizeof(ssc_ou_desc),sizeof(ssc_policy_desc),'
-                   'sizeof(ssc_rollout_state),sizeof(ssc_transition_log),sizeof(ssc_episode_ring),'
-                   'sizeof(ssc_mlp_desc),sizeof(ssc_norm),sizeof(ssc_mpc_problems),sizeof(ssc_critic_desc),sizeof(ssc_ddpg_desc),sizeof(ssc_replay_view),sizeof(ssc_mlp_train_desc),sizeof(ssc_replay_ring),sizeof(ssc_smartstart_step));return 0;}\n')
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ssc.h"\nint main(){' + "".join(lines) + "return 0;}\n")
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    sizes = [int(x) for x in subprocess.check_output([str(exe)]).split()]
-    expect = [ctypes.sizeof(c) for c in (_ffi.EnvParams, _ffi.ActorDesc, _ffi.OuDesc, _ffi.PolicyDesc,
-                                         _ffi.RolloutState, _ffi.TransitionLog, _ffi.EpisodeRing, _ffi.MlpDesc,
-                                         _ffi.Norm, _ffi.MpcProblems, _ffi.CriticDesc,
-                                         _ffi.DdpgDesc, _ffi.ReplayView, _ffi.MlpTrainDesc, _ffi.ReplayRing, _ffi.SmartStartStep)]
-    assert sizes == expect
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    sizes, offsets = got[:len(structs)], got[len(structs):]
+    assert sizes == [ctypes.sizeof(getattr(_ffi, STRUCT_MIRRORS[n])) for n in structs], list(zip(structs, sizes))
+    expect = [getattr(getattr(_ffi, STRUCT_MIRRORS[n]), f).offset for n, f in fields]
+    assert offsets == expect, [(n, f, o, e) for (n, f), o, e in zip(fields, offsets, expect) if o != e]
+    # the C field lists of the two structs hold nothing the mirrors lack (same number of members)
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ssc.h")).read(), flags=re.S)
+    for n in OFFSET_CHECKED:
+        body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (n, n), text, flags=re.S).group(1)
+        members = [m for decl in body.split(";") if decl.strip() for m in decl.split(",")]
+        assert len(members) == len(getattr(_ffi, STRUCT_MIRRORS[n])._fields_), (n, members)
 
 
 def test_product_never_imports_oracle():

@@ -226,6 +226,32 @@ def test_pendulum_step_kernel(ssc):
         assert d[: n // 2].all() and not d[n // 2:].any()       # TimeLimit(200) only
 
 
+def test_pendulum_step_kernel_known_answers(ssc):
+    """ssc_pend_step against the hand-derived literals of tests/pendulum_kats.py (no oracle in between), at the
+    tolerances of test_pendulum_step_kernel."""
+    from tests.pendulum_kats import PENDULUM_KATS as K
+    ffi = ssc._ffi
+    n = len(K)
+    for v1 in (0, 1):
+        p = ffi.default_params(ffi.SSC_ENV_PENDULUM, 1.0, 200)
+        p.pend_v1_order = v1
+        dt, dd, da = (torch.as_tensor(K[:, c].astype(np.float32), device="cuda") for c in (0, 1, 2))
+        obs = torch.empty((3, n), dtype=torch.float32, device="cuda")
+        rew = torch.empty(n, dtype=torch.float32, device="cuda")
+        done = torch.empty(n, dtype=torch.uint8, device="cuda")
+        steps = torch.zeros(n, dtype=torch.int32, device="cuda")
+        ffi.check(ffi.lib().ssc_pend_step(ctypes.byref(p), n, ffi.ptr(dt), ffi.ptr(dd), ffi.ptr(da), ffi.ptr(obs),
+                                          ffi.ptr(rew), ffi.ptr(done), ffi.ptr(steps), None))
+        torch.cuda.synchronize()
+        want_th, want_thd, want_r = K[:, 3 + 2 * v1], K[:, 4 + 2 * v1], K[:, 7]
+        assert np.max(np.abs(dt.cpu().numpy() - want_th)) <= 4e-6
+        assert np.max(np.abs(dd.cpu().numpy() - want_thd)) <= 2e-6
+        assert np.max(np.abs(rew.cpu().numpy() - want_r) / np.maximum(1, np.abs(want_r))) <= 2e-5
+        o = obs.cpu().numpy()
+        assert np.max(np.abs(o[0] - np.cos(want_th))) <= 5e-6 and np.max(np.abs(o[1] - np.sin(want_th))) <= 5e-6
+        assert not done.cpu().numpy().any()
+
+
 @pytest.mark.parametrize("env_id,v1", [("Pendulum-v0", False), ("Pendulum-v1", True)])
 def test_pendulum_env_id_selects_update_order(ssc, env_id, v1):
     """The env built BY ID runs the update order its id names (gym 0.10.5 'v0': theta integrates the unclipped new
