@@ -20,12 +20,13 @@ import smartstartcontinuous_amd as ssc  # noqa: E402
 from smartstartcontinuous_amd.agents import DDPG_Baselines_agent  # noqa: E402
 
 
-def make_agent(env, seed, normalize_observations=False):
+def make_agent(env, seed, normalize_observations=False, param_noise=None):
     return DDPG_Baselines_agent(env, None, buffer_size=100000, batch_size=64, num_train_iterations=50,
                                 num_steps_before_train=200, ou_epsilon=1.0, ou_min_epsilon=0.01,
                                 ou_epsilon_decay_factor=.99, ou_mu=0.4, ou_sigma=0.6, ou_theta=.15, actor_lr=0.001,
                                 actor_h1=64, actor_h2=32, critic_lr=0.001, critic_h1=64, critic_h2=32,
-                                lastLayerTanh=True, normalize_observations=normalize_observations, seed=seed)
+                                lastLayerTanh=True, normalize_observations=normalize_observations, seed=seed,
+                                param_noise_stddev=param_noise)
 
 
 def main():
@@ -41,23 +42,30 @@ def main():
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--normalize-observations", action="store_true",
                     help="DDPG normalize_observations: networks see running-statistics-normalised observations")
+    ap.add_argument("--param-noise", type=float, default=None, metavar="STDDEV",
+                    help="adaptive parameter-space noise with this initial (and desired action) stddev, on top of the OU noise")
     args = ap.parse_args()
+    if args.param_noise is not None and args.overlap:
+        ap.error("--param-noise needs the synchronous loop (no --overlap)")
     np.random.seed(args.seed)
     if args.mode == "single":
         env = ssc.Continuous_MountainCarEnv_Editted.make_timed_env(args.power_scalar, max_episode_steps=1000,
                                                                    seed=args.seed)
-        agent = make_agent(env, args.seed, args.normalize_observations)
+        agent = make_agent(env, args.seed, args.normalize_observations, args.param_noise)
         summary = ssc.rlTrain(agent, env, print_results=True, print_steps=False, num_episodes=args.episodes,
                               max_steps=1000)
     else:
         env = ssc.VecEnv("MountainCarContinuousActionX%s-v0" % args.power_scalar, args.envs, seed=args.seed)
-        agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations)
+        agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations,
+                           args.param_noise)
         summary, losses, replay = ssc.rl_train_vec_ddpg(env, agent, num_chunks=args.chunks, chunk_steps=250,
                                                         replay_capacity=1 << 20, train_iters=50, overlap=args.overlap)
         goals = sum(1 for steps, ret in summary.episodes if ret > 0)
         print("%d env-steps, %d finished episodes (%d reached the goal), %d records in the replay ring, "
               "last critic/actor loss %.4g / %.4g" % (args.envs * args.chunks * 250, len(summary), goals, len(replay),
                                                       *losses[-1][-1].tolist()))
+    if agent.param_noise is not None:
+        print("parameter noise:", agent.param_noise.get_stats())
     if args.save_dir:
         os.makedirs(args.save_dir, exist_ok=True)
         print("summary written to", summary.save(args.save_dir))

@@ -634,6 +634,29 @@ int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *ddpg, const ssc_replay_view *repl
                           const double *d_rms);
 
 /* ---------------------------------------------------------------------------------------
+ * Adaptive parameter-space noise (ddpg_editted.py:47-60, 151-166, 255-259, 360-385)
+ * -------------------------------------------------------------------------------------
+ * A perturbed actor is a second flat parameter array [W1|b1|(beta1|gamma1)|W2|b2|(beta2|gamma2)|W3|b3] that the
+ * forward and rollout kernels read through an ordinary ssc_actor_desc.
+ *
+ * ssc_param_noise_perturb: d_dst[i] = d_src[i] + *d_stddev * g_i for the n elements outside the two skip ranges
+ * [skipX_begin, skipX_end) (the LayerNorm beta / gamma segments, models_editted.py:18-19: perturbable_vars; an empty
+ * range is begin == end), a bit copy inside them and everywhere when *d_stddev == 0.  The stream depends on the flat
+ * index alone: ONE Philox(seed; q, generation, TAG_PARAM_NOISE = 9) evaluation serves elements 4q .. 4q+3 -- words
+ * (0, 1) are one Box-Muller pair (cos -> 4q, sin -> 4q+1), words (2, 3) the pair of (4q+2, 4q+3).  generation < 2^56.
+ * stddev is read from device memory when the kernel runs; d_src == d_dst is allowed; n == 0 launches nothing.
+ *
+ * ssc_param_noise_adapt: *d_distance = sqrt(mean((a - b)^2)) over count = batch * act_dim elements (ddpg_editted.py:166;
+ * one workgroup, f64 accumulation in a fixed order), then AdaptiveParamNoiseSpec.adapt of baselines 0.1.5 on the device
+ * value: *d_stddev /= coefficient if distance > desired, else *d_stddev *= coefficient (fp32; a tie multiplies).
+ * 1 <= count <= 4096 * SSC_MAX_ACT, coefficient > 1.  a and b come from two ssc_actor_forward[_rms] calls. */
+int ssc_param_noise_perturb(int64_t n, const float *d_src, float *d_dst, const float *d_stddev, int64_t skip0_begin,
+                            int64_t skip0_end, int64_t skip1_begin, int64_t skip1_end, uint64_t seed, uint64_t generation,
+                            ssc_stream_t stream);
+int ssc_param_noise_adapt(int64_t count, const float *d_a, const float *d_b, float desired, float coefficient,
+                          float *d_stddev, float *d_distance, ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Dynamics-model training step
  * ------------------------------------------------------------------------------------- */
 

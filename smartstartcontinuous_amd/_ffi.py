@@ -197,6 +197,10 @@ _SIGNATURES = {
                                 c_void_p]),
     "ssc_ddpg_train_ws_rms": (c_int, [POINTER(DdpgDesc), POINTER(ReplayView), c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
                                       c_void_p, c_void_p]),
+    # adaptive parameter-space noise: perturb a flat actor, adapt the device stddev
+    "ssc_param_noise_perturb": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint64,
+                                        c_uint64, c_void_p]),
+    "ssc_param_noise_adapt": (c_int, [c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "ssc_dataset_scan_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_dataset_scan": (c_int, [POINTER(TransitionLog), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),

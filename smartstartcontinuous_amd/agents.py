@@ -163,6 +163,51 @@ def flatten_params(weights, device, extra=0):
     return flat, views
 
 
+class AdaptiveParamNoiseSpec:
+    """baselines 0.1.5 ddpg/noise.py AdaptiveParamNoiseSpec [third-party, restated in DESIGN section 5]: the stddev of
+    the parameter-space noise, adapted so that the perturbed actor's actions lie ``desired_action_stddev`` from the plain
+    actor's.  On an agent the value lives in ONE fp32 device scalar (``d_stddev``) that ``ssc_param_noise_perturb`` reads
+    and ``ssc_param_noise_adapt`` updates; ``current_stddev`` reads it (a device -> host copy).  ``adapt`` is the same
+    rule in the same fp32 arithmetic on the host."""
+
+    def __init__(self, initial_stddev=0.1, desired_action_stddev=0.1, adoption_coefficient=1.01, d_stddev=None):
+        if not float(adoption_coefficient) > 1.0:
+            raise ValueError("adoption_coefficient must be > 1")
+        if not float(initial_stddev) >= 0.0:
+            raise ValueError("initial_stddev must be >= 0")
+        self.initial_stddev = float(initial_stddev)
+        self.desired_action_stddev = float(desired_action_stddev)
+        self.adoption_coefficient = float(adoption_coefficient)
+        self.d_stddev = d_stddev
+        self.current_stddev = self.initial_stddev
+
+    @property
+    def current_stddev(self):
+        if self.d_stddev is not None:
+            return float(self.d_stddev.item())
+        return float(self._stddev)
+
+    @current_stddev.setter
+    def current_stddev(self, value):
+        self._stddev = np.float32(value)
+        if self.d_stddev is not None:
+            self.d_stddev.fill_(float(self._stddev))
+
+    def adapt(self, distance):
+        sd, c = np.float32(self.current_stddev), np.float32(self.adoption_coefficient)
+        if np.float32(distance) > np.float32(self.desired_action_stddev):
+            self.current_stddev = sd / c          # decrease stddev
+        else:
+            self.current_stddev = sd * c          # increase stddev (a tie lands here)
+
+    def get_stats(self):
+        return {"param_noise_stddev": self.current_stddev}
+
+    def __repr__(self):
+        return "AdaptiveParamNoiseSpec(initial_stddev={}, desired_action_stddev={}, adoption_coefficient={})".format(
+            self.initial_stddev, self.desired_action_stddev, self.adoption_coefficient)
+
+
 class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
     """Action path of smartstart/RLAgents/DDPG_Baselines_agent.py (:86-273): actor forward on the GPU
     (``ssc_actor_forward``), decaying OU noise, clip, double ``scale``; transitions go to the shared
@@ -173,7 +218,8 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                  ou_mu=0.4, ou_sigma=0.2, ou_theta=.15, actor_lr=1e-4, actor_h1=64, actor_h2=64, critic_lr=1e-3,
                  critic_h1=64, critic_h2=64, gamma=0.99, tau=0.001, layer_norm=False, normalize_observations=False,
                  normalize_returns=False, critic_l2_reg=0, enable_popart=False, clip_norm=None, reward_scale=1.,
-                 lastLayerTanh=False, finalizeGraph=True, device="cuda", precision="f32", seed=None, training=True):
+                 lastLayerTanh=False, finalizeGraph=True, device="cuda", precision="f32", seed=None, training=True,
+                 param_noise_stddev=None, param_noise_desired_action_stddev=None, param_noise_adoption_coefficient=1.01):
         args = dict(locals())
         self.param_dict = {k: (v if isinstance(v, (int, float, bool, str, type(None))) else "Not serializable")
                            for k, v in args.items() if k not in ("self", "__class__")}   # :135-137
@@ -211,6 +257,17 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             aw, cw = with_layer_norm(aw), with_layer_norm(cw)
         # normalize_observations (ddpg_editted.py:100-109): the running obs statistics every network input goes through
         self.obs_rms = ObsRms(obs_dim, self.device) if normalize_observations else None
+        # adaptive parameter-space noise (ddpg_editted.py:151-166; main_editted.py:48: desired = initial stddev)
+        self.param_noise = None
+        if param_noise_stddev is not None:
+            desired = param_noise_stddev if param_noise_desired_action_stddev is None else param_noise_desired_action_stddev
+            # [stddev | distance]: what the perturb kernel reads and the adapt kernel writes
+            self._pn_scalars = torch.zeros(2, dtype=torch.float32, device=self.device)
+            self.d_param_noise_stddev, self.d_param_noise_distance = self._pn_scalars[0:1], self._pn_scalars[1:2]
+            self.param_noise = AdaptiveParamNoiseSpec(param_noise_stddev, desired, param_noise_adoption_coefficient,
+                                                      d_stddev=self.d_param_noise_stddev)
+            self.param_noise_seed = int(seed) if seed is not None else int(np.random.randint(0, 2 ** 31 - 1))
+            self.param_noise_generation = 0      # the generation the NEXT perturbation draws (acting or adaptive copy)
         self.set_weights(aw)
         self.set_critic_weights(cw)
         self.decaying_ou_action_noise = DecayingOrnsteinUhlenbeckActionNoise(
@@ -244,6 +301,74 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         if "ln1_g" in w:
             d.ln1_g, d.ln1_b, d.ln2_g, d.ln2_b = (w[k].data_ptr() for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b"))
         self._desc = d
+        if self.param_noise is not None:
+            self._setup_param_noise()
+
+    # ---- parameter-space noise ---------------------------------------------------------------
+    def _views_desc(self, flat):
+        """views into ``flat`` laid out like ``actor_flat`` + the actor descriptor over them"""
+        views, o = {}, 0
+        for k, v in self.weights.items():
+            views[k] = flat[o:o + v.numel()].view(v.shape)
+            o += v.numel()
+        d = _ffi.ActorDesc.from_buffer_copy(self._desc)
+        d.W1, d.b1, d.W2, d.b2, d.W3, d.b3 = (views[k].data_ptr() for k in ("W1", "b1", "W2", "b2", "W3", "b3"))
+        if "ln1_g" in views:
+            d.ln1_g, d.ln1_b, d.ln2_g, d.ln2_b = (views[k].data_ptr() for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b"))
+        return views, d
+
+    def _setup_param_noise(self):
+        """setup_param_noise (ddpg_editted.py:151-166): the acting copy and the copy the stddev is adapted on, both flat
+        arrays in the layout of ``actor_flat``; the acting copy is perturbed right away (the reset() before the first
+        episode, training_editted.py:70)."""
+        self.perturbed_actor_flat = self.actor_flat.clone()
+        self.adaptive_actor_flat = self.actor_flat.clone()
+        self.perturbed_weights, self._perturbed_desc = self._views_desc(self.perturbed_actor_flat)
+        _, self._adaptive_desc = self._views_desc(self.adaptive_actor_flat)
+        # LayerNorm beta / gamma are not perturbable_vars (models_editted.py:18-19): [beta | gamma] of each layer is one range
+        self._pn_skip, o = [], 0
+        for k, v in self.weights.items():
+            if k in ("ln1_b", "ln2_b"):
+                self._pn_skip += [o, o + 2 * v.numel()]
+            o += v.numel()
+        self._pn_skip = tuple(self._pn_skip) if self._pn_skip else (0, 0, 0, 0)
+        self.perturbed_generation = None
+        if self.device.type == "cuda":
+            self.perturb_policy()
+
+    def _perturb(self, dst):
+        """dst = actor_flat + stddev * N(0, 1) with a generation of its own; returns that generation"""
+        g = self.param_noise_generation
+        self.param_noise_generation = g + 1
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_param_noise_perturb(self.actor_flat.numel(), _ffi.ptr(self.actor_flat), _ffi.ptr(dst),
+                                                        _ffi.ptr(self.d_param_noise_stddev), *self._pn_skip,
+                                                        self.param_noise_seed, g, _stream()))
+        return g
+
+    def perturb_policy(self):
+        """The perturbation of DDPG_editted.reset (ddpg_editted.py:382-385): ``perturbed_actor_flat`` = actor + noise of the
+        current (device) stddev.  Stream-ordered; ``perturbed_generation`` is the generation it drew."""
+        if self.param_noise is None:
+            raise RuntimeError("the agent was built without param_noise_stddev")
+        self.perturbed_generation = self._perturb(self.perturbed_actor_flat)
+
+    def adapt_param_noise(self, obs_batch, obs_rms=None):
+        """DDPG_editted.adapt_param_noise (ddpg_editted.py:360-376) on a batch of obs0 [m, obs_dim]: perturb the adaptive
+        copy, distance = sqrt(mean((actor(obs) - adaptive_actor(obs))^2)), adapt the device stddev.  Returns the
+        1-element DEVICE tensor holding the distance (no host read; 0. without parameter noise, like the reference)."""
+        if self.param_noise is None:
+            return 0.
+        o = torch.as_tensor(obs_batch, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
+        self._perturb(self.adaptive_actor_flat)
+        a = self._forward(self._desc, o, obs_rms)
+        b = self._forward(self._adaptive_desc, o, obs_rms)
+        pn = self.param_noise
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_param_noise_adapt(a.numel(), _ffi.ptr(a), _ffi.ptr(b), pn.desired_action_stddev,
+                                                      pn.adoption_coefficient, _ffi.ptr(self.d_param_noise_stddev),
+                                                      _ffi.ptr(self.d_param_noise_distance), _stream()))
+        return self.d_param_noise_distance
 
     def set_critic_weights(self, weights):
         """weights: dict W1[obs,h1] b1 W2[h1+act,h2] b2 W3[h2,1] b3 (Critic_Editted, models_editted.py:78-100)."""
@@ -287,15 +412,19 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
     def actor(self, obs, obs_rms=None):
         """Actor_Editted forward (models_editted.py:38-61) on a batch: obs [m, obs_dim] -> [m, act_dim] (normalised
         observations as in :meth:`critic`)."""
+        return self._forward(self._desc, obs, obs_rms)
+
+    def _forward(self, desc, obs, obs_rms=None):
+        """:meth:`actor` through ``desc``: the actor itself or one of its perturbed copies"""
         o = torch.as_tensor(obs, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
         out = torch.empty((o.shape[0], self.act_dim), dtype=torch.float32, device=self.device)
         rms = self._rms_block(obs_rms)
         with torch.cuda.device(self.device):
             if rms is None:
-                _ffi.check(self.lib.ssc_actor_forward(ctypes.byref(self._desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
+                _ffi.check(self.lib.ssc_actor_forward(ctypes.byref(desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
                                                       _stream()))
             else:
-                _ffi.check(self.lib.ssc_actor_forward_rms(ctypes.byref(self._desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
+                _ffi.check(self.lib.ssc_actor_forward_rms(ctypes.byref(desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
                                                           _stream(), _ffi.ptr(rms)))
         return out
 
@@ -308,20 +437,27 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
 
     def get_action(self, state):
         """:206-234 -> DDPG_editted.pi (ddpg_editted.py:255-272)"""
-        action = self.actor(np.asarray(state, np.float32)[None, :])[0].cpu().numpy()   # fp32, like sess.run
+        # pi (ddpg_editted.py:256-259): the perturbed actor acts while training when parameter noise is on
+        desc = self._perturbed_desc if self.param_noise is not None and self.training_enabled else self._desc
+        action = self._forward(desc, np.asarray(state, np.float32)[None, :])[0].cpu().numpy()   # fp32, like sess.run
         noise = self.decaying_ou_action_noise()
         action = action + noise.astype(np.float32)             # in-place add keeps fp32 (:266-270)
         action = np.clip(action, -1.0, 1.0)                    # :271
         return self.scale(self.scale(action))
 
-    def as_policy(self, precision=None, device_epsilon=False, obs_rms=None):
+    def as_policy(self, precision=None, device_epsilon=False, obs_rms=None, perturbed=False):
         """The same action path as a fused-rollout policy (current epsilon).  ``device_epsilon``: the kernel reads
         epsilon from ``self.d_epsilon`` (kept current by a :class:`rl_train.DecaySchedule`) instead of the host value.
-        With observation statistics (the agent's, or ``obs_rms``) the rollout reads them once per launch."""
+        With observation statistics (the agent's, or ``obs_rms``) the rollout reads them once per launch.
+        ``perturbed=True``: the policy over ``perturbed_weights`` (views into ``perturbed_actor_flat``, so every
+        :meth:`perturb_policy` shows in the next launch; LayerNorm parameters are copied unperturbed)."""
         n = self.decaying_ou_action_noise
         if "ln1_g" in self.weights:
             precision = "f32"                    # LayerNorm networks run on the fp32 kernels
-        return ActorPolicy(self.weights, last_layer_tanh=self.lastLayerTanh, precision=precision or "bf16_mfma",
+        if perturbed and self.param_noise is None:
+            raise ValueError("as_policy(perturbed=True) needs an agent built with param_noise_stddev")
+        weights = self.perturbed_weights if perturbed else self.weights
+        return ActorPolicy(weights, last_layer_tanh=self.lastLayerTanh, precision=precision or "bf16_mfma",
                            ou_mu=float(self.ou["mu"]), ou_sigma=float(self.ou["sigma"]), ou_theta=float(self.ou["theta"]),
                            ou_dt=n.dt, ou_epsilon=float(max(n.epsilon, 0)), obs_clip=float(self.observation_range[1]),
                            d_ou_epsilon=self.d_epsilon if device_epsilon else None, d_obs_rms=self._rms_block(obs_rms))
@@ -350,7 +486,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
 
     def start_new_episode(self, state):
         """:249-250 -- ``pass`` in the reference: a bare DDPG agent never marks episode starts in its buffer (only the
-        SmartStart wrapper, the buffer's main agent then, does: smartexplorationcontinuous.py:369)."""
+        SmartStart wrapper, the buffer's main agent then, does: smartexplorationcontinuous.py:369).  With parameter noise
+        the acting copy is perturbed anew, as DDPG_editted.reset does between episodes (ddpg_editted.py:382-385)."""
+        if self.param_noise is not None:
+            self.perturb_policy()
 
     def render(self, env, **kwargs):
         return env.render()
@@ -426,6 +565,8 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         self.remaining_steps_before_train = self.num_steps_before_train
         n = self.num_train_iterations
         B = self.batch_size
+        if self.param_noise is not None:                         # the commented call of :270, once per train()
+            self.adapt_param_noise(np.asarray(self.replay_buffer.sample_batch(B)[0], np.float32))
         cols = [[] for _ in range(5)]
         for _ in range(n):                                       # sample_batch per iteration (:287-289)
             for c, x in zip(cols, self.replay_buffer.sample_batch(B)):

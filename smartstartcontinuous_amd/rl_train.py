@@ -332,7 +332,18 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     generation, sampling) is ordered as in the synchronous loop, and the result is deterministic.  The default follows
     the reference's order: act with the weights of the last completed train().
     ``on_chunk(i, chunk, env)`` -- if given -- is called once chunk i's rollout, append and learner iterations are enqueued.
+
+    An agent with parameter-space noise (``param_noise_stddev``) rolls every chunk with its PERTURBED actor, one
+    perturbation for all envs of the chunk -- the chunk is the vector analogue of the reference's per-episode reset and
+    of its adaption interval (training_editted.py:100-112): behind the learner iterations of chunk i the stddev is adapted
+    on the obs0 of one freshly sampled batch (``agent.adapt_param_noise``) and the acting copy is perturbed anew with the
+    adapted stddev -- both stream-ordered, no host read.  The learner trains ``actor_flat`` only.  Synchronous loop only.
+    The adaption batch comes from the replay ring's own index stream (``replay.sample_indices``), so with the same seed the
+    learner's later batches differ from those of an agent without parameter noise; the run stays deterministic.
     Returns (Summary, losses per chunk, replay)."""
+    param_noise = getattr(agent, "param_noise", None) is not None
+    if param_noise and overlap:
+        raise NotImplementedError("rl_train_vec_ddpg: overlap=True is not supported for an agent with param_noise")
     import torch
     from .replay_buffer import DeviceReplayBuffer
     from .vec_env import EpisodeRing, TransitionChunk
@@ -423,7 +434,11 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         finish()
         return summary, losses, replay
 
-    pd = env.policy_desc(agent.as_policy(device_epsilon=True))   # weights are views into the flat parameter arrays
+    if param_noise:
+        pd = env.policy_desc(agent.as_policy(device_epsilon=True, perturbed=True))   # views into perturbed_actor_flat
+        agent.perturb_policy()
+    else:
+        pd = env.policy_desc(agent.as_policy(device_epsilon=True))   # weights are views into the flat parameter arrays
     for i in range(num_chunks):
         out = env.rollout(chunk_steps, out=chunk, ring=ring, policy_desc=pd)
         after_rollout()
@@ -432,6 +447,11 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         l = agent.train_from(replay, train_iters)
         if l is not None:
             losses.append(l)
+        if param_noise:
+            if len(replay) >= agent.batch_size:                  # ddpg_editted.py:360-376 on one fresh batch's obs0
+                rows = replay.sample_indices(1, agent.batch_size)[0].long()
+                agent.adapt_param_noise(replay.s.index_select(0, rows))
+            agent.perturb_policy()                               # the next chunk's actor, with the adapted stddev
         if on_chunk is not None:
             on_chunk(i, out, env)
         if (i + 1) % drain_every == 0:
@@ -460,6 +480,8 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
     c - 1 and its plans are used one chunk later than in the sequential loop; the chunk costs max(rollout, selection)
     instead of their sum.
     Returns (Summary, losses per chunk, replay)."""
+    if getattr(getattr(smart, "agent", None), "param_noise", None) is not None:
+        raise NotImplementedError("rl_train_vec_smartstart: an agent with param_noise is not supported on the SmartStart loop")
     import torch
     from .replay_buffer import DeviceReplayBuffer
     from .vec_env import EpisodeRing, TransitionChunk

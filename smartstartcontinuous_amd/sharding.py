@@ -290,6 +290,9 @@ def rl_train_sharded_ddpg(env, agent, num_chunks, chunk_steps, rank, world, lear
     the chunk's transition log.
 
     Returns (Summary of THIS rank's finished episodes, losses per chunk [learner only], replay [learner only])."""
+    if getattr(agent, "param_noise", None) is not None:
+        # the reference averages the adaptive distance over its MPI ranks; that exchange is not built yet
+        raise NotImplementedError("rl_train_sharded_ddpg: an agent with param_noise is not supported on the sharded loop")
     if getattr(agent, "obs_rms", None) is not None:
         # the reference all-reduces RunningMeanStd over its MPI ranks; that exchange is not built yet
         raise NotImplementedError("rl_train_sharded_ddpg: normalize_observations=True is not supported on the sharded loop")
