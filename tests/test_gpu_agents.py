@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import ssc_oracle as O
+from tests.gpu_util import x_hat64
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -423,12 +424,31 @@ class _BoxEnv:
         self.action_space = spaces.Box(low=np.array([-1.0], np.float32), high=np.array([1.0], np.float32))
 
 
+def _assert_inputs_reach_the_clip(obs_rms, rows, obs_clip=5.0):
+    """Conditions on the INPUTS of a run on floor statistics: in the sampled rows some component of x_hat sits on +clip and
+    some on -clip, and at least half of the rows have no clipped component (their gradients still depend on the inputs)."""
+    xh = x_hat64(rows, obs_rms, obs_clip)
+    assert (xh == obs_clip).any() and (xh == -obs_clip).any()
+    assert np.mean((np.abs(xh) < obs_clip).all(axis=1)) >= 0.5
+
+
 def _ddpg_kernel_vs_oracle(ssc, obs_dim, h1, h2, B=64, ch1=None, ch2=None, n_iters=6, llts=(True, False), cap=1000, layer_norm=False,
-                           critic_l2_reg=0.0, clip_norm=None):
+                           critic_l2_reg=0.0, clip_norm=None, obs_rms=None, obs_range=None, expect_clip=None, rms_rows=None):
     """ssc_ddpg_train_ws against the fp64 restatement of ddpg_editted.py:287-339 (itself cross-checked against torch
-    autograd on the CPU): parameters, targets, Adam moments, losses after ``n_iters`` iterations on batches of ``B``."""
+    autograd on the CPU): parameters, targets, all four Adam moment arrays, losses after ``n_iters`` iterations on batches
+    of ``B``.
+
+    ``obs_rms`` (an ObsRms; normalize_observations): the device gets the RAW s / s2 and ``train_on(..., obs_rms=obs_rms)``,
+    the oracle clip((x - mean) / std, -5, 5) formed in fp64 from the fp32 mean / std of ``obs_rms.mean_std()``.
+    ``obs_range`` = (low, high) per component replaces the ranges the raw observations are drawn from.  ``expect_clip``:
+    True asserts on the host, before the launch, that the sampled rows reach both clips in s and in s2 while half of them
+    stay clear of it, False that no sampled input is clipped.  ``rms_rows``: the iterations run as TWO launches of
+    ``n_iters // 2``, with ``obs_rms.update_rows(rms_rows)`` between them (it must move every mean and std by more than 1e-2);
+    the oracle normalises each half with the statistics of its launch and carries its Adam state across."""
     from smartstartcontinuous_amd.agents import DDPG_Baselines_agent
     ch1, ch2 = ch1 or h1, ch2 or h2
+    assert obs_rms is not None or (expect_clip is None and rms_rows is None), "expect_clip / rms_rows need obs_rms"
+    assert rms_rows is None or len(llts) == 1      # the update stays in obs_rms
     rng = np.random.default_rng(11)
     env = ssc.make("MountainCarContinuous-v0") if obs_dim == 2 else _BoxEnv(obs_dim)
     for llt in llts:
@@ -443,9 +463,12 @@ def _ddpg_kernel_vs_oracle(ssc, obs_dim, h1, h2, B=64, ch1=None, ch2=None, n_ite
         agent.target_actor_flat += 0.01
         agent.target_critic_flat -= 0.01
         cap = max(cap, B)
-        s = rng.uniform(-1.2, 0.6, (cap, obs_dim)).astype(np.float32)
-        if obs_dim == 3:
-            s[:, 2] = rng.uniform(-8, 8, cap)            # Pendulum's theta-dot: observation_range (-5, 5) clips it
+        if obs_range is not None:
+            s = rng.uniform(obs_range[0], obs_range[1], (cap, obs_dim)).astype(np.float32)
+        else:
+            s = rng.uniform(-1.2, 0.6, (cap, obs_dim)).astype(np.float32)
+            if obs_dim == 3:
+                s[:, 2] = rng.uniform(-8, 8, cap)            # Pendulum's theta-dot: observation_range (-5, 5) clips it
         a = rng.uniform(-1, 1, (cap, 1)).astype(np.float32)
         r = (rng.normal(size=cap) * 0.5).astype(np.float32)
         t = (rng.random(cap) < 0.1)
@@ -458,16 +481,36 @@ def _ddpg_kernel_vs_oracle(ssc, obs_dim, h1, h2, B=64, ch1=None, ch2=None, n_ite
         o_tc = O.unflatten_params(agent.target_critic_flat.cpu().numpy().astype(np.float64), o_c)
         na, nc = agent.actor_flat.numel(), agent.critic_flat.numel()
         adam = dict(m_actor=np.zeros(na), v_actor=np.zeros(na), t_actor=0, m_critic=np.zeros(nc), v_critic=np.zeros(nc), t_critic=0)
-        ref_losses = []
-        for it in range(n_iters):
-            bi = idx[it]
-            o_a, o_c, o_ta, o_tc, adam, cl, al = O.ddpg_train_step(
-                o_a, o_c, o_ta, o_tc, adam, (s[bi], a[bi], r[bi], t[bi], s2[bi]), gamma=0.99, tau=0.001,
-                actor_lr=1e-3, critic_lr=1e-3, last_layer_tanh=llt, obs_clip=5.0, critic_l2_reg=critic_l2_reg, clip_norm=clip_norm)
-            ref_losses.append((cl, al))
         dev = lambda x, dt: torch.as_tensor(x, dtype=dt, device="cuda").contiguous()
-        losses = agent.train_on(dev(s, torch.float32), dev(a, torch.float32), dev(r, torch.float32), dev(t, torch.uint8),
-                                dev(s2, torch.float32), dev(idx, torch.int32), n_iters)
+        d_rows = (dev(s, torch.float32), dev(a, torch.float32), dev(r, torch.float32), dev(t, torch.uint8), dev(s2, torch.float32))
+        ref_losses, got_losses = [], []
+        launches = [(0, n_iters)] if rms_rows is None else [(0, n_iters // 2), (n_iters // 2, n_iters)]
+        for first, last in launches:
+            if first > 0:      # the statistics move between two launches on the same agent and the same ObsRms object
+                before = obs_rms.mean_std()
+                obs_rms.update_rows(rms_rows)
+                after = obs_rms.mean_std()
+                assert all(np.min(np.abs(x - y)) > 1e-2 for x, y in zip(before, after)), (before, after)
+            o_s, o_s2 = (s, s2) if obs_rms is None else (x_hat64(s, obs_rms), x_hat64(s2, obs_rms))
+            if expect_clip is not None:
+                used = np.unique(idx[first:last])
+                if expect_clip:
+                    _assert_inputs_reach_the_clip(obs_rms, s[used])
+                    _assert_inputs_reach_the_clip(obs_rms, s2[used])
+                else:
+                    assert np.abs(o_s[used]).max() < 5.0 and np.abs(o_s2[used]).max() < 5.0
+            for it in range(first, last):
+                bi = idx[it]
+                o_a, o_c, o_ta, o_tc, adam, cl, al = O.ddpg_train_step(
+                    o_a, o_c, o_ta, o_tc, adam, (o_s[bi], a[bi], r[bi], t[bi], o_s2[bi]), gamma=0.99, tau=0.001,
+                    actor_lr=1e-3, critic_lr=1e-3, last_layer_tanh=llt, obs_clip=5.0, critic_l2_reg=critic_l2_reg, clip_norm=clip_norm)
+                ref_losses.append((cl, al))
+            d_idx = dev(idx[first:last], torch.int32)
+            if obs_rms is None:
+                got_losses.append(agent.train_on(*d_rows, d_idx, last - first))
+            else:
+                got_losses.append(agent.train_on(*d_rows, d_idx, last - first, obs_rms=obs_rms))
+        losses = torch.cat(got_losses)
         torch.cuda.synchronize()
         assert agent._adam_t.cpu().tolist() == [n_iters, n_iters]
         got_l = losses.cpu().numpy()
@@ -477,8 +520,10 @@ def _ddpg_kernel_vs_oracle(ssc, obs_dim, h1, h2, B=64, ch1=None, ch2=None, n_ite
         assert np.max(np.abs(agent.critic_flat.cpu().numpy() - O.flatten_params(o_c))) <= tol
         assert np.max(np.abs(agent.target_actor_flat.cpu().numpy() - O.flatten_params(o_ta))) <= tol
         assert np.max(np.abs(agent.target_critic_flat.cpu().numpy() - O.flatten_params(o_tc))) <= tol
-        assert np.allclose(agent._adam_actor[0].cpu().numpy(), adam["m_actor"], rtol=1e-3, atol=1e-7)
-        assert np.allclose(agent._adam_critic[1].cpu().numpy(), adam["v_critic"], rtol=2e-3, atol=1e-9)
+        # (Adam's first step is lr * sign(g) whatever the size of g: a mis-scaled gradient shows in the moments only)
+        for net, mv in (("actor", agent._adam_actor), ("critic", agent._adam_critic)):
+            assert np.allclose(mv[0].cpu().numpy(), adam["m_" + net], rtol=1e-3, atol=1e-7), "m_" + net
+            assert np.allclose(mv[1].cpu().numpy(), adam["v_" + net], rtol=2e-3, atol=1e-9), "v_" + net
         # the weight VIEWS used by the forward kernels see the update
         assert np.max(np.abs(agent.weights["W2"].cpu().numpy() - o_a["W2"])) <= tol
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import ssc_oracle as O
-from tests.gpu_util import actor_weights
+from tests.gpu_util import actor_weights, x_hat64 as _x_hat64
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -39,11 +39,6 @@ def _stats(obs_dim, seed):
 def _x_hat32(x, rms):
     mean, std = rms.mean_std()
     return np.clip((np.asarray(x, np.float32) - mean) / std, np.float32(-CLIP), np.float32(CLIP)).astype(np.float32)
-
-
-def _x_hat64(x, rms):
-    mean, std = rms.mean_std()
-    return np.clip((np.asarray(x, np.float64) - mean.astype(np.float64)) / std.astype(np.float64), -CLIP, CLIP)
 
 
 def _agent(ssc, obs_dim, h, precision="f32", batch=64):

@@ -4,6 +4,7 @@ cross-checked structurally against independent torch-CPU fp64 implementations.""
 import ctypes
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import ssc_oracle as O
@@ -313,6 +314,83 @@ def test_ddpg_l2_regularisation_and_gradient_clipping_match_torch_autograd():
         assert np.allclose(adam2["m_actor"], 0.1 * gflat_a, rtol=1e-9, atol=1e-14)
 
 
+@pytest.mark.parametrize("ln", [False, True])
+@pytest.mark.parametrize("llt", [True, False])
+@pytest.mark.parametrize("obs_dim", [3, 8])
+def test_ddpg_train_step_on_clipped_inputs_matches_torch_autograd(obs_dim, llt, ln):
+    """What the normalising learner tests feed the oracle: obs_dim 3 and 8, last_layer_tanh False as well as True, LayerNorm
+    together with critic_l2_reg and clip_norm, and observations with components exactly ON +-obs_clip and beyond it (the
+    normalised inputs of statistics on the std floor) -- losses, clipped gradients (through both Adam moments of the first
+    step), the step itself and the target update against torch autograd on the clamped inputs."""
+    import torch.nn.functional as F
+    rng = np.random.default_rng(100 + 10 * obs_dim + 2 * llt + ln)
+    l2, clip, obs_clip = 0.03, 0.3, 5.0
+    if ln:
+        aw, cw = ln_params(rng, obs_dim, 24, 12, 1), ln_params(rng, obs_dim, 20, 16, 1, extra=1)
+    else:
+        aw = {k: v.astype(np.float64) for k, v in actor_weights(obs_dim, 24, 12, seed=3 + obs_dim, w3_scale=0.3).items()}
+        cw = dict(W1=rng.normal(size=(obs_dim, 20)) * 0.3, b1=rng.normal(size=20) * 0.1, W2=rng.normal(size=(21, 16)) * 0.3,
+                  b2=rng.normal(size=16) * 0.1, W3=rng.normal(size=(16, 1)) * 0.4, b3=rng.normal(size=1) * 0.1)
+    taw = {k: v + 0.01 * rng.normal(size=v.shape) for k, v in aw.items()}
+    tcw = {k: v + 0.01 * rng.normal(size=v.shape) for k, v in cw.items()}
+    keys = O.param_keys(aw)
+    B = 48
+    s_np = rng.uniform(-6.0, 6.0, (B, obs_dim))
+    s_np[0::4, 0], s_np[1::4, obs_dim - 1], s_np[2::4, 1] = obs_clip, -obs_clip, np.nextafter(obs_clip, np.inf)
+    s2_np = s_np + 0.05 * rng.normal(size=(B, obs_dim))
+    s2_np[0::6, 1], s2_np[3::6, obs_dim - 1] = -obs_clip, obs_clip
+    for x in (s_np, s2_np):     # on the clip, beyond it on both sides, and rows clear of it
+        assert (x == obs_clip).any() and (x == -obs_clip).any() and (x > obs_clip).any() and (x < -obs_clip).any()
+    batch = (s_np, rng.uniform(-1, 1, (B, 1)), rng.normal(size=B) * 2, rng.random(B) < 0.1, s2_np)
+    na, nc = O.flatten_params(aw).size, O.flatten_params(cw).size
+    adam = dict(m_actor=np.zeros(na), v_actor=np.zeros(na), t_actor=0, m_critic=np.zeros(nc), v_critic=np.zeros(nc), t_critic=0)
+    a2, c2, ta2, tc2, adam2, closs, aloss = O.ddpg_train_step(aw, cw, taw, tcw, adam, batch, last_layer_tanh=llt, obs_clip=obs_clip,
+                                                              critic_l2_reg=l2, clip_norm=clip)
+    T = lambda d: {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in d.items()}
+    pa, pc = T(aw), T(cw)
+    s, a, r, t, s2 = (torch.tensor(np.asarray(x, np.float64)) for x in batch)
+    s, s2 = s.clamp(-obs_clip, obs_clip), s2.clamp(-obs_clip, obs_clip)
+    act_fn = torch.tanh if llt else torch.relu
+    lnf = (lambda x, p, w: F.layer_norm(x, (x.shape[-1],), p[w + "_g"], p[w + "_b"], eps=1e-12)) if ln else (lambda x, p, w: x)
+
+    def actor(p, x):
+        h = torch.relu(lnf(x @ p["W1"] + p["b1"], p, "ln1"))
+        return torch.tanh(act_fn(lnf(h @ p["W2"] + p["b2"], p, "ln2")) @ p["W3"] + p["b3"])
+
+    def critic(p, x, u):
+        h = torch.cat([torch.relu(lnf(x @ p["W1"] + p["b1"], p, "ln1")), u], dim=1)
+        return act_fn(lnf(h @ p["W2"] + p["b2"], p, "ln2")) @ p["W3"] + p["b3"]
+    with torch.no_grad():
+        y = r[:, None] + (1 - t[:, None]) * 0.99 * critic(T(tcw), s2, actor(T(taw), s2))
+    closs_t = ((critic(pc, s, a) - y) ** 2).mean() + l2 * sum((pc[k] ** 2).sum() / 2 for k in ("W1", "W2", "W3"))
+    aloss_t = -critic(pc, s, actor(pa, s)).mean()
+    gc = torch.autograd.grad(closs_t, [pc[k] for k in keys])
+    ga = torch.autograd.grad(aloss_t, [pa[k] for k in keys])
+    assert abs(closs - closs_t.item()) < 1e-12 and abs(aloss - aloss_t.item()) < 1e-12
+    clipv = lambda g: (g * (clip / max(float(g.norm()), clip))).numpy()
+    gflat_c = np.concatenate([clipv(g).reshape(-1) for g in gc])
+    gflat_a = np.concatenate([clipv(g).reshape(-1) for g in ga])
+    assert max(float(g.norm()) for g in list(gc) + list(ga)) > clip                 # the clip binds for some variable
+    assert np.allclose(adam2["m_critic"], 0.1 * gflat_c, rtol=1e-9, atol=1e-14)
+    assert np.allclose(adam2["m_actor"], 0.1 * gflat_a, rtol=1e-9, atol=1e-14)
+    assert np.allclose(adam2["v_critic"], 0.001 * gflat_c ** 2, rtol=1e-9, atol=1e-26)
+    assert np.allclose(adam2["v_actor"], 0.001 * gflat_a ** 2, rtol=1e-9, atol=1e-26)
+
+    def adam1(p, g, lr):
+        a_ = lr * np.sqrt(1 - 0.999) / (1 - 0.9)
+        return p - a_ * (0.1 * g) / (np.sqrt(0.001 * g * g) + 1e-8)
+    for i, k in enumerate(keys):
+        gck, gak = clipv(gc[i]), clipv(ga[i])
+        okc, oka = np.abs(gck) > 1e-10, np.abs(gak) > 1e-10    # (Adam's first step is ~ -lr * sign(g))
+        assert np.allclose(c2[k][okc], adam1(cw[k], gck, 1e-3)[okc], rtol=1e-7, atol=1e-12), k
+        assert np.allclose(a2[k][oka], adam1(aw[k], gak, 1e-4)[oka], rtol=1e-7, atol=1e-12), k
+        assert np.allclose(ta2[k], 0.999 * taw[k] + 0.001 * a2[k]) and np.allclose(tc2[k], 0.999 * tcw[k] + 0.001 * c2[k])
+    # clipping happens inside the step: the same step on inputs clamped beforehand is the same step
+    pre = (np.clip(s_np, -obs_clip, obs_clip), *batch[1:4], np.clip(s2_np, -obs_clip, obs_clip))
+    a3, c3, *_ = O.ddpg_train_step(aw, cw, taw, tcw, adam, pre, last_layer_tanh=llt, obs_clip=None, critic_l2_reg=l2, clip_norm=clip)
+    assert all(np.array_equal(a2[k], a3[k]) and np.array_equal(c2[k], c3[k]) for k in keys)
+
+
 def test_mlp_train_step_matches_torch_autograd_and_adam():
     """oracle.mlp_train_step (manual backprop + tf-style Adam) against torch autograd + torch.optim.Adam
     (same update rule as tf.train.AdamOptimizer up to where epsilon enters -- compared after ONE step where
@@ -371,8 +449,6 @@ def test_pendulum_known_answers_pin_both_oracles(oracle_clib):
 
 
 # --------------------------------------------------------------------------- the bf16 bound of the simulation matrix --
-import pytest                                     # noqa: E402
-
 from tests import sim_cases as SC                 # noqa: E402
 
 
