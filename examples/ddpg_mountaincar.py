@@ -45,8 +45,6 @@ def main():
     ap.add_argument("--param-noise", type=float, default=None, metavar="STDDEV",
                     help="adaptive parameter-space noise with this initial (and desired action) stddev, on top of the OU noise")
     args = ap.parse_args()
-    if args.param_noise is not None and args.overlap:
-        ap.error("--param-noise needs the synchronous loop (no --overlap)")
     np.random.seed(args.seed)
     if args.mode == "single":
         env = ssc.Continuous_MountainCarEnv_Editted.make_timed_env(args.power_scalar, max_episode_steps=1000,

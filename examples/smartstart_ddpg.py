@@ -44,6 +44,8 @@ def main():
     ap.add_argument("--nav-precision", choices=("f32", "bf16_mfma"), default="f32", help="forward-simulation path of the navigator (vec mode; f32 = the fused VALU kernel for one small hidden layer)")
     ap.add_argument("--kde-max-states", type=int, default=500000, help="bound the KDE's data set by a strided subsample of the ring (vec mode; default: the reference's replay capacity; 0 = every state)")
     ap.add_argument("--sequential-selection", action="store_true", help="vec mode: select, then roll (default: the selection of a chunk overlaps its rollout and its plans go on offer one chunk later)")
+    ap.add_argument("--param-noise", type=float, default=None, metavar="STDDEV",
+                    help="vec mode: adaptive parameter-space noise with this initial (and desired action) stddev on the base agent, on top of the OU noise")
     ap.add_argument("--replay-capacity", type=int, default=None, help="records in the device ring (default: two full episodes per env)")
     args = ap.parse_args()
     np.random.seed(args.seed)
@@ -83,7 +85,8 @@ def vec(args, dyn_model):
     ddpg = DDPG_Baselines_agent(ssc.make("MountainCarContinuous-v0"), None, batch_size=args.batch, num_train_iterations=args.train_iters,
                                 ou_epsilon=1.0, ou_min_epsilon=0.01, ou_epsilon_decay_factor=.99, ou_mu=0.4, ou_sigma=0.6,
                                 ou_theta=.15, actor_lr=0.001, actor_h1=64, actor_h2=32, critic_lr=0.001, critic_h1=64,
-                                critic_h2=32, lastLayerTanh=True, seed=args.seed, precision="bf16_mfma")
+                                critic_h2=32, lastLayerTanh=True, seed=args.seed, precision="bf16_mfma",
+                                param_noise_stddev=args.param_noise)
     dyn_model.precision = args.nav_precision     # fused kernels both: bf16 MFMA (any size) or fp32 VALU (one small hidden layer)
     dyn_model.invalidate()
     smart = ssc.VecSmartStart(env, ddpg, dyn_model, eta=0.5, eta_decay_factor=1., n_ss=2000, n_plans=args.plans,
@@ -107,6 +110,8 @@ def vec(args, dyn_model):
           "best return %.2f; %.1f %% of the env-steps were navigated; %d selections, %d plans published"
           % (args.envs, args.chunk_steps, args.chunks, dt, steps / dt, dt / (args.chunk_steps * args.chunks) * 1e3, len(eps), goals,
              summary.best_reward, 100.0 * sum(nav_steps) / steps, smart.selections, smart.pool.published))
+    if ddpg.param_noise is not None:
+        print("parameter noise:", ddpg.param_noise.get_stats())
 
     def timed(fn, reps=5):
         torch.cuda.synchronize()

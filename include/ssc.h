@@ -649,12 +649,30 @@ int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *ddpg, const ssc_replay_view *repl
  * ssc_param_noise_adapt: *d_distance = sqrt(mean((a - b)^2)) over count = batch * act_dim elements (ddpg_editted.py:166;
  * one workgroup, f64 accumulation in a fixed order), then AdaptiveParamNoiseSpec.adapt of baselines 0.1.5 on the device
  * value: *d_stddev /= coefficient if distance > desired, else *d_stddev *= coefficient (fp32; a tie multiplies).
- * 1 <= count <= 4096 * SSC_MAX_ACT, coefficient > 1.  a and b come from two ssc_actor_forward[_rms] calls. */
+ * 1 <= count <= 4096 * SSC_MAX_ACT, coefficient > 1.  a and b come from two ssc_actor_forward[_rms] calls.
+ *
+ * ssc_param_noise_cycle: one adaption interval in ONE launch (one workgroup).  Equal to, in this order,
+ *   ssc_param_noise_perturb(d_src -> adaptive copy, generation_adaptive)      with the stddev in *d_stddev,
+ *   a = actor(obs), b = adaptive_actor(obs)                                   obs [m][obs_dim], 1 <= m <= 4096,
+ *   ssc_param_noise_adapt(a, b) -> *d_distance, *d_stddev,
+ *   ssc_param_noise_perturb(d_src -> d_dst, generation_acting)                with the NEW stddev,
+ * where the adaptive copy lives in LDS only and never reaches HBM.  `actor` describes the PLAIN actor: its parameter
+ * pointers must lie inside d_src[0 .. n) (the copy is addressed by the same offsets); both forwards run in fp32 with
+ * every unit summed in index order, whatever `precision` says, with or without LayerNorm.  d_rms: as in
+ * ssc_actor_forward_rms (NULL: none).  The distance is an f64 sum in a fixed order (no atomics): the same bits run to
+ * run.  *d_stddev and d_dst carry the bits of the four-call sequence whenever both agree on which side of `desired` the
+ * distance lies; the distance itself agrees to the rounding of the fp32 forwards.  SSC_EINVAL for m, n or coefficient out
+ * of range and for d_dst == d_src; SSC_EUNSUPPORTED, with the byte count in ssc_last_error(), when the adaptive copy plus
+ * the working space of a 4-row tile exceed the 160 KB of LDS (a 200-100 actor fits, a 400-300 one does not). */
 int ssc_param_noise_perturb(int64_t n, const float *d_src, float *d_dst, const float *d_stddev, int64_t skip0_begin,
                             int64_t skip0_end, int64_t skip1_begin, int64_t skip1_end, uint64_t seed, uint64_t generation,
                             ssc_stream_t stream);
 int ssc_param_noise_adapt(int64_t count, const float *d_a, const float *d_b, float desired, float coefficient,
                           float *d_stddev, float *d_distance, ssc_stream_t stream);
+int ssc_param_noise_cycle(const ssc_actor_desc *actor, int64_t m, const float *d_obs, const double *d_rms, int64_t n,
+                          const float *d_src, int64_t skip0_begin, int64_t skip0_end, int64_t skip1_begin, int64_t skip1_end,
+                          uint64_t seed, uint64_t generation_adaptive, uint64_t generation_acting, float desired,
+                          float coefficient, float *d_stddev, float *d_distance, float *d_dst, ssc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Dynamics-model training step

@@ -201,6 +201,9 @@ _SIGNATURES = {
     "ssc_param_noise_perturb": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint64,
                                         c_uint64, c_void_p]),
     "ssc_param_noise_adapt": (c_int, [c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "ssc_param_noise_cycle": (c_int, [POINTER(ActorDesc), c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                      c_int64, c_int64, c_uint64, c_uint64, c_uint64, c_float, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
     "ssc_dataset_scan_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_dataset_scan": (c_int, [POINTER(TransitionLog), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),

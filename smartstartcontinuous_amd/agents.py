@@ -370,6 +370,31 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                                                       _ffi.ptr(self.d_param_noise_distance), _stream()))
         return self.d_param_noise_distance
 
+    def param_noise_cycle(self, obs_batch, dst=None, obs_rms=None):
+        """:meth:`adapt_param_noise` on ``obs_batch`` [m <= 4096, obs_dim] followed by :meth:`perturb_policy`, in ONE launch
+        (``ssc_param_noise_cycle``): the adaptive copy is drawn, used and dropped inside the kernel (``adaptive_actor_flat``
+        is not touched), the device stddev is adapted and ``dst`` (default ``perturbed_actor_flat``) becomes actor + noise
+        of the NEW stddev.  Consumes two generations, adaptive then acting, exactly like the pair of calls, and leaves
+        ``perturbed_generation`` at the acting one.  Both forwards run in fp32.  Returns the 1-element DEVICE tensor
+        holding the distance."""
+        if self.param_noise is None:
+            raise RuntimeError("the agent was built without param_noise_stddev")
+        o = torch.as_tensor(obs_batch, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
+        dst = self.perturbed_actor_flat if dst is None else dst
+        if dst.dtype != torch.float32 or dst.numel() != self.actor_flat.numel() or not dst.is_contiguous():
+            raise ValueError("dst must be a contiguous fp32 array of the size of actor_flat")
+        g = self.param_noise_generation
+        pn, rms = self.param_noise, self._rms_block(obs_rms)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_param_noise_cycle(
+                ctypes.byref(self._desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(rms), self.actor_flat.numel(),
+                _ffi.ptr(self.actor_flat), *self._pn_skip, self.param_noise_seed, g, g + 1, pn.desired_action_stddev,
+                pn.adoption_coefficient, _ffi.ptr(self.d_param_noise_stddev), _ffi.ptr(self.d_param_noise_distance),
+                _ffi.ptr(dst), _stream()))
+        self.param_noise_generation = g + 2
+        self.perturbed_generation = g + 1
+        return self.d_param_noise_distance
+
     def set_critic_weights(self, weights):
         """weights: dict W1[obs,h1] b1 W2[h1+act,h2] b2 W3[h2,1] b3 (Critic_Editted, models_editted.py:78-100)."""
         self.critic_flat, self.critic_weights = flatten_params(weights, self.device)

@@ -337,13 +337,24 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     perturbation for all envs of the chunk -- the chunk is the vector analogue of the reference's per-episode reset and
     of its adaption interval (training_editted.py:100-112): behind the learner iterations of chunk i the stddev is adapted
     on the obs0 of one freshly sampled batch (``agent.adapt_param_noise``) and the acting copy is perturbed anew with the
-    adapted stddev -- both stream-ordered, no host read.  The learner trains ``actor_flat`` only.  Synchronous loop only.
+    adapted stddev -- both stream-ordered, no host read.  The learner trains ``actor_flat`` only.
     The adaption batch comes from the replay ring's own index stream (``replay.sample_indices``), so with the same seed the
     learner's later batches differ from those of an agent without parameter noise; the run stays deterministic.
+
+    ``overlap=True`` with parameter noise: the rollouts act with one of TWO perturbed copies (chunk i with copy i & 1).
+    On the learner stream, behind the iterations of chunk i, ONE launch (``agent.param_noise_cycle``) adapts the stddev on
+    a fresh batch and writes copy (i + 1) & 1 -- the one rollout i + 1 reads -- and that rollout waits for the event
+    recorded behind it, so no copy is read while it is written.  The acting copy is perturbed from the actor as of the END
+    of train i: the noise centre is NOT one chunk stale, while the plain overlap snapshot is; the price is that rollout
+    i + 1 starts behind the learner iterations of chunk i instead of beside them (the rollout still runs on its own
+    stream, and the host still runs ahead).  With normalize_observations the cycle reads the live statistics block on the
+    learner stream and the rollout the snapshot.  As in the synchronous loop, only the adaption is skipped while the ring
+    holds fewer than ``batch_size`` records.  When the loop ends ``agent.perturbed_actor_flat`` holds the last copy.
     Returns (Summary, losses per chunk, replay)."""
     param_noise = getattr(agent, "param_noise", None) is not None
-    if param_noise and overlap:
-        raise NotImplementedError("rl_train_vec_ddpg: overlap=True is not supported for an agent with param_noise")
+    if param_noise and overlap and not hasattr(agent, "param_noise_cycle"):
+        raise NotImplementedError("rl_train_vec_ddpg: overlap=True with param_noise needs an agent with param_noise_cycle "
+                                  "(the one-launch adapt and re-perturb)")
     import torch
     from .replay_buffer import DeviceReplayBuffer
     from .vec_env import EpisodeRing, TransitionChunk
@@ -383,17 +394,27 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         snap = agent.actor_flat.clone()                  # the weights the NEXT rollout acts with
         rms = getattr(agent, "obs_rms", None)
         rms_snap = rms.block.clone() if rms is not None else None   # ... and the observation statistics (normalize_observations)
-        views, o = {}, 0
-        for k, v in agent.weights.items():               # same order and shapes as the flat array (flatten_params)
-            views[k] = snap[o:o + v.numel()].view(v.shape)
-            o += v.numel()
         rolled2 = [torch.cuda.Event(), torch.cuda.Event()]
         appended = [torch.cuda.Event(), torch.cuda.Event()]
         snap_ready = torch.cuda.Event()
         live = agent.as_policy(device_epsilon=True)
-        pd = env.policy_desc(ActorPolicy(views, last_layer_tanh=live.last_layer_tanh, precision=live.precision, ou_mu=live.ou_mu,
-                                         ou_sigma=live.ou_sigma, ou_theta=live.ou_theta, ou_dt=live.ou_dt,
-                                         obs_clip=live.obs_clip, d_ou_epsilon=agent.d_epsilon, d_obs_rms=rms_snap))
+
+        def policy_over(flat):
+            views, o = {}, 0
+            for k, v in agent.weights.items():           # same order and shapes as the flat array (flatten_params)
+                views[k] = flat[o:o + v.numel()].view(v.shape)
+                o += v.numel()
+            return env.policy_desc(ActorPolicy(views, last_layer_tanh=live.last_layer_tanh, precision=live.precision,
+                                               ou_mu=live.ou_mu, ou_sigma=live.ou_sigma, ou_theta=live.ou_theta,
+                                               ou_dt=live.ou_dt, obs_clip=live.obs_clip, d_ou_epsilon=agent.d_epsilon,
+                                               d_obs_rms=rms_snap))
+
+        if param_noise:                                  # rollout i acts with perturbed copy i & 1
+            acting = [agent.perturbed_actor_flat, torch.empty_like(agent.perturbed_actor_flat)]
+            pds = [policy_over(acting[0]), policy_over(acting[1])]
+            agent.perturb_policy()                       # copy 0, as the synchronous loop perturbs in front of chunk 0
+        else:
+            pds = [policy_over(snap)] * 2
         act.wait_stream(cur)
 
         drained = torch.cuda.Event()
@@ -402,7 +423,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             for e in wait_for:
                 act.wait_event(e)
             with torch.cuda.stream(act):
-                env.rollout(chunk_steps, out=chunks[b], ring=ring, policy_desc=pd)
+                env.rollout(chunk_steps, out=chunks[b], ring=ring, policy_desc=pds[b])
                 after_rollout()
                 rolled2[b].record(act)
 
@@ -414,13 +435,22 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             replay.append_chunk(chunks[b], reward_scale=agent.reward_scale, last_steps=replay_last_steps)
             update_obs_rms(agent, chunks[b], replay_last_steps)
             appended[b].record(cur)
-            snap.copy_(agent.actor_flat)                 # behind train i-1 on this stream, in front of train i
+            if not param_noise:
+                snap.copy_(agent.actor_flat)             # behind train i-1 on this stream, in front of train i
             if rms_snap is not None:
                 rms_snap.copy_(rms.block)                # (the side-stream rollout must not read the block while it is updated)
-            snap_ready.record(cur)
+            if not param_noise:
+                snap_ready.record(cur)
             l = agent.train_from(replay, train_iters)
             if l is not None:
                 losses.append(l)
+            if param_noise:                              # copy b ^ 1 = actor as of the end of train i + noise of the adapted stddev
+                if len(replay) >= agent.batch_size:
+                    rows = replay.sample_indices(1, agent.batch_size)[0].long()
+                    agent.param_noise_cycle(replay.s.index_select(0, rows), dst=acting[b ^ 1])
+                else:
+                    agent.perturbed_generation = agent._perturb(acting[b ^ 1])
+                snap_ready.record(cur)
             if on_chunk is not None:
                 on_chunk(i, chunks[b], env)
             extra = []
@@ -431,6 +461,8 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             if i + 1 < num_chunks:                       # chunk buffer b^1 was last read by append i-1
                 launch_rollout(b ^ 1, [snap_ready] + extra + ([appended[b ^ 1]] if i >= 1 else []))
         cur.wait_stream(act)
+        if param_noise and num_chunks & 1:               # the last perturbation went into the second copy
+            acting[0].copy_(acting[1])
         finish()
         return summary, losses, replay
 
@@ -479,9 +511,17 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
     c + 1 (published on the rollout's stream behind chunk c: deterministic).  The selection then sees the ring as of chunk
     c - 1 and its plans are used one chunk later than in the sequential loop; the chunk costs max(rollout, selection)
     instead of their sum.
+
+    A base agent with parameter-space noise (``param_noise_stddev``): the per-step actor launch of the envs in agent mode
+    reads the PERTURBED actor (``VecSmartStart.acting_desc``), and once per chunk, behind the learner iterations, ONE launch
+    (``agent.param_noise_cycle``) adapts the stddev on the obs0 of a fresh replay batch and perturbs the acting copy anew
+    (only the perturbation while the ring holds fewer than ``batch_size`` records).  The OU noise is still added as
+    configured; navigating steps are untouched; the selection's Q(s, pi(s)) uses the plain actor.
     Returns (Summary, losses per chunk, replay)."""
-    if getattr(getattr(smart, "agent", None), "param_noise", None) is not None:
-        raise NotImplementedError("rl_train_vec_smartstart: an agent with param_noise is not supported on the SmartStart loop")
+    base = getattr(smart, "agent", None)
+    if getattr(base, "param_noise", None) is not None and not hasattr(base, "param_noise_cycle"):
+        raise NotImplementedError("rl_train_vec_smartstart: a base agent with param_noise needs param_noise_cycle "
+                                  "(the one-launch adapt and re-perturb)")
     import torch
     from .replay_buffer import DeviceReplayBuffer
     from .vec_env import EpisodeRing, TransitionChunk
@@ -519,6 +559,12 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
         l = agent.train_from(replay, train_iters)
         if overlap_selection:
             learned.record(main)
+        if getattr(agent, "param_noise", None) is not None:      # the next chunk's acting copy, with the adapted stddev
+            if len(replay) >= agent.batch_size:
+                rows = replay.sample_indices(1, agent.batch_size)[0].long()
+                agent.param_noise_cycle(replay.s.index_select(0, rows))
+            else:
+                agent.perturb_policy()
         if l is not None:
             losses.append(l)
         if on_chunk is not None:

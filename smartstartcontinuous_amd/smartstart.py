@@ -353,6 +353,14 @@ class VecSmartStart:
             ss.d_mode_log, ss.mode_log_stride = self.mode_log.data_ptr(), e.n
         return ss
 
+    def acting_desc(self):
+        """The actor descriptor the per-step launch reads: over ``perturbed_actor_flat`` for a base agent with parameter
+        noise (pi, ddpg_editted.py:256-259) -- the same pointer slots for the life of the agent, so a captured step graph
+        stays valid while every perturbation changes the array's contents -- else the agent's own.  The selection
+        (``state_value_device``) always evaluates the PLAIN actor: get_q_value is not an acting path."""
+        a = self.agent
+        return a._perturbed_desc if getattr(a, "param_noise", None) is not None else a._desc
+
     def fused_step(self, chunk, ring):
         """Enqueue ONE step for every env (five launches); step index and log row are device counters."""
         from . import navigator as nav
@@ -361,11 +369,12 @@ class VecSmartStart:
         with torch.cuda.device(env.device):
             _ffi.check(lib.ssc_nav_compact(env.n, _ffi.ptr(self.mode), _ffi.ptr(self.live_list), _ffi.ptr(self.n_live), _stream()))
             rms = getattr(self.agent, "obs_rms", None)
+            desc = self.acting_desc()
             if rms is None:
-                _ffi.check(lib.ssc_actor_forward(ctypes.byref(self.agent._desc), env.n, _ffi.ptr(fb["plan"]),
+                _ffi.check(lib.ssc_actor_forward(ctypes.byref(desc), env.n, _ffi.ptr(fb["plan"]),
                                                  _ffi.ptr(self.actor_out), _stream()))
             else:   # normalize_observations: the kernel reads the block at launch (valid inside the captured graph)
-                _ffi.check(lib.ssc_actor_forward_rms(ctypes.byref(self.agent._desc), env.n, _ffi.ptr(fb["plan"]),
+                _ffi.check(lib.ssc_actor_forward_rms(ctypes.byref(desc), env.n, _ffi.ptr(fb["plan"]),
                                                      _ffi.ptr(self.actor_out), _stream(), _ffi.ptr(rms.block)))
         sp = nav.mpc_sampling(b.N, b.low, b.high, b.seed, b.problem_id0, 0, t_base=fb["t"], active=self.mode,
                               live_list=self.live_list, n_live=self.n_live)
@@ -415,7 +424,7 @@ class VecSmartStart:
                 self.fused_step(out, ring)
             env.t += K
             return out
-        key = (K, out.obs.data_ptr(), None if ring is None else ring.cursor.data_ptr(), self.agent.actor_flat.data_ptr(),
+        key = (K, out.obs.data_ptr(), None if ring is None else ring.cursor.data_ptr(), self.acting_desc().W1,
                tuple(w.data_ptr() for w in self.model.W), None if self.model._image is None else self.model._image.data_ptr(),
                self.log_modes)
         if key not in self._graphs:
