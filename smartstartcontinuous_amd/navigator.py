@@ -488,9 +488,11 @@ def mpc_sample_actions(P, N, H, low, high, seed, problem_id0=0, t=0, device="cud
     return A
 
 
-def mpc_score(problems, S):
+def mpc_score(problems, S, out=None):
     """``generate_scores_add_delta`` + argmax (NND_MB_agent.py:566-628) for P problems.
-    S: [H+1, P*N, d].  Returns (scores [P, N], best_idx [P] int32, best_score [P])."""
+    S: [H+1, P*N, d].  Returns (scores [P, N], best_idx [P] int32, best_score [P]).
+    ``out``: dict of preallocated scores / best / best_score / ws tensors (problems that the set's ``active`` mask or live
+    list leaves out keep what these held)."""
     S = S.contiguous()
     H1, M, d = S.shape
     P = problems.P
@@ -498,15 +500,16 @@ def mpc_score(problems, S):
     if N * P != M or d != problems.d:
         raise ValueError("S has the wrong shape for this problem set")
     lib = _ffi.lib()
-    scores = torch.empty(M, dtype=torch.float32, device=S.device)
-    best_idx = torch.empty(P, dtype=torch.int32, device=S.device)
-    best_score = torch.empty(P, dtype=torch.float32, device=S.device)
+    o = out if out is not None else {}
+    scores = o.get("scores") if o.get("scores") is not None else torch.empty(M, dtype=torch.float32, device=S.device)
+    best_idx = o.get("best") if o.get("best") is not None else torch.empty(P, dtype=torch.int32, device=S.device)
+    best_score = o.get("best_score") if o.get("best_score") is not None else torch.empty(P, dtype=torch.float32, device=S.device)
     st = problems.as_struct(N, H1 - 1)
     with torch.cuda.device(S.device):
         nbytes = lib.ssc_mpc_score_workspace_bytes(P, N, H1 - 1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=S.device)
+        ws = o.get("ws") if o.get("ws") is not None else torch.empty(nbytes, dtype=torch.uint8, device=S.device)
         _ffi.check(lib.ssc_mpc_score(ctypes.byref(st), _ffi.ptr(S), _ffi.ptr(scores), _ffi.ptr(best_idx),
-                                     _ffi.ptr(best_score), _ffi.ptr(ws), nbytes, _stream()))
+                                     _ffi.ptr(best_score), _ffi.ptr(ws), ws.numel(), _stream()))
     return scores.view(P, N), best_idx, best_score
 
 
