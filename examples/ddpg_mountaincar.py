@@ -44,24 +44,44 @@ def main():
                     help="DDPG normalize_observations: networks see running-statistics-normalised observations")
     ap.add_argument("--param-noise", type=float, default=None, metavar="STDDEV",
                     help="adaptive parameter-space noise with this initial (and desired action) stddev, on top of the OU noise")
+    ap.add_argument("--stats-every", type=int, default=None, metavar="K",
+                    help="the reference's training diagnostics (get_stats): vec: logged on the device every K chunks and printed "
+                         "after the run; single: printed every K episodes")
     args = ap.parse_args()
     np.random.seed(args.seed)
     if args.mode == "single":
         env = ssc.Continuous_MountainCarEnv_Editted.make_timed_env(args.power_scalar, max_episode_steps=1000,
                                                                    seed=args.seed)
         agent = make_agent(env, args.seed, args.normalize_observations, args.param_noise)
-        summary = ssc.rlTrain(agent, env, print_results=True, print_steps=False, num_episodes=args.episodes,
-                              max_steps=1000)
+        if args.stats_every is None:
+            summary = ssc.rlTrain(agent, env, print_results=True, print_steps=False, num_episodes=args.episodes,
+                                  max_steps=1000)
+        else:                                  # one rlTrain call per episode, the diagnostics between them
+            summary = None
+            for episode in range(args.episodes):
+                one = ssc.rlTrain(agent, env, print_results=True, print_steps=False, num_episodes=1, max_steps=1000)
+                if summary is None:
+                    summary = one
+                else:
+                    summary.append_record(*one.episodes[0])
+                if (episode + 1) % args.stats_every == 0 and len(agent.replay_buffer) >= agent.batch_size:
+                    print("  stats:", ", ".join("%s %.6g" % kv for kv in agent.get_stats().items()))
     else:
         env = ssc.VecEnv("MountainCarContinuousActionX%s-v0" % args.power_scalar, args.envs, seed=args.seed)
         agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations,
                            args.param_noise)
         summary, losses, replay = ssc.rl_train_vec_ddpg(env, agent, num_chunks=args.chunks, chunk_steps=250,
-                                                        replay_capacity=1 << 20, train_iters=50, overlap=args.overlap)
+                                                        replay_capacity=1 << 20, train_iters=50, overlap=args.overlap,
+                                                        stats_every=args.stats_every)
         goals = sum(1 for steps, ret in summary.episodes if ret > 0)
         print("%d env-steps, %d finished episodes (%d reached the goal), %d records in the replay ring, "
               "last critic/actor loss %.4g / %.4g" % (args.envs * args.chunks * 250, len(summary), goals, len(replay),
                                                       *losses[-1][-1].tolist()))
+        if args.stats_every is not None:
+            shown = [k for k, v in summary.agent_stats.items() if not np.all(np.isnan(v))]
+            print("chunk  " + "  ".join(shown))
+            for row, chunk in enumerate(summary.agent_stats_chunks):
+                print("%5d  " % chunk + "  ".join("%*.6g" % (len(k), summary.agent_stats[k][row]) for k in shown))
     if agent.param_noise is not None:
         print("parameter noise:", agent.param_noise.get_stats())
     if args.save_dir:

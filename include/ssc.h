@@ -675,6 +675,35 @@ int ssc_param_noise_cycle(const ssc_actor_desc *actor, int64_t m, const float *d
                           float coefficient, float *d_stddev, float *d_distance, float *d_dst, ssc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Training diagnostics (ddpg_editted.py:219-253 setup_stats, 341-358 get_stats; printed per epoch by
+ * training_editted.py:144)
+ * -------------------------------------------------------------------------------------
+ * ssc_ddpg_stats: the stats_ops of DDPG_editted on a fixed sample of m transitions (obs [m][obs_dim], act [m][act_dim],
+ * 1 <= m <= 4096) into d_out[SSC_DDPG_N_STATS] (f64, device), in the reference's stats_names order:
+ *   0 obs_rms_mean   1 obs_rms_std             mean over the dimensions of the fp32 mean / std the networks use (d_rms)
+ *   2 reference_Q_mean   3 reference_Q_std                           Q(obs, act)
+ *   4 reference_actor_Q_mean   5 reference_actor_Q_std               Q(obs, actor(obs))
+ *   6 reference_action_mean   7 reference_action_std                 actor(obs), all m * act_dim elements
+ *   8 reference_perturbed_action_mean   9 reference_perturbed_action_std   perturbed(obs), likewise
+ *   10 param_noise_stddev                                            *d_param_noise_stddev, read when the kernel runs
+ * mean and population std sqrt(mean((x - mean)^2)) (baselines' reduce_std).  Slots that do not apply are NaN: 0-1 with
+ * d_rms == NULL, 8-9 with perturbed == NULL, 10 with d_param_noise_stddev == NULL.  Observations enter the networks as in
+ * ssc_actor_forward_rms / ssc_critic_forward_rms (each descriptor's own obs_clip; normalised when d_rms is given); all
+ * forward passes run in fp32 with every unit summed in index order, whatever `precision` says, with or without LayerNorm.
+ * The batch is tiled over workgroups of 16 rows; each leaves (count, mean, M2) per statistic in the workspace -- M2 from a
+ * second sweep around the tile mean, never sum(x^2) / n - mean^2 -- and a second small launch merges them in workgroup
+ * order with Chan's formula, all in f64, no atomics: the same bits run to run.  No host read; stream-ordered.
+ * SSC_EINVAL for NULL descriptors / sample / output, m out of range, actor / critic / perturbed shapes that disagree, or a
+ * workspace below ssc_ddpg_stats_workspace_bytes(m) (0 for m out of range) -- all checked before any HIP call;
+ * SSC_EUNSUPPORTED, with the byte count in ssc_last_error(), when a 16-row tile's activations exceed the 160 KB of LDS
+ * (roughly max(actor h1, critic h1) + max(actor h2, critic h2) > 2500 units). */
+#define SSC_DDPG_N_STATS 11
+size_t ssc_ddpg_stats_workspace_bytes(int64_t m);
+int ssc_ddpg_stats(const ssc_actor_desc *actor, const ssc_critic_desc *critic, const ssc_actor_desc *perturbed, int64_t m,
+                   const float *d_obs, const float *d_act, const double *d_rms, const float *d_param_noise_stddev,
+                   double *d_out, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Dynamics-model training step
  * ------------------------------------------------------------------------------------- */
 

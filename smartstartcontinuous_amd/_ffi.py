@@ -20,6 +20,7 @@ SSC_ENV_MOUNTAINCAR, SSC_ENV_PENDULUM = 0, 1
 SSC_POLICY_RANDOM, SSC_POLICY_ACTOR = 0, 1
 SSC_PREC_F32, SSC_PREC_BF16_MFMA, SSC_PREC_BF16_MFMA_PREPARED = 0, 1, 2
 SSC_MAX_OBS, SSC_MAX_LAYERS, SSC_MAX_STATE, SSC_MAX_ACT = 3, 4, 8, 4
+SSC_DDPG_N_STATS = 11
 
 
 class SscError(RuntimeError):
@@ -204,6 +205,10 @@ _SIGNATURES = {
     "ssc_param_noise_cycle": (c_int, [POINTER(ActorDesc), c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                       c_int64, c_int64, c_uint64, c_uint64, c_uint64, c_float, c_float, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    # training diagnostics (get_stats): one f64 block per call
+    "ssc_ddpg_stats_workspace_bytes": (c_size_t, [c_int64]),
+    "ssc_ddpg_stats": (c_int, [POINTER(ActorDesc), POINTER(CriticDesc), POINTER(ActorDesc), c_int64, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ssc_dataset_scan_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_dataset_scan": (c_int, [POINTER(TransitionLog), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),

@@ -526,6 +526,94 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         if self.training_enabled:
             self.train()
 
+    # ---- training diagnostics (ddpg_editted.py:219-253 setup_stats, 341-358 get_stats) ---------------------------------
+    # the reference's stats_names with normalize_observations and parameter noise on; ret_rms_* (normalize_returns) is
+    # not on the accelerated path
+    STATS_NAMES = ("obs_rms_mean", "obs_rms_std", "reference_Q_mean", "reference_Q_std", "reference_actor_Q_mean",
+                   "reference_actor_Q_std", "reference_action_mean", "reference_action_std",
+                   "reference_perturbed_action_mean", "reference_perturbed_action_std", "param_noise_stddev")
+    _STATS_KEY = 0x5354415453          # the stats sample's own Philox key / host generator seed ("STATS")
+
+    def set_stats_sample(self, obs, act):
+        """Fix the sample the diagnostics are evaluated on (ddpg_editted.py:345-349 draws it once): obs [m, obs_dim] and
+        act [m, act_dim], host arrays or device tensors, 1 <= m <= 4096.  Kept as device tensors (copies)."""
+        o = torch.as_tensor(obs, dtype=torch.float32).to(self.device).reshape(-1, self.obs_dim).contiguous().clone()
+        a = torch.as_tensor(act, dtype=torch.float32).to(self.device).reshape(o.shape[0], -1).contiguous().clone()
+        if a.shape[1] != self.act_dim or not 1 <= o.shape[0] <= 4096:
+            raise ValueError(f"stats sample: need 1..4096 rows of ({self.obs_dim}, {self.act_dim}) columns, got "
+                             f"{tuple(o.shape)} / {tuple(a.shape)}")
+        self.stats_sample = (o, a)
+
+    def _draw_stats_sample(self, replay):
+        """``batch_size`` records of ``replay`` (a host ReplayBuffer or a DeviceReplayBuffer), drawn from a stream of their
+        own: neither the ring's batch counter nor the host ``random`` state moves, so the learner's next batch is the one
+        it would have been."""
+        B = self.batch_size
+        if len(replay) < B:
+            raise ValueError(f"get_stats: the replay buffer holds {len(replay)} records, the sample needs {B}")
+        if hasattr(replay, "sample_indices"):                    # DeviceReplayBuffer: ssc_replay_sample under another key
+            idx = torch.empty((1, B), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                _ffi.check(self.lib.ssc_replay_sample((replay.seed ^ self._STATS_KEY) & (2 ** 64 - 1), 0, len(replay), 1, B,
+                                                      _ffi.ptr(idx), _stream()))
+            rows = idx[0].long()
+            self.set_stats_sample(replay.s.index_select(0, rows), replay.a.index_select(0, rows))
+        else:                                                    # replay_buffer.py:79-91 with a generator of its own
+            import random
+            rows = np.asarray(random.Random(self._STATS_KEY).sample(range(len(replay)), B), dtype=np.int64)
+            s, a = replay._gather(rows)[:2]
+            self.set_stats_sample(np.asarray(s, np.float32).reshape(B, -1), np.asarray(a, np.float32).reshape(B, -1))
+
+    def get_stats_device(self, replay=None, out=None, perturbed=None):
+        """The stats_ops of DDPG_editted in one enqueue (``ssc_ddpg_stats``): a float64 DEVICE tensor [SSC_DDPG_N_STATS] in
+        ``STATS_NAMES`` order, NaN where a slot does not apply (no observation statistics / no parameter noise).  No host
+        read; stream-ordered.  The first call without a fixed sample draws ``batch_size`` records from ``replay`` (default:
+        the agent's own buffer) and keeps them.  ``out``: a contiguous float64 device tensor of that size to write into.
+        ``perturbed``: the flat perturbed copy to measure (default ``perturbed_actor_flat``)."""
+        if getattr(self, "stats_sample", None) is None:
+            self._draw_stats_sample(self.replay_buffer if replay is None else replay)
+        o, a = self.stats_sample
+        n = _ffi.SSC_DDPG_N_STATS
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != n or not out.is_contiguous() or out.device != o.device:
+            raise ValueError(f"out must be a contiguous float64 tensor of {n} elements on {o.device}")
+        pdesc = sd = None
+        if self.param_noise is not None:
+            sd = self.d_param_noise_stddev
+            pdesc = self._perturbed_desc
+            if perturbed is not None and perturbed.data_ptr() != self.perturbed_actor_flat.data_ptr():
+                if perturbed.dtype != torch.float32 or perturbed.numel() != self.actor_flat.numel() or not perturbed.is_contiguous():
+                    raise ValueError("perturbed must be a contiguous fp32 array of the size of actor_flat")
+                cache = self.__dict__.setdefault("_stats_pdesc", {})      # (the overlapped loop alternates two copies)
+                if perturbed.data_ptr() not in cache:
+                    cache[perturbed.data_ptr()] = (perturbed, self._views_desc(perturbed)[1])
+                pdesc = cache[perturbed.data_ptr()][1]
+        with torch.cuda.device(self.device):
+            need = int(self.lib.ssc_ddpg_stats_workspace_bytes(o.shape[0]))
+            ws = getattr(self, "_stats_ws", None)
+            if ws is None or ws.numel() < need:
+                ws = self._stats_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _ffi.check(self.lib.ssc_ddpg_stats(ctypes.byref(self._desc), ctypes.byref(self._critic_desc),
+                                               None if pdesc is None else ctypes.byref(pdesc), o.shape[0], _ffi.ptr(o),
+                                               _ffi.ptr(a), _ffi.ptr(self._rms_block()), _ffi.ptr(sd), _ffi.ptr(out),
+                                               _ffi.ptr(ws), ws.numel(), _stream()))
+        return out
+
+    @classmethod
+    def stats_dict(cls, values):
+        """name -> Python float in ``STATS_NAMES`` order, without the slots that do not apply (NaN)."""
+        vals = [float(v) for v in values]
+        return {k: v for k, v in zip(cls.STATS_NAMES, vals) if not np.isnan(v)}
+
+    def get_stats(self, replay=None):
+        """DDPG_editted.get_stats (ddpg_editted.py:341-358): dict name -> float in the reference's order; with parameter
+        noise merged with ``param_noise.get_stats()`` (:355-356).  Reads the device block (a device -> host copy)."""
+        stats = self.stats_dict(self.get_stats_device(replay).cpu().tolist())
+        if self.param_noise is not None:
+            stats = {**stats, **self.param_noise.get_stats()}
+        return stats
+
     def get_param_dict(self):
         return self.param_dict
 

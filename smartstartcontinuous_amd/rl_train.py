@@ -310,7 +310,7 @@ def update_obs_rms(agent, chunk, last_steps=None):
 
 def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
                       replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
-                      drain_every=None, on_chunk=None):
+                      drain_every=None, on_chunk=None, stats_every=None):
     """Actor-learner loop entirely in HBM: every chunk is a fused rollout of ``chunk_steps`` steps of all
     ``env.n`` envs under the agent's current actor (+ OU noise), appended to a device replay ring, followed
     by ``train_iters`` DDPG iterations (default ``agent.num_train_iterations``) on batches drawn from it.
@@ -350,8 +350,20 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     stream, and the host still runs ahead).  With normalize_observations the cycle reads the live statistics block on the
     learner stream and the rollout the snapshot.  As in the synchronous loop, only the adaption is skipped while the ring
     holds fewer than ``batch_size`` records.  When the loop ends ``agent.perturbed_actor_flat`` holds the last copy.
+
+    ``stats_every=k``: the training diagnostics of the reference (``agent.get_stats_device``, training_editted.py:144)
+    behind the learner iterations -- and the adapt / re-perturb, so the perturbed actor measured is the one the next chunk
+    acts with -- of every chunk i with (i + 1) % k == 0, written into row i // k of a DEVICE log
+    [ceil(num_chunks / k), SSC_DDPG_N_STATS] on the learner's stream; no host read.  The sample is fixed at the first such
+    chunk whose ring holds ``batch_size`` records (drawn under a key of its own: the learner's batches do not move; a sample
+    the agent already has is kept); rows before that, and a last row whose chunk the loop never reaches, stay NaN.  The log
+    is copied to the host once, when the loop ends: ``summary.agent_stats`` (name -> float64 array, one entry per row) and
+    ``summary.agent_stats_chunks`` (the chunk number of each row).  Everything else the loop computes is bit-identical to
+    the run without it.
     Returns (Summary, losses per chunk, replay)."""
     param_noise = getattr(agent, "param_noise", None) is not None
+    if stats_every is not None and (int(stats_every) != stats_every or stats_every < 1):
+        raise ValueError("stats_every must be None or a positive integer")
     if param_noise and overlap and not hasattr(agent, "param_noise_cycle"):
         raise NotImplementedError("rl_train_vec_ddpg: overlap=True with param_noise needs an agent with param_noise_cycle "
                                   "(the one-launch adapt and re-perturb)")
@@ -379,11 +391,30 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         dropped += d
         summary.extend_records(lens, rets)
 
+    stats_log = None
+    if stats_every is not None:
+        from ._ffi import SSC_DDPG_N_STATS
+        stats_every = int(stats_every)
+        stats_log = torch.full((-(-num_chunks // stats_every), SSC_DDPG_N_STATS), float("nan"), dtype=torch.float64,
+                               device=env.device)
+
+    def log_stats(i, perturbed=None):
+        """the diagnostics of chunk i, enqueued on the current (learner) stream"""
+        if stats_log is None or (i + 1) % stats_every != 0:
+            return
+        if getattr(agent, "stats_sample", None) is None and len(replay) < agent.batch_size:
+            return                                               # no sample yet: the row stays NaN
+        agent.get_stats_device(replay, out=stats_log[i // stats_every], perturbed=perturbed)
+
     def finish():
         drain()
         summary.dropped_episode_records = dropped
         _g, (eps,) = schedule.read()
         agent.decaying_ou_action_noise.epsilon = eps
+        if stats_log is not None:
+            host = stats_log.cpu().numpy()
+            summary.agent_stats = {name: host[:, j].copy() for j, name in enumerate(agent.STATS_NAMES)}
+            summary.agent_stats_chunks = [(r + 1) * stats_every - 1 for r in range(host.shape[0])]
 
     if overlap:
         from .vec_env import ActorPolicy
@@ -451,6 +482,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
                 else:
                     agent.perturbed_generation = agent._perturb(acting[b ^ 1])
                 snap_ready.record(cur)
+            log_stats(i, acting[b ^ 1] if param_noise else None)   # behind the event: rollout i + 1 does not wait for it
             if on_chunk is not None:
                 on_chunk(i, chunks[b], env)
             extra = []
@@ -484,6 +516,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
                 rows = replay.sample_indices(1, agent.batch_size)[0].long()
                 agent.adapt_param_noise(replay.s.index_select(0, rows))
             agent.perturb_policy()                               # the next chunk's actor, with the adapted stddev
+        log_stats(i)
         if on_chunk is not None:
             on_chunk(i, out, env)
         if (i + 1) % drain_every == 0:
