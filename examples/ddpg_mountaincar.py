@@ -47,6 +47,11 @@ def main():
     ap.add_argument("--stats-every", type=int, default=None, metavar="K",
                     help="the reference's training diagnostics (get_stats): vec: logged on the device every K chunks and printed "
                          "after the run; single: printed every K episodes")
+    ap.add_argument("--eval-every", type=int, default=None, metavar="K",
+                    help="vec: the reference's evaluation block (eval/return, eval/Q: the actor without noise on envs of its own) "
+                         "every K chunks, logged on the device and printed after the run")
+    ap.add_argument("--eval-envs", type=int, default=128, metavar="E", help="vec: evaluation envs")
+    ap.add_argument("--eval-steps", type=int, default=None, metavar="S", help="vec: steps per evaluation (default: the time limit)")
     args = ap.parse_args()
     np.random.seed(args.seed)
     if args.mode == "single":
@@ -70,9 +75,13 @@ def main():
         env = ssc.VecEnv("MountainCarContinuousActionX%s-v0" % args.power_scalar, args.envs, seed=args.seed)
         agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations,
                            args.param_noise)
+        eval_kw = {}
+        if args.eval_every is not None:        # envs of their own: another seed, ids behind the training envs'
+            eval_kw = dict(eval_env=ssc.VecEnv(env.spec.id, args.eval_envs, seed=args.seed + 1, env_id0=args.envs),
+                           eval_every=args.eval_every, eval_steps=args.eval_steps)
         summary, losses, replay = ssc.rl_train_vec_ddpg(env, agent, num_chunks=args.chunks, chunk_steps=250,
                                                         replay_capacity=1 << 20, train_iters=50, overlap=args.overlap,
-                                                        stats_every=args.stats_every)
+                                                        stats_every=args.stats_every, **eval_kw)
         goals = sum(1 for steps, ret in summary.episodes if ret > 0)
         print("%d env-steps, %d finished episodes (%d reached the goal), %d records in the replay ring, "
               "last critic/actor loss %.4g / %.4g" % (args.envs * args.chunks * 250, len(summary), goals, len(replay),
@@ -82,6 +91,11 @@ def main():
             print("chunk  " + "  ".join(shown))
             for row, chunk in enumerate(summary.agent_stats_chunks):
                 print("%5d  " % chunk + "  ".join("%*.6g" % (len(k), summary.agent_stats[k][row]) for k in shown))
+        if args.eval_every is not None:
+            names = list(summary.eval_stats)
+            print("chunk  " + "  ".join(names))
+            for row, chunk in enumerate(summary.eval_chunks):
+                print("%5d  " % chunk + "  ".join("%*.6g" % (len(k), summary.eval_stats[k][row]) for k in names))
     if agent.param_noise is not None:
         print("parameter noise:", agent.param_noise.get_stats())
     if args.save_dir:

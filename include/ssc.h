@@ -704,6 +704,47 @@ int ssc_ddpg_stats(const ssc_actor_desc *actor, const ssc_critic_desc *critic, c
                    double *d_out, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Evaluation rollouts (training_editted.py:122-138, reported :160-164 as eval/return, eval/Q, eval/episodes)
+ * -------------------------------------------------------------------------------------
+ * ssc_ddpg_eval_rollout: K steps of the reference's evaluation loop for n independent eval envs in ONE fused launch (plus
+ * a small merge launch).  Per step, with o the observation of the env's state:
+ *   x = clip(o), or clip((o - mean) / std) when d_rms is given -- formed as ssc_actor_forward_rms / ssc_critic_forward_rms
+ *       form it, each descriptor's own obs_clip;
+ *   a_raw = actor(x);  Q = critic(x, a_raw)          critic_with_actor_tf (ddpg_editted.py:130-131, 262): Q of the RAW output
+ *   executed action = scale(scale(clip(a_raw, -1, 1)))   DDPG_Baselines_agent.get_action with the noise off (act_low / act_high)
+ *   env.step, TimeLimit, the running episode return in fp32 in step order, auto-reset with
+ *   Philox(seed; env_id, step0 + k, TAG_RESET)      as ssc_rollout: chunks compose, the id space shards
+ * No noise of any kind: state->ou_x is neither read nor written and may be NULL.  s0, s1, steps and ep_ret are written
+ * back.  zero_returns != 0 starts every env's running return at 0 for this launch while the episode itself goes on (the
+ * reference zeroes eval_episode_reward and keeps eval_obs, training_editted.py:125); 0 carries state->ep_ret.
+ * All forward arithmetic is fp32 with every unit summed in index order by fused multiply-adds -- the arithmetic of
+ * ssc_ddpg_stats (critic hidden tanh: tanhf, actor: the fast one); `precision` is ignored, LayerNorm and last_layer_tanh
+ * are honoured.  act_dim is 1.
+ * d_out[SSC_DDPG_N_EVAL] (f64, device), every slot written by every call:
+ *   0 eval/episodes            episodes finished in this launch
+ *   1 eval/return   2 its population std    over those episodes; NaN if none (np.mean([]))
+ *   3 eval/Q        4 its population std    over all n * K steps
+ *   5 env-steps = n * K        6 goal terminations        7 mean length of the finished episodes; NaN if none
+ * log (may be NULL): the usual [K][n] transition columns, with the EXECUTED action.  d_q (may be NULL): Q as [K][n], the
+ * reference's eval_qs.
+ * Reduction: every env keeps (count, mean, M2) of its Q stream, of its finished-episode returns and of their lengths in
+ * f64 registers (Welford); a workgroup of 16 envs merges them in env order with Chan's formula into the workspace, and a
+ * second small launch merges the workgroups in workgroup order.  No atomics; the grid depends on n alone: the same bits
+ * run to run.  The weights are staged in LDS once per launch when both networks and a tile's activations fit its 160 KB
+ * (64-32, 128-64), read from global memory otherwise (200-100); the summation order, and the bits, are the same.
+ * SSC_EINVAL for NULL params / descriptors / state / output / workspace, n < 1 or K < 1, actor / critic / env obs_dim that
+ * disagree, critic->act_dim != actor->act_dim, or a workspace below ssc_ddpg_eval_workspace_bytes(n) -- all checked
+ * before any HIP call; SSC_EUNSUPPORTED for act_dim != 1, and, with the byte count in ssc_last_error(), when a tile's
+ * activations alone exceed LDS. */
+#define SSC_DDPG_N_EVAL 8
+size_t ssc_ddpg_eval_workspace_bytes(int64_t n);
+int ssc_ddpg_eval_rollout(const ssc_env_params *p, const ssc_actor_desc *actor, const ssc_critic_desc *critic,
+                          float act_low, float act_high, int64_t n, int32_t K, const ssc_rollout_state *state,
+                          const double *d_rms, const ssc_transition_log *log, float *d_q, int32_t zero_returns,
+                          double *d_out, void *d_workspace, size_t workspace_bytes,
+                          uint64_t seed, uint64_t env_id0, uint64_t step0, ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Dynamics-model training step
  * ------------------------------------------------------------------------------------- */
 

@@ -21,6 +21,7 @@ SSC_POLICY_RANDOM, SSC_POLICY_ACTOR = 0, 1
 SSC_PREC_F32, SSC_PREC_BF16_MFMA, SSC_PREC_BF16_MFMA_PREPARED = 0, 1, 2
 SSC_MAX_OBS, SSC_MAX_LAYERS, SSC_MAX_STATE, SSC_MAX_ACT = 3, 4, 8, 4
 SSC_DDPG_N_STATS = 11
+SSC_DDPG_N_EVAL = 8
 
 
 class SscError(RuntimeError):
@@ -209,6 +210,11 @@ _SIGNATURES = {
     "ssc_ddpg_stats_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_ddpg_stats": (c_int, [POINTER(ActorDesc), POINTER(CriticDesc), POINTER(ActorDesc), c_int64, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # evaluation rollouts (eval/return, eval/Q): one fused launch, one f64 block per call
+    "ssc_ddpg_eval_workspace_bytes": (c_size_t, [c_int64]),
+    "ssc_ddpg_eval_rollout": (c_int, [POINTER(EnvParams), POINTER(ActorDesc), POINTER(CriticDesc), c_float, c_float, c_int64, c_int32,
+                                      POINTER(RolloutState), c_void_p, POINTER(TransitionLog), c_void_p, c_int32, c_void_p, c_void_p,
+                                      c_size_t, c_uint64, c_uint64, c_uint64, c_void_p]),
     "ssc_dataset_scan_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_dataset_scan": (c_int, [POINTER(TransitionLog), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),

@@ -614,6 +614,72 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             stats = {**stats, **self.param_noise.get_stats()}
         return stats
 
+    # ---- evaluation rollouts (training_editted.py:122-138; reported :160-164) -----------------------------------------
+    EVAL_NAMES = ("eval/episodes", "eval/return", "eval/return_std", "eval/Q", "eval/Q_std", "eval/steps", "eval/goals",
+                  "eval/episode_length")
+    _EVAL_COUNTS = ("eval/episodes", "eval/steps", "eval/goals")
+
+    def evaluate_device(self, eval_env, nb_eval_steps, out=None, log=None, q=None, carry_returns=False):
+        """``nb_eval_steps`` steps of the reference's evaluation loop on every env of ``eval_env`` (a VecEnv of its own, never
+        the training env) in one fused launch (``ssc_ddpg_eval_rollout``): the PLAIN actor without noise of any kind -- also
+        on a parameter-noise agent, ``pi(apply_noise=False)`` uses ``actor_tf`` -- Q of its raw output from the critic at
+        every step, the live observation statistics when the agent normalises.  Returns the float64 DEVICE tensor
+        [SSC_DDPG_N_EVAL] in ``EVAL_NAMES`` order (NaN return / length when no episode ended).  No host read; enqueued on
+        the current stream.  ``eval_env`` keeps its own state, seed, ``env_id0`` and step counter ``t`` (advanced by
+        ``nb_eval_steps``; reset first if it never was), so consecutive calls continue the same episodes.
+        ``carry_returns=False`` is the reference: every env's running return starts at 0 in each call while its episode goes
+        on (training_editted.py:125); True carries ``eval_env.ep_ret`` over.  ``out``: a contiguous float64 device tensor
+        of that size to write into; ``log``: a TransitionChunk [nb_eval_steps, n] that receives the transitions (the
+        executed action); ``q``: a contiguous fp32 [nb_eval_steps, n] tensor that receives Q (the reference's eval_qs)."""
+        K, n = int(nb_eval_steps), eval_env.n
+        if K < 1 or K != nb_eval_steps:
+            raise ValueError("nb_eval_steps must be a positive integer")
+        if eval_env.obs_dim != self.obs_dim:
+            raise ValueError(f"eval_env observes {eval_env.obs_dim} values, the agent's networks take {self.obs_dim}")
+        dev = eval_env.s0.device                         # (a tensor's device carries its index: cuda:0, not cuda)
+        if dev != self.actor_flat.device:
+            raise ValueError(f"eval_env lives on {dev}, the agent on {self.actor_flat.device}")
+        ne = _ffi.SSC_DDPG_N_EVAL
+        if out is None:
+            out = torch.empty(ne, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != ne or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous float64 tensor of {ne} elements on {dev}")
+        if log is not None and (log.K, log.N, log.obs_dim) != (K, n, eval_env.obs_dim):
+            raise ValueError("log chunk has the wrong shape")
+        if q is not None and (q.dtype != torch.float32 or tuple(q.shape) != (K, n) or not q.is_contiguous()
+                              or q.device != dev):
+            raise ValueError(f"q must be a contiguous fp32 [{K}, {n}] tensor on {dev}")
+        if eval_env._needs_reset:
+            eval_env.reset()
+        if log is not None:
+            log.step0, log.env_id0 = eval_env.t, eval_env.env_id0
+        st = _ffi.RolloutState(eval_env.s0.data_ptr(), eval_env.s1.data_ptr(), eval_env.steps.data_ptr(),
+                               eval_env.ep_ret.data_ptr(), None)
+        log_s = log.as_struct() if log is not None else None
+        with torch.cuda.device(self.device):
+            need = int(self.lib.ssc_ddpg_eval_workspace_bytes(n))
+            ws = getattr(self, "_eval_ws", None)
+            if ws is None or ws.numel() < need:
+                ws = self._eval_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _ffi.check(self.lib.ssc_ddpg_eval_rollout(
+                ctypes.byref(eval_env.params), ctypes.byref(self._desc), ctypes.byref(self._critic_desc),
+                float(eval_env.action_space.low[0]), float(eval_env.action_space.high[0]), n, K, ctypes.byref(st),
+                _ffi.ptr(self._rms_block()), ctypes.byref(log_s) if log_s is not None else None, _ffi.ptr(q),
+                0 if carry_returns else 1, _ffi.ptr(out), _ffi.ptr(ws), ws.numel(), eval_env._seed, eval_env.env_id0,
+                eval_env.t, _stream()))
+        eval_env.t += K
+        return out
+
+    @classmethod
+    def eval_dict(cls, values):
+        """name -> value in ``EVAL_NAMES`` order; the three counts as ints"""
+        return {k: (int(v) if k in cls._EVAL_COUNTS else float(v)) for k, v in zip(cls.EVAL_NAMES, values)}
+
+    def evaluate(self, eval_env, nb_eval_steps, **kw):
+        """:meth:`evaluate_device` as a dict by ``EVAL_NAMES`` (eval/episodes, eval/steps and eval/goals as ints).  Reads
+        the device block (a device -> host copy)."""
+        return self.eval_dict(self.evaluate_device(eval_env, nb_eval_steps, **kw).cpu().tolist())
+
     def get_param_dict(self):
         return self.param_dict
 

@@ -310,7 +310,7 @@ def update_obs_rms(agent, chunk, last_steps=None):
 
 def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
                       replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
-                      drain_every=None, on_chunk=None, stats_every=None):
+                      drain_every=None, on_chunk=None, stats_every=None, eval_env=None, eval_every=None, eval_steps=None):
     """Actor-learner loop entirely in HBM: every chunk is a fused rollout of ``chunk_steps`` steps of all
     ``env.n`` envs under the agent's current actor (+ OU noise), appended to a device replay ring, followed
     by ``train_iters`` DDPG iterations (default ``agent.num_train_iterations``) on batches drawn from it.
@@ -360,10 +360,36 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     is copied to the host once, when the loop ends: ``summary.agent_stats`` (name -> float64 array, one entry per row) and
     ``summary.agent_stats_chunks`` (the chunk number of each row).  Everything else the loop computes is bit-identical to
     the run without it.
+
+    ``eval_env`` + ``eval_every=k``: the evaluation block of the reference (training_editted.py:122-138, 160-164) --
+    ``agent.evaluate_device(eval_env, eval_steps)``: the plain actor without noise on a VecEnv of its own, eval/return,
+    eval/Q, eval/episodes -- behind the learner iterations (and the adapt / re-perturb) of every chunk i with
+    (i + 1) % k == 0, into row i // k of a DEVICE log [ceil(num_chunks / k), SSC_DDPG_N_EVAL] pre-filled with NaN, on the
+    learner's stream; in the overlapped loop behind the ``snap_ready`` record, so rollout i + 1 does not wait for it.
+    ``eval_steps`` defaults to ``eval_env.spec.max_episode_steps`` or 1000.  No host read; the log is copied out once, when
+    the loop ends: ``summary.eval_stats`` (name -> float64 array) and ``summary.eval_chunks``.  The eval envs keep
+    their episodes from one evaluation to the next.  Everything else the loop computes is bit-identical to the run without it.
     Returns (Summary, losses per chunk, replay)."""
     param_noise = getattr(agent, "param_noise", None) is not None
     if stats_every is not None and (int(stats_every) != stats_every or stats_every < 1):
         raise ValueError("stats_every must be None or a positive integer")
+    if (eval_env is None) != (eval_every is None):
+        raise ValueError("eval_env and eval_every come together")
+    if eval_env is not None:
+        if eval_env is env:
+            raise ValueError("eval_env must be an env of its own, not the training env")
+        for what in ("observation_space", "action_space"):
+            ea, eb = getattr(eval_env, what), getattr(env, what)
+            if tuple(ea.shape) != tuple(eb.shape) or not (np.array_equal(ea.low, eb.low) and np.array_equal(ea.high, eb.high)):
+                raise ValueError(f"eval_env's {what} differs from the training env's")
+        if eval_steps is None:
+            eval_steps = getattr(getattr(eval_env, "spec", None), "max_episode_steps", None) or 1000
+        for name, v in (("eval_every", eval_every), ("eval_steps", eval_steps)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be a positive integer")
+        eval_every, eval_steps = int(eval_every), int(eval_steps)
+    elif eval_steps is not None:
+        raise ValueError("eval_steps needs eval_env and eval_every")
     if param_noise and overlap and not hasattr(agent, "param_noise_cycle"):
         raise NotImplementedError("rl_train_vec_ddpg: overlap=True with param_noise needs an agent with param_noise_cycle "
                                   "(the one-launch adapt and re-perturb)")
@@ -406,6 +432,17 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             return                                               # no sample yet: the row stays NaN
         agent.get_stats_device(replay, out=stats_log[i // stats_every], perturbed=perturbed)
 
+    eval_log = None
+    if eval_env is not None:
+        from ._ffi import SSC_DDPG_N_EVAL
+        eval_log = torch.full((-(-num_chunks // eval_every), SSC_DDPG_N_EVAL), float("nan"), dtype=torch.float64,
+                              device=env.device)
+
+    def log_eval(i):
+        """the evaluation behind chunk i, enqueued on the current (learner) stream"""
+        if eval_log is not None and (i + 1) % eval_every == 0:
+            agent.evaluate_device(eval_env, eval_steps, out=eval_log[i // eval_every])
+
     def finish():
         drain()
         summary.dropped_episode_records = dropped
@@ -415,6 +452,10 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             host = stats_log.cpu().numpy()
             summary.agent_stats = {name: host[:, j].copy() for j, name in enumerate(agent.STATS_NAMES)}
             summary.agent_stats_chunks = [(r + 1) * stats_every - 1 for r in range(host.shape[0])]
+        if eval_log is not None:
+            host = eval_log.cpu().numpy()
+            summary.eval_stats = {name: host[:, j].copy() for j, name in enumerate(agent.EVAL_NAMES)}
+            summary.eval_chunks = [(r + 1) * eval_every - 1 for r in range(host.shape[0])]
 
     if overlap:
         from .vec_env import ActorPolicy
@@ -483,6 +524,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
                     agent.perturbed_generation = agent._perturb(acting[b ^ 1])
                 snap_ready.record(cur)
             log_stats(i, acting[b ^ 1] if param_noise else None)   # behind the event: rollout i + 1 does not wait for it
+            log_eval(i)                                  # likewise
             if on_chunk is not None:
                 on_chunk(i, chunks[b], env)
             extra = []
@@ -517,6 +559,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
                 agent.adapt_param_noise(replay.s.index_select(0, rows))
             agent.perturb_policy()                               # the next chunk's actor, with the adapted stddev
         log_stats(i)
+        log_eval(i)
         if on_chunk is not None:
             on_chunk(i, out, env)
         if (i + 1) % drain_every == 0:
