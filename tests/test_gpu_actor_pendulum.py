@@ -76,6 +76,11 @@ def test_actor_forward_generic_sizes(ssc):
     obs = rng.uniform(-1, 1, size=(130, 4)).astype(np.float32)
     got = _actor_forward_gpu(ssc, w, obs, ffi.SSC_PREC_F32, act_dim=3)
     assert got.shape == (130, 3) and np.max(np.abs(got - O.actor_forward(obs, **w))) <= TOL_ACT_F32
+    # the row kernel (m = 20) and the generic kernel (m = 100) on the paths the shapes above do not take: LayerNorm, a ReLU
+    # second layer, a statistics block, three actions, and 400-300 (> 64 KB of dynamic LDS) -- identical bits
+    from tests.test_gpu_net_forward import ROW_GENERIC_CASES, row_and_generic_agree
+    for case in ROW_GENERIC_CASES:
+        row_and_generic_agree(case)
 
 
 def test_mfma_layout_with_asymmetric_weights(ssc):
