@@ -20,13 +20,13 @@ import smartstartcontinuous_amd as ssc  # noqa: E402
 from smartstartcontinuous_amd.agents import DDPG_Baselines_agent  # noqa: E402
 
 
-def make_agent(env, seed, normalize_observations=False, param_noise=None):
+def make_agent(env, seed, normalize_observations=False, param_noise=None, popart=False):
     return DDPG_Baselines_agent(env, None, buffer_size=100000, batch_size=64, num_train_iterations=50,
                                 num_steps_before_train=200, ou_epsilon=1.0, ou_min_epsilon=0.01,
                                 ou_epsilon_decay_factor=.99, ou_mu=0.4, ou_sigma=0.6, ou_theta=.15, actor_lr=0.001,
                                 actor_h1=64, actor_h2=32, critic_lr=0.001, critic_h1=64, critic_h2=32,
                                 lastLayerTanh=True, normalize_observations=normalize_observations, seed=seed,
-                                param_noise_stddev=param_noise)
+                                param_noise_stddev=param_noise, normalize_returns=popart, enable_popart=popart)
 
 
 def main():
@@ -44,6 +44,9 @@ def main():
                     help="DDPG normalize_observations: networks see running-statistics-normalised observations")
     ap.add_argument("--param-noise", type=float, default=None, metavar="STDDEV",
                     help="adaptive parameter-space noise with this initial (and desired action) stddev, on top of the OU noise")
+    ap.add_argument("--popart", action="store_true",
+                    help="DDPG normalize_returns + enable_popart: the critic learns normalised returns, its output layer is "
+                         "rescaled with the running return statistics (Pop-Art)")
     ap.add_argument("--stats-every", type=int, default=None, metavar="K",
                     help="the reference's training diagnostics (get_stats): vec: logged on the device every K chunks and printed "
                          "after the run; single: printed every K episodes")
@@ -57,7 +60,7 @@ def main():
     if args.mode == "single":
         env = ssc.Continuous_MountainCarEnv_Editted.make_timed_env(args.power_scalar, max_episode_steps=1000,
                                                                    seed=args.seed)
-        agent = make_agent(env, args.seed, args.normalize_observations, args.param_noise)
+        agent = make_agent(env, args.seed, args.normalize_observations, args.param_noise, args.popart)
         if args.stats_every is None:
             summary = ssc.rlTrain(agent, env, print_results=True, print_steps=False, num_episodes=args.episodes,
                                   max_steps=1000)
@@ -74,7 +77,7 @@ def main():
     else:
         env = ssc.VecEnv("MountainCarContinuousActionX%s-v0" % args.power_scalar, args.envs, seed=args.seed)
         agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations,
-                           args.param_noise)
+                           args.param_noise, args.popart)
         eval_kw = {}
         if args.eval_every is not None:        # envs of their own: another seed, ids behind the training envs'
             eval_kw = dict(eval_env=ssc.VecEnv(env.spec.id, args.eval_envs, seed=args.seed + 1, env_id0=args.envs),
@@ -96,6 +99,8 @@ def main():
             print("chunk  " + "  ".join(names))
             for row, chunk in enumerate(summary.eval_chunks):
                 print("%5d  " % chunk + "  ".join("%*.6g" % (len(k), summary.eval_stats[k][row]) for k in names))
+    if agent.ret_rms is not None:
+        print("return statistics: mean %.6g, std %.6g" % tuple(float(x[0]) for x in agent.ret_rms.mean_std()))
     if agent.param_noise is not None:
         print("parameter noise:", agent.param_noise.get_stats())
     if args.save_dir:

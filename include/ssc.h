@@ -634,6 +634,35 @@ int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *ddpg, const ssc_replay_view *repl
                           const double *d_rms);
 
 /* ---------------------------------------------------------------------------------------
+ * normalize_returns + enable_popart (ddpg_editted.py:129-133, 140-149, 201-217, 291-301; arXiv 1602.07714)
+ * -------------------------------------------------------------------------------------
+ * ret_rms is the same RunningMeanStd as above with one column: d_ret_rms = [sum | sumsq | count] in f64, caller-
+ * initialised (0, 1e-2, 1e-2); mean and std in the fp32 arithmetic above.  The critic then outputs NORMALISED values and
+ * everything that reads Q denormalises: Q = q * std + mean (:129-131).  One iteration on a batch of B rows:
+ *   1. y_i = r_i + (1 - t_i) gamma (q'_i sigma_old + mu_old), q' from the target networks (:132-133, :292-296);
+ *   2. sum += sum (double) y_i, sumsq += sum (double) y_i^2, count += B (:297) -> mu_new, sigma_new;
+ *   3. critic AND target critic: W3 <- W3 sigma_old / sigma_new, b3 <- (b3 sigma_old + mu_old - mu_new) / sigma_new
+ *      (:209-217; Adam moments untouched), so that sigma q + mu is preserved;
+ *   4. the usual step with critic loss mean((q - (y - mu_new) / sigma_new)^2) (+ the l2 term over the rescaled W3) and
+ *      actor loss -mean(q(s, pi(s)) sigma_new + mu_new); d_losses holds these two (:181-192, :170).
+ * With normalize_returns alone ret_rms is never updated (the only call site, :291-297, is under popart): mean 0, std 1,
+ * the plain step -- call ssc_ddpg_train_ws[_rms].  This entry point is the conjunction.
+ *
+ * Every shape and batch 1..4096 runs the multi-workgroup kernels: four launches per iteration (target pass, renormalise,
+ * gradient pass, apply), no atomics, fixed summation order: the same bits run to run.  The statistics are read from
+ * device memory when a kernel starts (no host read, no synchronisation inside), so a captured graph stays valid.
+ * d_workspace: ssc_ddpg_train_popart_workspace_bytes(ddpg) bytes, laid out [the ssc_ddpg_train_workspace_bytes(ddpg) of the
+ * plain step | y [batch_size] fp32 | per-workgroup (sum y, sum y^2) [ceil(batch_size / 16)][2] f64 | (mu_old, sigma_old,
+ * mu_new, sigma_new) fp32 + padding, 256 bytes], each part rounded up to 256 bytes; after the call the last three hold
+ * the last iteration's values.  d_rms: the observation statistics or NULL.
+ * d_ret_rms == NULL behaves exactly like ssc_ddpg_train_ws_rms. */
+size_t ssc_ddpg_train_popart_workspace_bytes(const ssc_ddpg_desc *ddpg);
+int ssc_ddpg_train_ws_popart(const ssc_ddpg_desc *ddpg, const ssc_replay_view *replay, const int32_t *d_batch_idx,
+                             int32_t n_iters, float *d_losses, void *d_workspace, size_t workspace_bytes,
+                             ssc_stream_t stream, const double *d_rms /* obs statistics or NULL */,
+                             double *d_ret_rms /* [sum | sumsq | count], read and written */);
+
+/* ---------------------------------------------------------------------------------------
  * Adaptive parameter-space noise (ddpg_editted.py:47-60, 151-166, 255-259, 360-385)
  * -------------------------------------------------------------------------------------
  * A perturbed actor is a second flat parameter array [W1|b1|(beta1|gamma1)|W2|b2|(beta2|gamma2)|W3|b3] that the

@@ -199,6 +199,10 @@ _SIGNATURES = {
                                 c_void_p]),
     "ssc_ddpg_train_ws_rms": (c_int, [POINTER(DdpgDesc), POINTER(ReplayView), c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
                                       c_void_p, c_void_p]),
+    # normalize_returns + enable_popart: the step with the return statistics (trailing d_rms or NULL, then d_ret_rms)
+    "ssc_ddpg_train_popart_workspace_bytes": (c_size_t, [POINTER(DdpgDesc)]),
+    "ssc_ddpg_train_ws_popart": (c_int, [POINTER(DdpgDesc), POINTER(ReplayView), c_void_p, c_int32, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_void_p, c_void_p]),
     # adaptive parameter-space noise: perturb a flat actor, adapt the device stddev
     "ssc_param_noise_perturb": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint64,
                                         c_uint64, c_void_p]),

@@ -223,9 +223,14 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         args = dict(locals())
         self.param_dict = {k: (v if isinstance(v, (int, float, bool, str, type(None))) else "Not serializable")
                            for k, v in args.items() if k not in ("self", "__class__")}   # :135-137
-        if normalize_returns or enable_popart:
-            raise NotImplementedError("return normalisation / popart are not on the accelerated path "
-                                      "(every shipped run uses False)")
+        # ddpg_editted.py:140-149, 201-217, 291-301: Pop-Art is the conjunction (the only ret_rms.update call site is under
+        # both).  One switch without the other -- in the reference the plain step, with a ret_rms that never moves for
+        # normalize_returns alone -- stays refused.
+        if bool(normalize_returns) != bool(enable_popart):
+            raise NotImplementedError("return normalisation / popart: only the conjunction normalize_returns=True, "
+                                      "enable_popart=True (Pop-Art) is on the accelerated path; one switch alone is the "
+                                      "plain step in the reference, use False for both")
+        self.normalize_returns, self.enable_popart = bool(normalize_returns), bool(enable_popart)
         self.layer_norm = bool(layer_norm)      # models_editted.py:45-46, 50-51, 85-86, 91-92 (fp32 kernels)
         if self.layer_norm:
             precision = "f32"
@@ -257,6 +262,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             aw, cw = with_layer_norm(aw), with_layer_norm(cw)
         # normalize_observations (ddpg_editted.py:100-109): the running obs statistics every network input goes through
         self.obs_rms = ObsRms(obs_dim, self.device) if normalize_observations else None
+        # Pop-Art: the one-column return statistics; the critic outputs normalised values, every read-out of Q denormalises
+        # (q * std + mean, :129-131) and the learner updates them with every iteration
+        self.popart = self.normalize_returns and self.enable_popart
+        self.ret_rms = ObsRms(1, self.device) if self.popart else None
         # adaptive parameter-space noise (ddpg_editted.py:151-166; main_editted.py:48: desired = initial stddev)
         self.param_noise = None
         if param_noise_stddev is not None:
@@ -418,9 +427,17 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         r = self.obs_rms if obs_rms is None else obs_rms
         return r.block if isinstance(r, ObsRms) else r
 
-    def critic(self, obs, act, obs_rms=None):
+    def _denormalize(self, q):
+        """critic_tf = denormalize(normalized_critic_tf, ret_rms) (ddpg_editted.py:129-131): q * std + mean in fp32, a
+        multiply and an add on the current stream with the statistics read on the device"""
+        mean, std = self.ret_rms.mean_std_device()
+        return q * std + mean
+
+    def critic(self, obs, act, obs_rms=None, raw=False):
         """Critic_Editted forward: Q(obs [m, obs_dim], act [m, act_dim]) -> [m].  With observation statistics (the
-        agent's, or ``obs_rms``) the network sees clip((obs - mean) / std)."""
+        agent's, or ``obs_rms``) the network sees clip((obs - mean) / std).  With return statistics
+        (Pop-Art: ``normalize_returns`` with ``enable_popart``) the network's output is the normalised value and the result is denormalised;
+        ``raw=True`` returns the network's output itself."""
         o = torch.as_tensor(obs, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
         a = torch.as_tensor(act, dtype=torch.float32, device=self.device).reshape(o.shape[0], -1).contiguous()
         q = torch.empty(o.shape[0], dtype=torch.float32, device=self.device)
@@ -432,7 +449,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             else:
                 _ffi.check(self.lib.ssc_critic_forward_rms(ctypes.byref(self._critic_desc), o.shape[0], _ffi.ptr(o),
                                                            _ffi.ptr(a), _ffi.ptr(q), _stream(), _ffi.ptr(rms)))
-        return q
+        return q if raw or self.ret_rms is None else self._denormalize(q)
 
     def actor(self, obs, obs_rms=None):
         """Actor_Editted forward (models_editted.py:38-61) on a batch: obs [m, obs_dim] -> [m, act_dim] (normalised
@@ -487,18 +504,20 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                            ou_dt=n.dt, ou_epsilon=float(max(n.epsilon, 0)), obs_clip=float(self.observation_range[1]),
                            d_ou_epsilon=self.d_epsilon if device_epsilon else None, d_obs_rms=self._rms_block(obs_rms))
 
-    def get_state_value(self, state):
+    def get_state_value(self, state, raw=False):
         """:197-204 -> DDPG_editted.get_q_value (ddpg_editted.py:274-279): Q(s, pi(s)) without noise.
-        Returns [n, 1] for a batch, a length-1 array for a single state (like ``sess.run(...)[0]``)."""
+        Returns [n, 1] for a batch, a length-1 array for a single state (like ``sess.run(...)[0]``).  Denormalised with
+        return statistics, like :meth:`critic` (``raw=True``: the network's output)."""
         single = np.ndim(state) == 1 if not torch.is_tensor(state) else state.dim() == 1
-        q = self.state_value_device(state).reshape(-1, 1).double().cpu().numpy()
+        q = self.state_value_device(state, raw=raw).reshape(-1, 1).double().cpu().numpy()
         return q[0] if single else q
 
-    def state_value_device(self, state):
+    def state_value_device(self, state, raw=False):
         """Q(s, pi(s)) for a batch of states as a DEVICE tensor [m] (no host round trip: the SmartStart selection of the
-        vectorised loop feeds candidate states gathered from the device replay ring)."""
+        vectorised loop feeds candidate states gathered from the device replay ring).  Denormalised with return
+        statistics, like :meth:`critic` (``raw=True``: the network's output)."""
         o = torch.as_tensor(state, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim)
-        return self.critic(o, self.actor(o)).reshape(-1)     # (both with the agent's observation statistics, if any)
+        return self.critic(o, self.actor(o), raw=raw).reshape(-1)     # (both with the agent's observation statistics, if any)
 
     def observe(self, state, action, reward, new_state, done):
         """:242-247 (store_transition, ddpg_editted.py:281-285)"""
@@ -527,8 +546,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             self.train()
 
     # ---- training diagnostics (ddpg_editted.py:219-253 setup_stats, 341-358 get_stats) ---------------------------------
-    # the reference's stats_names with normalize_observations and parameter noise on; ret_rms_* (normalize_returns) is
-    # not on the accelerated path
+    # the reference's stats_names with normalize_observations and parameter noise on: the eleven slots of the device block.
+    # With Pop-Art (normalize_returns + enable_popart) the four Q slots hold the DENORMALISED values (get_stats_device), and ret_rms_mean /
+    # ret_rms_std -- first in the reference's list, :223-225 -- are added in front by get_stats() from agent.ret_rms (the
+    # vectorised loop logs them beside the block: summary.ret_rms)
     STATS_NAMES = ("obs_rms_mean", "obs_rms_std", "reference_Q_mean", "reference_Q_std", "reference_actor_Q_mean",
                    "reference_actor_Q_std", "reference_action_mean", "reference_action_std",
                    "reference_perturbed_action_mean", "reference_perturbed_action_std", "param_noise_stddev")
@@ -598,6 +619,12 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                                                None if pdesc is None else ctypes.byref(pdesc), o.shape[0], _ffi.ptr(o),
                                                _ffi.ptr(a), _ffi.ptr(self._rms_block()), _ffi.ptr(sd), _ffi.ptr(out),
                                                _ffi.ptr(ws), ws.numel(), _stream()))
+        if self.ret_rms is not None:
+            # the four Q slots are statistics of the network's (normalised) output: mean * std + mean_ret, std * std_ret
+            # in f64 on the current stream (the mean and the std of an affine map of the sample)
+            mean, std = (x.to(torch.float64) for x in self.ret_rms.mean_std_device())
+            out[2:6:2].mul_(std).add_(mean)
+            out[3:6:2].mul_(std)
         return out
 
     @classmethod
@@ -610,6 +637,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         """DDPG_editted.get_stats (ddpg_editted.py:341-358): dict name -> float in the reference's order; with parameter
         noise merged with ``param_noise.get_stats()`` (:355-356).  Reads the device block (a device -> host copy)."""
         stats = self.stats_dict(self.get_stats_device(replay).cpu().tolist())
+        ret_rms = getattr(self, "ret_rms", None)
+        if ret_rms is not None:                                 # setup_stats lists ret_rms first (:223-225)
+            mean, std = ret_rms.mean_std()
+            stats = {"ret_rms_mean": float(mean[0]), "ret_rms_std": float(std[0]), **stats}
         if self.param_noise is not None:
             stats = {**stats, **self.param_noise.get_stats()}
         return stats
@@ -667,6 +698,12 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                 _ffi.ptr(self._rms_block()), ctypes.byref(log_s) if log_s is not None else None, _ffi.ptr(q),
                 0 if carry_returns else 1, _ffi.ptr(out), _ffi.ptr(ws), ws.numel(), eval_env._seed, eval_env.env_id0,
                 eval_env.t, _stream()))
+            if self.ret_rms is not None:                         # eval/Q, eval/Q_std and eval_qs are denormalised Q too
+                mean, std = self.ret_rms.mean_std_device()
+                out[3:4].mul_(std.to(torch.float64)).add_(mean.to(torch.float64))
+                out[4:5].mul_(std.to(torch.float64))
+                if q is not None:
+                    q.mul_(std).add_(mean)
         eval_env.t += K
         return out
 
@@ -713,18 +750,41 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             raise ValueError(f"batch_idx must be [{n_iters}, {self.batch_size}], got {tuple(batch_idx.shape)}")
         with torch.cuda.device(self.device):
             # gradient partials of the multi-workgroup path (layers wider than 64 / batch != 64); kept with the agent
-            need = self.lib.ssc_ddpg_train_workspace_bytes(ctypes.byref(d))
+            need = (self.lib.ssc_ddpg_train_popart_workspace_bytes if self.popart
+                    else self.lib.ssc_ddpg_train_workspace_bytes)(ctypes.byref(d))
             ws = getattr(self, "_train_ws", None)
             if ws is None or ws.numel() < need:
                 ws = self._train_ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
             rms = self._rms_block(obs_rms)
-            if rms is None:
+            if self.popart:
+                # Pop-Art (ddpg_editted.py:201-217, 291-301): the return statistics move with every iteration and both
+                # critics' output layers with them; four launches per iteration on the multi-workgroup kernels
+                _ffi.check(self.lib.ssc_ddpg_train_ws_popart(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
+                                                             _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream(),
+                                                             _ffi.ptr(rms), _ffi.ptr(self.ret_rms.block)))
+            elif rms is None:
                 _ffi.check(self.lib.ssc_ddpg_train_ws(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
                                                       _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream()))
             else:
                 _ffi.check(self.lib.ssc_ddpg_train_ws_rms(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
                                                           _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream(), _ffi.ptr(rms)))
         return losses
+
+    def popart_workspace(self):
+        """What the last Pop-Art iteration left in the learner's workspace, as views (include/ssc.h: [the plain step's
+        workspace | y | partials | scalars], each part rounded up to 256 bytes): ``y`` fp32 [batch_size], ``partials`` f64
+        [ceil(batch_size / 16), 2] = per-workgroup (sum y, sum y^2), ``scalars`` fp32 [4] = (mu_old, sigma_old, mu_new,
+        sigma_new)."""
+        if not self.popart or getattr(self, "_train_ws", None) is None:
+            raise RuntimeError("popart_workspace: no Pop-Art iteration has run on this agent")
+        up = lambda x: (int(x) + 255) // 256 * 256
+        B, nb = self.batch_size, (self.batch_size + 15) // 16
+        o_y = up(self.lib.ssc_ddpg_train_workspace_bytes(ctypes.byref(self.ddpg_desc())))
+        o_part = o_y + up(4 * B)
+        o_scal = o_part + up(16 * nb)
+        ws = self._train_ws
+        return dict(y=ws[o_y:o_y + 4 * B].view(torch.float32), partials=ws[o_part:o_part + 16 * nb].view(torch.float64).view(nb, 2),
+                    scalars=ws[o_scal:o_scal + 16].view(torch.float32))
 
     def train_from(self, device_replay, n_iters=None):
         """``train()`` on a :class:`DeviceReplayBuffer`: batch indices drawn on the device, the records read

@@ -57,5 +57,11 @@ void ddpg_wide_finish(const ssc_ddpg_desc *d, int32_t n_iters, hipStream_t strea
 // d_rms (all three): NULL, or the RunningMeanStd block of normalize_observations (actor_device.h)
 int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                     float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms);
+// Pop-Art (normalize_returns + enable_popart): every shape runs the multi-workgroup kernels, four launches per iteration;
+// d_ret_rms: the one-column RunningMeanStd block of the returns, read and written
+size_t ddpg_popart_workspace_bytes(const ssc_ddpg_desc *d);
+int ddpg_train_wide_popart(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
+                           float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms,
+                           double *d_ret_rms);
 
 }  // namespace ssc

@@ -679,6 +679,39 @@ extern "C" int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *d, const ssc_replay_vi
                           d_rms);
 }
 
+static bool ddpg_desc_sized(const ssc_ddpg_desc *d) {
+    return d != nullptr && d->batch_size >= 1 && d->batch_size <= 4096 && d->obs_dim >= 1 && d->act_dim >= 1 && d->actor_h1 >= 1 &&
+           d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1;
+}
+
+extern "C" size_t ssc_ddpg_train_popart_workspace_bytes(const ssc_ddpg_desc *d) {
+    return ddpg_desc_sized(d) ? ddpg_popart_workspace_bytes(d) : 256;
+}
+
+// normalize_returns + enable_popart (ddpg_editted.py:201-217, 291-301): the step with the return statistics d_ret_rms,
+// on the multi-workgroup kernels whatever the shape (ddpg_train_wide.hip)
+extern "C" int ssc_ddpg_train_ws_popart(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
+                                        int32_t n_iters, float *d_losses, void *d_workspace, size_t workspace_bytes,
+                                        ssc_stream_t stream, const double *d_rms, double *d_ret_rms) {
+    const char *who = "ssc_ddpg_train_ws_popart";
+    if (d_ret_rms == nullptr)
+        return ddpg_train_any(who, d, rp, d_batch_idx, n_iters, d_losses, d_workspace, workspace_bytes, true, stream, d_rms);
+    SSC_REQUIRE(d && rp, "%s: NULL descriptor", who);
+    SSC_REQUIRE(n_iters >= 0, "%s: n_iters < 0", who);
+    SSC_REQUIRE(d->batch_size >= 1, "%s: batch_size %d", who, d->batch_size);
+    SSC_REQUIRE(d->obs_dim >= 1 && d->obs_dim <= SSC_MAX_STATE && d->act_dim >= 1 && d->act_dim <= SSC_MAX_ACT,
+                "%s: obs_dim/act_dim out of range", who);
+    SSC_REQUIRE(d->actor_h1 >= 1 && d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1, "%s: bad hidden sizes", who);
+    SSC_REQUIRE(d->critic_l2_reg >= 0.0f, "%s: critic_l2_reg < 0", who);
+    if (n_iters == 0) return SSC_OK;
+    SSC_REQUIRE(d->actor && d->critic && d->target_actor && d->target_critic && d->adam_m_actor && d->adam_v_actor &&
+                    d->adam_m_critic && d->adam_v_critic && d->adam_t,
+                "%s: NULL parameter / optimiser pointer", who);
+    SSC_REQUIRE(rp->s && rp->a && rp->r && rp->t && rp->s2 && rp->capacity > 0 && d_batch_idx, "%s: NULL replay pointer", who);
+    return ddpg_train_wide_popart(d, rp, d_batch_idx, n_iters, d_losses, d_workspace, workspace_bytes, as_stream(stream), d_rms,
+                                  d_ret_rms);
+}
+
 extern "C" int ssc_ddpg_train(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
                               int32_t n_iters, float *d_losses, ssc_stream_t stream) {
     return ddpg_train_any("ssc_ddpg_train", d, rp, d_batch_idx, n_iters, d_losses, nullptr, 0, false, stream);

@@ -21,6 +21,13 @@
 // Two launches per training iteration (the iterations are a serial chain through the parameters); the Adam step
 // counters are read-only during the launch sequence (iteration index added on the fly) and advanced by one
 // one-thread launch at the end.
+//
+// Pop-Art (normalize_returns + enable_popart, ddpg_editted.py:201-217, 291-301) is four launches per iteration on the same
+// pieces: the grad kernel built as a target pass (target networks only; writes y and per-workgroup sums), a one-workgroup
+// renormalise kernel (statistics update, rescaling of both critics' output layers), the grad kernel built without the
+// target levels (normalised TD error), and the unchanged apply pass -- ddpg_train_wide_popart below.
+#include <type_traits>
+
 #include "actor_device.h"
 #include "ddpg_device.h"
 #include "ssc_host.h"
@@ -332,7 +339,78 @@ __device__ __forceinline__ void ln_level(const WideTables *T, int first, int end
     __syncthreads();
 }
 
-// Rms (normalize_observations): the RunningMeanStd block; obs0 / obs1 enter the networks as clip((x - mean) / std)
+// ---- Pop-Art (normalize_returns + enable_popart, ddpg_editted.py:201-217, 291-301) ---------------------------------
+// The kernel's trailing pack carries, besides the observation statistics, ONE of two Pop-Art arguments; each selects a
+// build of its own (the builds without one keep their parameter list and code):
+//   PopTarget  the target pass: only the target levels are in the tables; at td_level the rows' y = r + (1 - t) gamma
+//              (q' sigma_old + mu_old) go to `y` and the workgroup's (sum y, sum y^2) in f64 to `part`;
+//   PopGrad    the gradient pass: no target levels; y comes from `y`, the statistics from `scal` = (mu_old, sigma_old,
+//              mu_new, sigma_new) as the renormalise launch left them.
+struct PopTarget { const double *ret_rms; float *y; double *part; };
+struct PopGrad { const float *y; const float *scal; };
+
+template <class T, class... X> inline constexpr bool kHas = (std::is_same_v<T, X> || ...);
+template <class T> __device__ __forceinline__ T pack_get() { return T{}; }
+template <class T, class H, class... R> __device__ __forceinline__ T pack_get(H h, R... r) {
+    if constexpr (std::is_same_v<T, H>) return h;
+    else return pack_get<T>(r...);
+}
+
+// mean / std of a one-column RunningMeanStd block [sum | sumsq | count] in the fp32 arithmetic of ObsNorm::load
+__device__ __forceinline__ void ret_mean_std(double sum, double sumsq, double cnt, float &mean, float &std) {
+#pragma clang fp contract(off)
+    mean = (float)(sum / cnt);
+    const float sq = (float)(sumsq / cnt);
+    std = sqrtf(fmaxf(sq - mean * mean, 1e-2f));
+}
+
+// td_level of the target pass, thread r < 16 = the workgroup's row r: target_Q with the OLD statistics (:132-133 through
+// denormalize, :292-296), and the 16 rows' sums in f64 by an xor butterfly (the same order every time)
+__device__ __forceinline__ void pop_target_rows(const WideArgs &a, const PopTarget &pt, float *rt, int r, int row0, bool valid) {
+#pragma clang fp contract(off)
+    float mu, sg;
+    ret_mean_std(pt.ret_rms[0], pt.ret_rms[1], pt.ret_rms[2], mu, sg);
+    const float qd = rt[RT_QT * kWR + r] * sg + mu;
+    const float y = rt[RT_R * kWR + r] + (1.0f - rt[RT_T * kWR + r]) * a.gamma * qd;
+    rt[RT_Y * kWR + r] = y;
+    if (valid) pt.y[row0 + r] = y;
+    double s = valid ? (double)y : 0.0, s2 = valid ? (double)y * (double)y : 0.0;
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) {
+        s += __shfl_xor(s, m);
+        s2 += __shfl_xor(s2, m);
+    }
+    if (r == 0) {
+        pt.part[blockIdx.x * 2 + 0] = s;
+        pt.part[blockIdx.x * 2 + 1] = s2;
+    }
+}
+
+// td_level of the gradient pass: critic loss mean((q - (y - mu_new) / sigma_new)^2) (:181 with normalize, :140-149),
+// actor loss -mean(q_pi sigma_new + mu_new) (:131, :170), hence dL/dq_pi = -sigma_new / B
+__device__ __forceinline__ void pop_grad_rows(const WideArgs &a, const PopGrad &pg, float *rt, int r, int row0, bool valid, float *lpart) {
+#pragma clang fp contract(off)
+    const float mu = pg.scal[2], sg = pg.scal[3];
+    const float y = pg.y[min(row0 + r, a.batch - 1)];
+    const float e = rt[RT_Q * kWR + r] - (y - mu) / sg;
+    const float inv_b = 1.0f / (float)a.batch;
+    rt[RT_Y * kWR + r] = y;
+    rt[RT_DQ * kWR + r] = valid ? 2.0f * e * inv_b : 0.0f;
+    rt[RT_DQB * kWR + r] = valid ? -sg * inv_b : 0.0f;
+    float lc = valid ? e * e : 0.0f, la = valid ? -(rt[RT_QPI * kWR + r] * sg + mu) : 0.0f;
+#pragma unroll
+    for (int m = 8; m >= 1; m >>= 1) {
+        lc += __shfl_xor(lc, m);
+        la += __shfl_xor(la, m);
+    }
+    if (r == 0) {
+        lpart[blockIdx.x * 2 + 0] = lc;
+        lpart[blockIdx.x * 2 + 1] = la;
+    }
+}
+
+// Rms (normalize_observations): the RunningMeanStd block; obs0 / obs1 enter the networks as clip((x - mean) / std).
+// The pack may end in a PopTarget or a PopGrad (above).
 template <class... Rms>
 __global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a, Rms... rms) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -411,9 +489,9 @@ __global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a, R
     // last record and carry zero weight in every loss ----
     if (row_thread) {
         const int r = tid;
-        if constexpr (kObsNorm<Rms...>) {
+        if constexpr (kHas<const double *, Rms...>) {
             ObsNorm<SSC_MAX_STATE> nrm;
-            nrm.load(rms_block(rms...), a.obs_dim);
+            nrm.load(pack_get<const double *>(rms...), a.obs_dim);
 #pragma unroll
             for (int k = 0; k < SSC_MAX_STATE; ++k)
                 if (k < a.obs_dim) {
@@ -473,7 +551,11 @@ __global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a, R
         if (lv == a.td_level) {
             // target_Q = r + (1 - terminal) * gamma * Q'(s2, pi'(s2))  (:132-133); critic loss mean((Q - y)^2) (:181),
             // actor loss -mean Q(s, pi(s)) (:168): per-row loss terms and the two output deltas
-            if (row_thread) {
+            if constexpr (kHas<PopTarget, Rms...>) {
+                if (row_thread) pop_target_rows(a, pack_get<PopTarget>(rms...), lds + a.off_RT, tid, row0, valid);
+            } else if constexpr (kHas<PopGrad, Rms...>) {
+                if (row_thread) pop_grad_rows(a, pack_get<PopGrad>(rms...), lds + a.off_RT, tid, row0, valid, a.lpart);
+            } else if (row_thread) {
                 const int r = tid;
                 float *rt = lds + a.off_RT;
                 const float y = rt[RT_R * kWR + r] + (1.0f - rt[RT_T * kWR + r]) * a.gamma * rt[RT_QT * kWR + r];
@@ -757,13 +839,13 @@ void ddpg_wide_finish(const ssc_ddpg_desc *d, int32_t n_iters, hipStream_t strea
     hipLaunchKernelGGL(ddpg_wide_finish_kernel, dim3(1), dim3(1), 0, stream, d->adam_t, n_iters);
 }
 
-int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
-                    float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms) {
-    if (d->batch_size < 1 || d->batch_size > 4096)
-        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: batch_size %d not in 1..4096", d->batch_size);
-    const size_t need = ddpg_wide_workspace_bytes(d);
-    SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= need,
-                "ssc_ddpg_train_ws: workspace %zu < %zu bytes (ssc_ddpg_train_workspace_bytes)", workspace_bytes, need);
+// Which networks a launch's tables hold: all four (the plain step), the target networks up to td_level (Pop-Art target
+// pass), or the trained networks with their backward levels (Pop-Art gradient pass).  The LDS carve and the level
+// numbering are the same in all three.
+enum : int { WIDE_FULL = 0, WIDE_POP_TARGET, WIDE_POP_GRAD };
+
+static int wide_build(const ssc_ddpg_desc *d, const ssc_replay_view *rp, int mode, void *d_workspace, WideArgs &g, size_t &lds_bytes) {
+    const bool tgt = mode != WIDE_POP_GRAD, trn = mode != WIDE_POP_TARGET;
     const int ln = d->layer_norm ? 1 : 0;
     const WNet A{d->obs_dim, d->actor_h1, d->actor_h2, d->act_dim, 0, ln}, C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim, ln};
     const int od = d->obs_dim, ad = d->act_dim;
@@ -771,7 +853,7 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     // with LayerNorm the contractions of the hidden layers leave the pre-normalisation sums and the LayerNorm op applies
     // the activation (ln_level)
     const int epi1 = ln ? EPI_NONE : EPI_RELU, epi2 = ln ? EPI_NONE : act2;
-    WideArgs g{};
+    g = WideArgs{};
     g.rp = *rp; g.batch = d->batch_size; g.obs_dim = od; g.act_dim = ad; g.gamma = d->gamma; g.obs_clip = d->obs_clip;
     // ---- LDS carve: rows of 16 floats ([unit][row]) ------------------------------------------------------------------
     int p = 0;
@@ -804,36 +886,38 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     for (int n = 0; n < 4; ++n) {
         const WNet &N = *nets[n];
         const int head = N.h1 * N.h2;
+        const bool used = n < 2 ? tgt : trn;     // a network the launch leaves out keeps its place in the image, uncopied
         img_lo[n] = p;
-        g.tab.seg[g.tab.n_seg].src = theta[n]; g.tab.seg[g.tab.n_seg].dst = p; g.tab.seg[g.tab.n_seg].n = N.oW2();
+        g.tab.seg[g.tab.n_seg].src = theta[n]; g.tab.seg[g.tab.n_seg].dst = p; g.tab.seg[g.tab.n_seg].n = used ? N.oW2() : 0;
         ++g.tab.n_seg;
         p += N.oW2();
         img_hi[n] = p - (N.oW2() + head);        // flat offsets >= oW2 + head map to img_hi + offset
-        g.tab.seg[g.tab.n_seg].src = theta[n] + N.oW2() + head; g.tab.seg[g.tab.n_seg].dst = p; g.tab.seg[g.tab.n_seg].n = N.total() - N.oW2() - head;
+        g.tab.seg[g.tab.n_seg].src = theta[n] + N.oW2() + head; g.tab.seg[g.tab.n_seg].dst = p;
+        g.tab.seg[g.tab.n_seg].n = used ? N.total() - N.oW2() - head : 0;
         ++g.tab.n_seg;
         p += N.total() - N.oW2() - head;
-        g.tab.big[g.tab.n_big].src = theta[n] + N.oW2(); g.tab.big[g.tab.n_big].n = head;
+        g.tab.big[g.tab.n_big].src = theta[n] + N.oW2(); g.tab.big[g.tab.n_big].n = used ? head : 0;
         ++g.tab.n_big;
     }
     auto img = [&](int n, int flat) { return flat < nets[n]->oW2() ? img_lo[n] + flat : img_hi[n] + flat; };
     g.off_tab = (p + 3) & ~3;
     p = g.off_tab + (int)(sizeof(WideTables) / 4);
     enum { TA = 0, TC = 1, CR = 2, AC = 3 };
-    const size_t lds = (size_t)p * sizeof(float);
+    const size_t lds = lds_bytes = (size_t)p * sizeof(float);
     if (lds > 160 * 1024)
         return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: these layer sizes need %zu B of LDS per workgroup (160 KB available)", lds);
     int ng = 0, nl = 0, nln = 0;
     auto level = [&]() { g.tab.ln_first[nl] = nln; g.tab.level_first[nl++] = ng; };
     // LayerNorm ops behind the current level's contractions; net n's gamma / beta of hidden layer `layer`
     auto ln_fwd = [&](int n, int layer, int x_off, int act, int xhat_off, int rstd_off) {
-        if (!ln) return;
+        if (!ln || !(n < 2 ? tgt : trn)) return;
         const WNet &N = *nets[n];
         WLn &L = g.tab.ln[nln++];
         L = WLn{0, x_off, xhat_off, rstd_off, img(n, layer == 1 ? N.og1() : N.og2()), img(n, layer == 1 ? N.obe1() : N.obe2()),
                 layer == 1 ? N.h1 : N.h2, act, -1, -1};
     };
     auto ln_bwd = [&](int n, int layer, int x_off, int xhat_off, int rstd_off, int gbase) {   // gbase < 0: no parameter gradients
-        if (!ln) return;
+        if (!ln || !(n < 2 ? tgt : trn)) return;
         const WNet &N = *nets[n];
         WLn &L = g.tab.ln[nln++];
         L = WLn{1, x_off, xhat_off, rstd_off, img(n, layer == 1 ? N.og1() : N.og2()), -1, layer == 1 ? N.h1 : N.h2, EPI_NONE,
@@ -842,6 +926,7 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     // net n, flat offset wflat of A(0, 0); big = true: the h1 x h2 block, streamed from L2
     auto gemm = [&](int n, int wflat, bool big, int sm, int sk, int M, int K, int bias_flat, int b_off, int out_off, int epi,
                     int add_off = -1, int aux_off = -1) {
+        if (!(n < 2 ? tgt : trn)) return;        // (a Pop-Art pass holds one pair of networks)
         WGemm &x = g.tab.gemm[ng++];
         x.W = big ? theta[n] + wflat : nullptr;
         x.w_off = big ? 0 : img(n, wflat);
@@ -909,11 +994,11 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     ln_bwd(AC, 1, DU1, XU1, RS + 3 * kWR, 0);
     g.tab.ln_first[nl] = nln;
     g.tab.level_first[nl] = ng;
-    g.n_gemm = ng; g.n_level = nl;
+    g.n_gemm = ng; g.n_level = trn ? nl : g.td_level + 1;   // (the target pass ends with target_Q)
     // gradients, flat [actor | critic], TF trainable_vars order inside a net
     const int nA = A.total(), nC = C.total();
     int nw = 0;
-    auto wgrad = [&](int x_off, int dz_off, int in, int out, int gW, int gb) { g.tab.wg[nw++] = WGrad{x_off, dz_off, in, out, gW, gb}; };
+    auto wgrad = [&](int x_off, int dz_off, int in, int out, int gW, int gb) { if (trn) g.tab.wg[nw++] = WGrad{x_off, dz_off, in, out, gW, gb}; };
     wgrad(C1, DZ2, C.h1 + ad, C.h2, nA + C.oW2(), nA + C.ob2());       // the large ones first: they are dealt out first
     wgrad(U1, DU2, A.h1, A.h2, A.oW2(), A.ob2());
     wgrad(S, DZ1, od, C.h1, nA + C.oW1(), nA + C.ob1());
@@ -925,13 +1010,28 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     const int nb = wide_blocks(d);
     g.gpart = static_cast<float *>(d_workspace);
     g.lpart = ddpg_wide_partials(d, d_workspace, nb).lpart;
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute(d_rms != nullptr ? reinterpret_cast<const void *>(ddpg_wide_grad_kernel<const double *>)
-                                                                : reinterpret_cast<const void *>(ddpg_wide_grad_kernel<>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                           "hipFuncSetAttribute(ddpg_wide_grad_kernel)");
-        if (rc) return rc;
-    }
+    return SSC_OK;
+}
+
+template <class... Rms> static int wide_lds_attr(size_t lds) {
+    if (lds <= 64 * 1024) return SSC_OK;
+    return check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_wide_grad_kernel<Rms...>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                     "hipFuncSetAttribute(ddpg_wide_grad_kernel)");
+}
+
+int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
+                    float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms) {
+    if (d->batch_size < 1 || d->batch_size > 4096)
+        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: batch_size %d not in 1..4096", d->batch_size);
+    const size_t need = ddpg_wide_workspace_bytes(d);
+    SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= need,
+                "ssc_ddpg_train_ws: workspace %zu < %zu bytes (ssc_ddpg_train_workspace_bytes)", workspace_bytes, need);
+    WideArgs g;
+    size_t lds = 0;
+    if (int rc = wide_build(d, rp, WIDE_FULL, d_workspace, g, lds)) return rc;
+    const int nb = wide_blocks(d);
+    if (int rc = d_rms != nullptr ? wide_lds_attr<const double *>(lds) : wide_lds_attr<>(lds)) return rc;
     for (int it = 0; it < n_iters; ++it) {
         g.batch_idx = d_batch_idx + (int64_t)it * d->batch_size;
         if (d_rms != nullptr) hipLaunchKernelGGL(ddpg_wide_grad_kernel<const double *>, dim3(nb), dim3(kWThreads), lds, stream, g, d_rms);
@@ -940,6 +1040,110 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     }
     ddpg_wide_finish(d, n_iters, stream);
     return check_launch("ssc_ddpg_train (wide)");
+}
+
+// ---- Pop-Art: four launches per iteration (target pass, renormalise, gradient pass, apply) -----------------------------
+struct RenormArgs {
+    double *ret_rms;          // [sum | sumsq | count], read and written
+    const double *part;       // [n_part][2] of the target pass
+    float *scal;              // (mu_old, sigma_old, mu_new, sigma_new)
+    float *cW3, *cb3, *tW3, *tb3;   // the output layers of the critic and of the target critic
+    int32_t n_part, batch, h2;
+};
+
+// ret_rms.update(target_Q) (:297), then the rescaling of both output layers that keeps sigma q + mu where it was
+// (setup_popart, :201-217).  One workgroup; thread 0 merges the partials in workgroup order.
+__global__ __launch_bounds__(256) void ddpg_popart_renorm_kernel(RenormArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double sp[2 * 256];
+    __shared__ float sc[4];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 2 * a.n_part; i += 256) sp[i] = a.part[i];
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0, s2 = 0.0;
+        for (int b = 0; b < a.n_part; ++b) {
+            s += sp[2 * b];
+            s2 += sp[2 * b + 1];
+        }
+        const double sum = a.ret_rms[0], sumsq = a.ret_rms[1], cnt = a.ret_rms[2];
+        const double sum_n = sum + s, sumsq_n = sumsq + s2, cnt_n = cnt + (double)a.batch;
+        ret_mean_std(sum, sumsq, cnt, sc[0], sc[1]);
+        ret_mean_std(sum_n, sumsq_n, cnt_n, sc[2], sc[3]);
+        a.ret_rms[0] = sum_n;
+        a.ret_rms[1] = sumsq_n;
+        a.ret_rms[2] = cnt_n;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a.scal[i] = sc[i];
+    }
+    __syncthreads();
+    const float mu_o = sc[0], sg_o = sc[1], mu_n = sc[2], sg_n = sc[3];
+    for (int u = tid; u < a.h2; u += 256) {
+        a.cW3[u] = (a.cW3[u] * sg_o) / sg_n;
+        a.tW3[u] = (a.tW3[u] * sg_o) / sg_n;
+    }
+    if (tid == 0) {
+        a.cb3[0] = ((a.cb3[0] * sg_o + mu_o) - mu_n) / sg_n;
+        a.tb3[0] = ((a.tb3[0] * sg_o + mu_o) - mu_n) / sg_n;
+    }
+}
+
+// [the plain step's workspace | y [batch] | partials [blocks][2] f64 | the four scalars]: the one layout both the size
+// query and the launcher use
+struct PopLayout { float *y; double *part; float *scal; size_t bytes; };
+static PopLayout popart_layout(const ssc_ddpg_desc *d, void *d_workspace) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    char *base = static_cast<char *>(d_workspace);
+    const size_t o_y = up(ddpg_wide_workspace_bytes(d));
+    const size_t o_part = o_y + up((size_t)d->batch_size * sizeof(float));
+    const size_t o_scal = o_part + up((size_t)wide_blocks(d) * 2 * sizeof(double));
+    return PopLayout{reinterpret_cast<float *>(base + o_y), reinterpret_cast<double *>(base + o_part),
+                     reinterpret_cast<float *>(base + o_scal), o_scal + 256};
+}
+
+size_t ddpg_popart_workspace_bytes(const ssc_ddpg_desc *d) { return popart_layout(d, nullptr).bytes; }
+
+template <class... Rms>
+static int wide_popart_iters(const ssc_ddpg_desc *d, WideArgs &gt, WideArgs &gg, size_t lds, const RenormArgs &rn, const PopLayout &L,
+                             const int32_t *d_batch_idx, int32_t n_iters, float *d_losses, void *d_workspace, hipStream_t stream,
+                             Rms... rms) {
+    if (int rc = wide_lds_attr<Rms..., PopTarget>(lds)) return rc;
+    if (int rc = wide_lds_attr<Rms..., PopGrad>(lds)) return rc;
+    const int nb = wide_blocks(d);
+    const PopTarget pt{rn.ret_rms, L.y, L.part};
+    const PopGrad pg{L.y, L.scal};
+    for (int it = 0; it < n_iters; ++it) {
+        gt.batch_idx = gg.batch_idx = d_batch_idx + (int64_t)it * d->batch_size;
+        hipLaunchKernelGGL((ddpg_wide_grad_kernel<Rms..., PopTarget>), dim3(nb), dim3(kWThreads), lds, stream, gt, rms..., pt);
+        hipLaunchKernelGGL(ddpg_popart_renorm_kernel, dim3(1), dim3(256), 0, stream, rn);
+        hipLaunchKernelGGL((ddpg_wide_grad_kernel<Rms..., PopGrad>), dim3(nb), dim3(kWThreads), lds, stream, gg, rms..., pg);
+        ddpg_wide_apply(d, d_workspace, nb, it, d_losses ? d_losses + 2 * it : nullptr, stream);
+    }
+    ddpg_wide_finish(d, n_iters, stream);
+    return check_launch("ssc_ddpg_train_ws_popart");
+}
+
+int ddpg_train_wide_popart(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
+                           float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms,
+                           double *d_ret_rms) {
+    if (d->batch_size < 1 || d->batch_size > 4096)
+        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train_ws_popart: batch_size %d not in 1..4096", d->batch_size);
+    const PopLayout L = popart_layout(d, d_workspace);
+    SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= L.bytes,
+                "ssc_ddpg_train_ws_popart: workspace %zu < %zu bytes (ssc_ddpg_train_popart_workspace_bytes)", workspace_bytes, L.bytes);
+    WideArgs gt, gg;
+    size_t lds = 0;
+    if (int rc = wide_build(d, rp, WIDE_POP_TARGET, d_workspace, gt, lds)) return rc;
+    if (int rc = wide_build(d, rp, WIDE_POP_GRAD, d_workspace, gg, lds)) return rc;
+    const int ln = d->layer_norm ? 1 : 0;
+    const WNet C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim, ln};
+    RenormArgs rn{};
+    rn.ret_rms = d_ret_rms; rn.part = L.part; rn.scal = L.scal;
+    rn.cW3 = d->critic + C.oW3(); rn.cb3 = d->critic + C.ob3();
+    rn.tW3 = d->target_critic + C.oW3(); rn.tb3 = d->target_critic + C.ob3();
+    rn.n_part = wide_blocks(d); rn.batch = d->batch_size; rn.h2 = C.h2;
+    if (d_rms != nullptr) return wide_popart_iters(d, gt, gg, lds, rn, L, d_batch_idx, n_iters, d_losses, d_workspace, stream, d_rms);
+    return wide_popart_iters(d, gt, gg, lds, rn, L, d_batch_idx, n_iters, d_losses, d_workspace, stream);
 }
 
 }  // namespace ssc

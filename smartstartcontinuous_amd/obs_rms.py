@@ -87,6 +87,16 @@ class ObsRms:
         """Host fp32 (mean, std): the values the kernels derive from the block."""
         return mean_std_f32(self.block.cpu().numpy(), self.obs_dim)
 
+    def mean_std_device(self):
+        """(mean, std) as fp32 DEVICE tensors [obs_dim], formed on the current stream without a host read, one tensor op
+        per rounding of the kernels' derivation (f64 divide, round to fp32, fp32 multiply, subtract, max, square root)."""
+        d, b = self.obs_dim, self.block
+        cnt = b[2 * d]
+        mean = (b[:d] / cnt).to(torch.float32)
+        sq = (b[d:2 * d] / cnt).to(torch.float32)
+        var = sq - mean * mean
+        return mean, torch.sqrt(torch.clamp_min(var, RMS_EPSILON))
+
     def snapshot_into(self, other):
         """Stream-ordered copy of the block into ``other`` (an ObsRms or a tensor of the same shape)."""
         dst = other.block if isinstance(other, ObsRms) else other

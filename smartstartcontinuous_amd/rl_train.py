@@ -361,6 +361,11 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     ``summary.agent_stats_chunks`` (the chunk number of each row).  Everything else the loop computes is bit-identical to
     the run without it.
 
+    A Pop-Art agent (``normalize_returns`` with ``enable_popart``: the learner moves the return statistics and rescales both
+    critics' output layers, four launches per iteration) runs in both loop forms: the critic and the block are touched on
+    the learner's stream only.  With ``stats_every`` the fp32 (mean, std) of ``agent.ret_rms`` is logged on the device beside
+    every diagnostics row: ``summary.ret_rms`` (``mean``, ``std`` arrays, NaN where the row is).
+
     ``eval_env`` + ``eval_every=k``: the evaluation block of the reference (training_editted.py:122-138, 160-164) --
     ``agent.evaluate_device(eval_env, eval_steps)``: the plain actor without noise on a VecEnv of its own, eval/return,
     eval/Q, eval/episodes -- behind the learner iterations (and the adapt / re-perturb) of every chunk i with
@@ -423,6 +428,11 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         stats_every = int(stats_every)
         stats_log = torch.full((-(-num_chunks // stats_every), SSC_DDPG_N_STATS), float("nan"), dtype=torch.float64,
                                device=env.device)
+    # Pop-Art: (mean, std) of the return statistics beside every diagnostics row, formed on the device
+    ret_rms = getattr(agent, "ret_rms", None)
+    ret_log = None
+    if stats_log is not None and ret_rms is not None:
+        ret_log = torch.full((stats_log.shape[0], 2), float("nan"), dtype=torch.float32, device=env.device)
 
     def log_stats(i, perturbed=None):
         """the diagnostics of chunk i, enqueued on the current (learner) stream"""
@@ -431,6 +441,10 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         if getattr(agent, "stats_sample", None) is None and len(replay) < agent.batch_size:
             return                                               # no sample yet: the row stays NaN
         agent.get_stats_device(replay, out=stats_log[i // stats_every], perturbed=perturbed)
+        if ret_log is not None:
+            mean, std = ret_rms.mean_std_device()
+            ret_log[i // stats_every, 0:1].copy_(mean)
+            ret_log[i // stats_every, 1:2].copy_(std)
 
     eval_log = None
     if eval_env is not None:
@@ -452,6 +466,9 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             host = stats_log.cpu().numpy()
             summary.agent_stats = {name: host[:, j].copy() for j, name in enumerate(agent.STATS_NAMES)}
             summary.agent_stats_chunks = [(r + 1) * stats_every - 1 for r in range(host.shape[0])]
+        if ret_log is not None:
+            host = ret_log.cpu().numpy()
+            summary.ret_rms = {"mean": host[:, 0].copy(), "std": host[:, 1].copy()}
         if eval_log is not None:
             host = eval_log.cpu().numpy()
             summary.eval_stats = {name: host[:, j].copy() for j, name in enumerate(agent.EVAL_NAMES)}
@@ -595,6 +612,9 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
     configured; navigating steps are untouched; the selection's Q(s, pi(s)) uses the plain actor.
     Returns (Summary, losses per chunk, replay)."""
     base = getattr(smart, "agent", None)
+    if getattr(base, "ret_rms", None) is not None:
+        raise NotImplementedError("rl_train_vec_smartstart: a base agent with normalize_returns / Pop-Art is not supported "
+                                  "(the selection reads the raw critic)")
     if getattr(base, "param_noise", None) is not None and not hasattr(base, "param_noise_cycle"):
         raise NotImplementedError("rl_train_vec_smartstart: a base agent with param_noise needs param_noise_cycle "
                                   "(the one-launch adapt and re-perturb)")

@@ -296,6 +296,9 @@ def rl_train_sharded_ddpg(env, agent, num_chunks, chunk_steps, rank, world, lear
     if getattr(agent, "obs_rms", None) is not None:
         # the reference all-reduces RunningMeanStd over its MPI ranks; that exchange is not built yet
         raise NotImplementedError("rl_train_sharded_ddpg: normalize_observations=True is not supported on the sharded loop")
+    if getattr(agent, "ret_rms", None) is not None:
+        # the reference all-reduces ret_rms like obs_rms; the broadcast carries the actor only, not the statistics
+        raise NotImplementedError("rl_train_sharded_ddpg: normalize_returns / Pop-Art is not supported on the sharded loop")
     from .replay_buffer import DeviceReplayBuffer
     from .rl_train import Summary, default_drain_every, epsilon_schedule
     from .vec_env import EpisodeRing, TransitionChunk

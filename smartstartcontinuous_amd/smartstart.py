@@ -227,6 +227,11 @@ class VecSmartStart:
                  stepsizes_in_waypoint_radii=1, steps_per_waypoint=1, chunk_steps=64, seed=1234, log_modes=False,
                  kde_max_states=500000):
         from . import navigator as nav
+        if getattr(agent, "ret_rms", None) is not None:
+            # the selection kernels rank candidates by the RAW critic output; with return normalisation / Pop-Art that is
+            # the normalised Q, and the denormalising read-out is not in those kernels yet
+            raise NotImplementedError("VecSmartStart: a base agent with normalize_returns / Pop-Art is not supported "
+                                      "(the selection reads the raw critic)")
         self.env, self.agent, self.model = env, agent, dyn_model
         self.eta, self.eta_decay_factor = float(eta), float(eta_decay_factor)
         self.n_ss, self.n_plans = int(n_ss), int(n_plans)
