@@ -301,3 +301,16 @@ def default_params(kind, power_scalar=1.0, max_episode_steps=0):
 def ptr(t):
     """data_ptr() of a tensor (or None -> NULL)."""
     return None if t is None else c_void_p(t.data_ptr())
+
+
+def stream(device=None):
+    """The ``hipStream_t`` argument of a launch: torch's current stream on ``device`` (default: the current device)."""
+    import torch
+    return c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def set_net_ptrs(desc, w):
+    """Point an ActorDesc / CriticDesc at the tensors of the weight dict ``w``: W1 .. b3 and, for a LayerNorm network
+    (models_editted.py:45-46, 50-51, 85-86, 91-92), ln1_g .. ln2_b."""
+    for k in ("W1", "b1", "W2", "b2", "W3", "b3") + (("ln1_g", "ln1_b", "ln2_g", "ln2_b") if "ln1_g" in w else ()):
+        setattr(desc, k, w[k].data_ptr())

@@ -78,10 +78,6 @@ class ReplayBufferRLAgent(RLAgent):
         self.replay_buffer.set_main_agent(new_main_agent)
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 # --------------------------------------------------------------------------------- DDPG --
 class DecayingOrnsteinUhlenbeckActionNoise:
     """DDPG_Baselines_agent.py:52-78 over baselines' OrnsteinUhlenbeckActionNoise [third-party]:
@@ -144,6 +140,18 @@ def with_layer_norm(weights):
     return dict(weights, ln1_b=torch.zeros(h1), ln1_g=torch.ones(h1), ln2_b=torch.zeros(h2), ln2_g=torch.ones(h2))
 
 
+def views_like(flat, like):
+    """dict of views into ``flat`` with the shapes of the weight dict ``like``, in ``param_keys`` order -- the ONE walk over
+    the flat layout [W1|b1|(beta1|gamma1)|W2|b2|(beta2|gamma2)|W3|b3]."""
+    views, o = {}, 0
+    for k in param_keys(like):
+        shape = tuple(torch.as_tensor(like[k]).shape)
+        n = int(np.prod(shape))
+        views[k] = flat[o:o + n].view(shape)
+        o += n
+    return views
+
+
 def flatten_params(weights, device, extra=0):
     """One flat fp32 tensor in TensorFlow trainable_vars order [W1|b1|W2|b2|W3|b3] (with LayerNorm:
     [W1|b1|beta1|gamma1|W2|b2|beta2|gamma2|W3|b3]) plus a dict of VIEWS into it, so that kernels reading the dict see what
@@ -154,13 +162,7 @@ def flatten_params(weights, device, extra=0):
     if extra:
         parts.append(torch.zeros(int(extra), dtype=torch.float32))
     flat = torch.cat(parts).to(device).contiguous()
-    views, o = {}, 0
-    for k in keys:
-        shape = tuple(torch.as_tensor(weights[k]).shape)
-        n = int(np.prod(shape))
-        views[k] = flat[o:o + n].view(shape)
-        o += n
-    return flat, views
+    return flat, views_like(flat, weights)
 
 
 class AdaptiveParamNoiseSpec:
@@ -303,12 +305,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         self.h2, self.act_dim = w["W3"].shape
         d = _ffi.ActorDesc()
         d.obs_dim, d.h1, d.h2, d.act_dim = self.obs_dim, self.h1, self.h2, self.act_dim
-        d.W1, d.b1, d.W2, d.b2, d.W3, d.b3 = (w[k].data_ptr() for k in ("W1", "b1", "W2", "b2", "W3", "b3"))
+        _ffi.set_net_ptrs(d, w)
         d.last_layer_tanh = int(self.lastLayerTanh)
         d.precision = _ffi.SSC_PREC_F32 if self.precision == "f32" else _ffi.SSC_PREC_BF16_MFMA
         d.obs_clip = float(self.observation_range[1])
-        if "ln1_g" in w:
-            d.ln1_g, d.ln1_b, d.ln2_g, d.ln2_b = (w[k].data_ptr() for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b"))
         self._desc = d
         if self.param_noise is not None:
             self._setup_param_noise()
@@ -316,14 +316,9 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
     # ---- parameter-space noise ---------------------------------------------------------------
     def _views_desc(self, flat):
         """views into ``flat`` laid out like ``actor_flat`` + the actor descriptor over them"""
-        views, o = {}, 0
-        for k, v in self.weights.items():
-            views[k] = flat[o:o + v.numel()].view(v.shape)
-            o += v.numel()
+        views = views_like(flat, self.weights)
         d = _ffi.ActorDesc.from_buffer_copy(self._desc)
-        d.W1, d.b1, d.W2, d.b2, d.W3, d.b3 = (views[k].data_ptr() for k in ("W1", "b1", "W2", "b2", "W3", "b3"))
-        if "ln1_g" in views:
-            d.ln1_g, d.ln1_b, d.ln2_g, d.ln2_b = (views[k].data_ptr() for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b"))
+        _ffi.set_net_ptrs(d, views)
         return views, d
 
     def _setup_param_noise(self):
@@ -352,7 +347,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.ssc_param_noise_perturb(self.actor_flat.numel(), _ffi.ptr(self.actor_flat), _ffi.ptr(dst),
                                                         _ffi.ptr(self.d_param_noise_stddev), *self._pn_skip,
-                                                        self.param_noise_seed, g, _stream()))
+                                                        self.param_noise_seed, g, _ffi.stream()))
         return g
 
     def perturb_policy(self):
@@ -376,7 +371,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.ssc_param_noise_adapt(a.numel(), _ffi.ptr(a), _ffi.ptr(b), pn.desired_action_stddev,
                                                       pn.adoption_coefficient, _ffi.ptr(self.d_param_noise_stddev),
-                                                      _ffi.ptr(self.d_param_noise_distance), _stream()))
+                                                      _ffi.ptr(self.d_param_noise_distance), _ffi.stream()))
         return self.d_param_noise_distance
 
     def param_noise_cycle(self, obs_batch, dst=None, obs_rms=None):
@@ -399,7 +394,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                 ctypes.byref(self._desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(rms), self.actor_flat.numel(),
                 _ffi.ptr(self.actor_flat), *self._pn_skip, self.param_noise_seed, g, g + 1, pn.desired_action_stddev,
                 pn.adoption_coefficient, _ffi.ptr(self.d_param_noise_stddev), _ffi.ptr(self.d_param_noise_distance),
-                _ffi.ptr(dst), _stream()))
+                _ffi.ptr(dst), _ffi.stream()))
         self.param_noise_generation = g + 2
         self.perturbed_generation = g + 1
         return self.d_param_noise_distance
@@ -415,11 +410,9 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         c.obs_dim, c.h1 = w["W1"].shape
         c.h2 = w["W2"].shape[1]
         c.act_dim = w["W2"].shape[0] - c.h1
-        c.W1, c.b1, c.W2, c.b2, c.W3, c.b3 = (w[k].data_ptr() for k in ("W1", "b1", "W2", "b2", "W3", "b3"))
+        _ffi.set_net_ptrs(c, w)
         c.last_layer_tanh = int(self.lastLayerTanh)
         c.obs_clip = float(self.observation_range[1])
-        if "ln1_g" in w:
-            c.ln1_g, c.ln1_b, c.ln2_g, c.ln2_b = (w[k].data_ptr() for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b"))
         self._critic_desc = c
 
     def _rms_block(self, obs_rms=None):
@@ -445,10 +438,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         with torch.cuda.device(self.device):
             if rms is None:
                 _ffi.check(self.lib.ssc_critic_forward(ctypes.byref(self._critic_desc), o.shape[0], _ffi.ptr(o),
-                                                       _ffi.ptr(a), _ffi.ptr(q), _stream()))
+                                                       _ffi.ptr(a), _ffi.ptr(q), _ffi.stream()))
             else:
                 _ffi.check(self.lib.ssc_critic_forward_rms(ctypes.byref(self._critic_desc), o.shape[0], _ffi.ptr(o),
-                                                           _ffi.ptr(a), _ffi.ptr(q), _stream(), _ffi.ptr(rms)))
+                                                           _ffi.ptr(a), _ffi.ptr(q), _ffi.stream(), _ffi.ptr(rms)))
         return q if raw or self.ret_rms is None else self._denormalize(q)
 
     def actor(self, obs, obs_rms=None):
@@ -464,10 +457,10 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         with torch.cuda.device(self.device):
             if rms is None:
                 _ffi.check(self.lib.ssc_actor_forward(ctypes.byref(desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
-                                                      _stream()))
+                                                      _ffi.stream()))
             else:
                 _ffi.check(self.lib.ssc_actor_forward_rms(ctypes.byref(desc), o.shape[0], _ffi.ptr(o), _ffi.ptr(out),
-                                                          _stream(), _ffi.ptr(rms)))
+                                                          _ffi.stream(), _ffi.ptr(rms)))
         return out
 
     # ---- RLAgent ---------------------------------------------------------------------------
@@ -576,7 +569,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             idx = torch.empty((1, B), dtype=torch.int32, device=self.device)
             with torch.cuda.device(self.device):
                 _ffi.check(self.lib.ssc_replay_sample((replay.seed ^ self._STATS_KEY) & (2 ** 64 - 1), 0, len(replay), 1, B,
-                                                      _ffi.ptr(idx), _stream()))
+                                                      _ffi.ptr(idx), _ffi.stream()))
             rows = idx[0].long()
             self.set_stats_sample(replay.s.index_select(0, rows), replay.a.index_select(0, rows))
         else:                                                    # replay_buffer.py:79-91 with a generator of its own
@@ -618,7 +611,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             _ffi.check(self.lib.ssc_ddpg_stats(ctypes.byref(self._desc), ctypes.byref(self._critic_desc),
                                                None if pdesc is None else ctypes.byref(pdesc), o.shape[0], _ffi.ptr(o),
                                                _ffi.ptr(a), _ffi.ptr(self._rms_block()), _ffi.ptr(sd), _ffi.ptr(out),
-                                               _ffi.ptr(ws), ws.numel(), _stream()))
+                                               _ffi.ptr(ws), ws.numel(), _ffi.stream()))
         if self.ret_rms is not None:
             # the four Q slots are statistics of the network's (normalised) output: mean * std + mean_ret, std * std_ret
             # in f64 on the current stream (the mean and the std of an affine map of the sample)
@@ -684,8 +677,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
             eval_env.reset()
         if log is not None:
             log.step0, log.env_id0 = eval_env.t, eval_env.env_id0
-        st = _ffi.RolloutState(eval_env.s0.data_ptr(), eval_env.s1.data_ptr(), eval_env.steps.data_ptr(),
-                               eval_env.ep_ret.data_ptr(), None)
+        st = eval_env.rollout_state(ou=False)
         log_s = log.as_struct() if log is not None else None
         with torch.cuda.device(self.device):
             need = int(self.lib.ssc_ddpg_eval_workspace_bytes(n))
@@ -697,7 +689,7 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                 float(eval_env.action_space.low[0]), float(eval_env.action_space.high[0]), n, K, ctypes.byref(st),
                 _ffi.ptr(self._rms_block()), ctypes.byref(log_s) if log_s is not None else None, _ffi.ptr(q),
                 0 if carry_returns else 1, _ffi.ptr(out), _ffi.ptr(ws), ws.numel(), eval_env._seed, eval_env.env_id0,
-                eval_env.t, _stream()))
+                eval_env.t, _ffi.stream()))
             if self.ret_rms is not None:                         # eval/Q, eval/Q_std and eval_qs are denormalised Q too
                 mean, std = self.ret_rms.mean_std_device()
                 out[3:4].mul_(std.to(torch.float64)).add_(mean.to(torch.float64))
@@ -760,14 +752,14 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
                 # Pop-Art (ddpg_editted.py:201-217, 291-301): the return statistics move with every iteration and both
                 # critics' output layers with them; four launches per iteration on the multi-workgroup kernels
                 _ffi.check(self.lib.ssc_ddpg_train_ws_popart(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
-                                                             _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream(),
+                                                             _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _ffi.stream(),
                                                              _ffi.ptr(rms), _ffi.ptr(self.ret_rms.block)))
             elif rms is None:
                 _ffi.check(self.lib.ssc_ddpg_train_ws(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
-                                                      _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream()))
+                                                      _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _ffi.stream()))
             else:
                 _ffi.check(self.lib.ssc_ddpg_train_ws_rms(ctypes.byref(d), ctypes.byref(rv), _ffi.ptr(batch_idx), n_iters,
-                                                          _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream(), _ffi.ptr(rms)))
+                                                          _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _ffi.stream(), _ffi.ptr(rms)))
         return losses
 
     def popart_workspace(self):

@@ -21,10 +21,6 @@ from . import _ffi
 from .vec_env import RandomPolicy, VecEnv
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class Policy_Random:
     """NN_Dynamics_Model/policy_random.py:3-15.  ``get_action`` is the host protocol; ``CollectSamples``
     recognises the class and runs the device random policy (same U(low, high), Philox-keyed) instead."""
@@ -73,7 +69,7 @@ def _scan(chunk):
     log = chunk.as_struct()
     with torch.cuda.device(dev):
         _ffi.check(lib.ssc_dataset_scan(ctypes.byref(log), chunk.K, n, _ffi.ptr(lens), _ffi.ptr(off), _ffi.ptr(ws),
-                                        ws.numel(), _stream()))
+                                        ws.numel(), _ffi.stream()))
     return lens, off
 
 
@@ -90,7 +86,7 @@ def dataset_from_chunk(chunk):
         Y = torch.empty((rows, 1), dtype=torch.float32, device=dev)
         Z = torch.empty((rows, d), dtype=torch.float32, device=dev)
         _ffi.check(lib.ssc_dataset_build(ctypes.byref(log), d, K, n, _ffi.ptr(lens), _ffi.ptr(off), rows, _ffi.ptr(X),
-                                         _ffi.ptr(Y), _ffi.ptr(Z), _stream()))
+                                         _ffi.ptr(Y), _ffi.ptr(Z), _ffi.stream()))
     return TrainingSet(X, Y, Z, lens, off)
 
 
@@ -104,7 +100,7 @@ def column_stats(x):
     ws = torch.empty(max(int(lib.ssc_column_stats_workspace_bytes(cols)), 8), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
         _ffi.check(lib.ssc_column_stats(_ffi.ptr(x), rows, cols, _ffi.ptr(mean), _ffi.ptr(std), _ffi.ptr(ws), ws.numel(),
-                                        _stream()))
+                                        _ffi.stream()))
     return mean, std
 
 
@@ -117,7 +113,7 @@ def zscore_into(x, mean, std, out, col0=0):
         raise ValueError("out must be a contiguous fp32 matrix with one row per data row")
     with torch.cuda.device(x.device):
         _ffi.check(lib.ssc_zscore(_ffi.ptr(x), rows, cols, _ffi.ptr(mean), _ffi.ptr(std), _ffi.ptr(out), out.shape[1],
-                                  col0, _stream()))
+                                  col0, _ffi.stream()))
     return out
 
 
@@ -136,7 +132,7 @@ def zscore_concat(x, mean_x, std_x, y, mean_y, std_y, out=None):
         raise ValueError("out must be a contiguous fp32 [rows, cols_x + cols_y] matrix")
     with torch.cuda.device(x.device):
         _ffi.check(lib.ssc_zscore_concat(_ffi.ptr(x), cx, _ffi.ptr(mean_x), _ffi.ptr(std_x), _ffi.ptr(y), cy, _ffi.ptr(mean_y),
-                                         _ffi.ptr(std_y), rows, _ffi.ptr(out), _stream()))
+                                         _ffi.ptr(std_y), rows, _ffi.ptr(out), _ffi.stream()))
     return out
 
 
@@ -149,7 +145,7 @@ def add_noise_device(x, noise_to_signal, seed, stream_id=0, mean=None):
         mean, _ = column_stats(x)
     with torch.cuda.device(x.device):
         _ffi.check(lib.ssc_add_noise(_ffi.ptr(x), x.shape[0], x.shape[1], _ffi.ptr(mean), float(noise_to_signal),
-                                     int(seed), int(stream_id), _stream()))
+                                     int(seed), int(stream_id), _ffi.stream()))
     return x
 
 

@@ -14,9 +14,7 @@ import torch
 
 from . import _ffi
 
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_stream = _ffi.stream         # the name this module had for it
 
 
 _PREC = {"f32": _ffi.SSC_PREC_F32, "bf16_mfma": _ffi.SSC_PREC_BF16_MFMA}
@@ -132,7 +130,7 @@ class DynamicsModel:
         with torch.cuda.device(self.device):
             ws = self._workspace(self.lib.ssc_mlp_train_workspace_bytes(ctypes.byref(d), B))
             _ffi.check(self.lib.ssc_mlp_train_step(ctypes.byref(d), _ffi.ptr(X), _ffi.ptr(Z), _ffi.ptr(idx), B,
-                                                   _ffi.ptr(loss), _ffi.ptr(ws), ws.numel(), _stream()))
+                                                   _ffi.ptr(loss), _ffi.ptr(ws), ws.numel(), _ffi.stream()))
         self.invalidate()
 
     def train_steps(self, X, Z, idx, lr=0.001):
@@ -145,7 +143,7 @@ class DynamicsModel:
         with torch.cuda.device(self.device):
             ws = self._workspace(self.lib.ssc_mlp_train_workspace_bytes(ctypes.byref(d), B))
             _ffi.check(self.lib.ssc_mlp_train_steps(ctypes.byref(d), _ffi.ptr(X), _ffi.ptr(Z), _ffi.ptr(idx), B, n_steps,
-                                                    _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _stream()))
+                                                    _ffi.ptr(losses), _ffi.ptr(ws), ws.numel(), _ffi.stream()))
         self.invalidate()
         return losses
 
@@ -201,7 +199,7 @@ class DynamicsModel:
         out = torch.empty(n_batches + 1, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.ssc_mse_batches(_ffi.ptr(pred), _ffi.ptr(Z[:rows].contiguous()), n_batches, int(batchsize) * self.out_dim,
-                                                _ffi.ptr(out), out.data_ptr() + 4 * n_batches, _stream()))
+                                                _ffi.ptr(out), out.data_ptr() + 4 * n_batches, _ffi.stream()))
         return float(out[n_batches].item())
 
     def _workspace(self, nbytes):
@@ -218,7 +216,7 @@ class DynamicsModel:
             self._image_stale = True
         if self._image_stale:
             _ffi.check(self.lib.ssc_dyn_prepare(ctypes.byref(self.desc), ctypes.byref(self.norm),
-                                                _ffi.ptr(self._image), self._image.numel(), _stream()))
+                                                _ffi.ptr(self._image), self._image.numel(), _ffi.stream()))
             self._image_stale = False
         return self._image
 
@@ -258,7 +256,7 @@ class DynamicsModel:
             else:
                 ws = self._workspace(self.lib.ssc_mlp_workspace_bytes(ctypes.byref(self.desc), m, prec))
             _ffi.check(self.lib.ssc_mlp_forward(ctypes.byref(self.desc), m, _ffi.ptr(x), _ffi.ptr(y), prec,
-                                                _ffi.ptr(ws), ws.numel(), _stream()))
+                                                _ffi.ptr(ws), ws.numel(), _ffi.stream()))
         return y
 
     def do_forward_sim_sampled(self, state0, sampling, m, H, precision=None, out=None, A_out=None):
@@ -278,7 +276,7 @@ class DynamicsModel:
                     A_out = torch.empty((m, H, self.act_dim), dtype=torch.float32, device=self.device)
             _ffi.check(self.lib.ssc_mpc_forward_sim(ctypes.byref(self.desc), ctypes.byref(self.norm), ctypes.byref(sampling),
                                                     m, H, self.state_dim, self.act_dim, _ffi.ptr(s0), s0_rows,
-                                                    _ffi.ptr(A_out), _ffi.ptr(S), prec, _ffi.ptr(ws), ws.numel(), _stream()))
+                                                    _ffi.ptr(A_out), _ffi.ptr(S), prec, _ffi.ptr(ws), ws.numel(), _ffi.stream()))
         return S
 
     def do_forward_sim(self, state0, actions, precision=None, out=None):
@@ -299,7 +297,7 @@ class DynamicsModel:
             _ffi.check(self.lib.ssc_dyn_forward_sim(ctypes.byref(self.desc), ctypes.byref(self.norm), m, H,
                                                     self.state_dim, self.act_dim, _ffi.ptr(s0), s0_rows,
                                                     _ffi.ptr(A), _ffi.ptr(S), prec, _ffi.ptr(ws), ws.numel(),
-                                                    _stream()))
+                                                    _ffi.stream()))
         return S
 
 
@@ -484,7 +482,7 @@ def mpc_sample_actions(P, N, H, low, high, seed, problem_id0=0, t=0, device="cud
     hi = (ctypes.c_float * act)(*high.tolist())
     with torch.cuda.device(A.device):
         _ffi.check(_ffi.lib().ssc_mpc_sample_actions(P, N, H, act, lo, hi, int(seed), int(problem_id0), int(t),
-                                                     _ffi.ptr(t_base), _ffi.ptr(A), _stream()))
+                                                     _ffi.ptr(t_base), _ffi.ptr(A), _ffi.stream()))
     return A
 
 
@@ -509,7 +507,7 @@ def mpc_score(problems, S, out=None):
         nbytes = lib.ssc_mpc_score_workspace_bytes(P, N, H1 - 1)
         ws = o.get("ws") if o.get("ws") is not None else torch.empty(nbytes, dtype=torch.uint8, device=S.device)
         _ffi.check(lib.ssc_mpc_score(ctypes.byref(st), _ffi.ptr(S), _ffi.ptr(scores), _ffi.ptr(best_idx),
-                                     _ffi.ptr(best_score), _ffi.ptr(ws), ws.numel(), _stream()))
+                                     _ffi.ptr(best_score), _ffi.ptr(ws), ws.numel(), _ffi.stream()))
     return scores.view(P, N), best_idx, best_score
 
 
@@ -541,7 +539,7 @@ def mpc_score_select(problems, S, sampling=None, A=None, act_dim=1, noise_amount
         _ffi.check(lib.ssc_mpc_score_select(ctypes.byref(st), _ffi.ptr(S), _ffi.ptr(scores), _ffi.ptr(best_idx),
                                             _ffi.ptr(best_score), _ffi.ptr(A), ctypes.byref(sampling) if sampling is not None else None,
                                             int(act_dim), float(noise_amount), int(seed), int(problem_id0), int(t),
-                                            _ffi.ptr(action), _ffi.ptr(path), _ffi.ptr(ws), ws.numel(), _stream()))
+                                            _ffi.ptr(action), _ffi.ptr(path), _ffi.ptr(ws), ws.numel(), _ffi.stream()))
     return scores.view(P, N), best_idx, action, path
 
 
@@ -556,7 +554,7 @@ def mpc_select_action(A, S, best_idx, P, noise_amount, seed, problem_id0=0, t=0,
     with torch.cuda.device(A.device):
         _ffi.check(_ffi.lib().ssc_mpc_select_action(P, N, H, d, act, _ffi.ptr(A), _ffi.ptr(S), _ffi.ptr(best_idx),
                                                     float(noise_amount), int(seed), int(problem_id0), int(t),
-                                                    _ffi.ptr(action), _ffi.ptr(path), _stream()))
+                                                    _ffi.ptr(action), _ffi.ptr(path), _ffi.stream()))
     return action, path
 
 
@@ -600,7 +598,7 @@ class NavigatorBatch:
         with torch.cuda.device(ns.device):
             _ffi.check(_ffi.lib().ssc_mpc_observe(ctypes.byref(st), _ffi.ptr(ns), _ffi.ptr(self.problems.cur_idx),
                                                   _ffi.ptr(self.actions_done), self.give_up, self.final_steps,
-                                                  _ffi.ptr(self.at_goal), _stream()))
+                                                  _ffi.ptr(self.at_goal), _ffi.stream()))
 
     def restart(self, mask):
         """Envs that were reset start their plan over (start_new_episode_plan :383-384)."""
@@ -631,26 +629,61 @@ class NavigatorBatch:
         forward sim from the planning states -> score -> ``ssc_mpc_rollout_step``.  Step index and log row come
         from device counters, so the sequence is captured once as a HIP graph and replayed."""
         fb = self._fused_buffers(env.device)
-        lib = _ffi.lib()
         if len(self.low) != 1:
             raise ValueError("the envs of this engine take one action component")
         # (the forward simulation draws the candidate sequences itself and leaves them in fb["A"] for the step kernel)
         sp = mpc_sampling(self.N, self.low, self.high, self.seed, self.problem_id0, 0, t_base=fb["t"])
         S = self.model.do_forward_sim_sampled(fb["plan"], sp, self.P * self.N, self.H, out=self._S, A_out=fb["A"])
+        self._score_and_step(env, chunk, ring, S, _ffi.lib().ssc_mpc_rollout_step)
+
+    def begin_chunk(self, env):
+        """What a graph rollout does in front of a chunk's first step: the device counters start at the env's step index
+        and log row 0, the planning states are the env's observations, the MFMA weight image follows the weights.
+        Returns the fused buffers."""
+        fb = self._fused_buffers(env.device)
+        fb["t"].fill_(env.t)
+        fb["k"].zero_()
+        fb["plan"].copy_(env.observe())
+        self.model.refresh_prepared_image()
+        return fb
+
+    def graph_key(self, env, chunk, ring):
+        """Everything a captured ``fused_step`` bakes in and that can still change under a live navigator: the address of
+        every tensor its launches read or write and every scalar they take by value.  tests/test_gpu_smartstart_vec.py
+        (test_graph_keys_cover_what_the_step_launches_bake_in) lists both and replaces them one at a time: what a launch
+        starts to use belongs here AND there."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        model, pr, fb = self.model, self.problems, self._fused_buffers(env.device)
+        return (self.P, self.N, self.H, env.n, env.kind, bytes(env.params), env._seed, env.env_id0,
+                tuple(ptr(x) for x in (env.s0, env.s1, env.steps, env.ep_ret, env.ou_x, env.stats)),
+                None if chunk is None else tuple(ptr(c) for c in (chunk.obs, chunk.act, chunk.rew, chunk.done, chunk.obs2)),
+                None if ring is None else (ptr(ring.cursor), ptr(ring.env_id), ptr(ring.length), ptr(ring.ret), ring.capacity),
+                model.precision, tuple(ptr(w) for w in model.W), tuple(ptr(b) for b in model.b),
+                bytes(model.norm),   # the fp32 path takes the statistics by value: baked into the capture
+                ptr(model._image), ptr(model._ws),
+                tuple(ptr(x) for x in (pr.wp, pr.left, pr.wp_off, pr.radii, pr.cur_idx)), pr.theta, pr.gamma, pr.hpf, pr.per_row,
+                tuple(ptr(x) for x in (self._S, self.actions_done, self.at_goal, self.start_idx)),
+                tuple(ptr(fb[k]) for k in sorted(fb)), self.noise_amount, self.seed, self.problem_id0, self.give_up,
+                self.final_steps, tuple(self.low.tolist()), tuple(self.high.tolist()))
+
+    def _score_and_step(self, env, chunk, ring, S, step_fn, *lead):
+        """The tail of a fused step: score the simulated candidates ``S`` (``ssc_mpc_score``), then ONE launch ``step_fn``
+        -- ``ssc_mpc_rollout_step``, or ``ssc_smartstart_rollout_step`` with its SmartStartStep in ``lead`` -- for action,
+        env step, log, statistics, waypoint advance and auto-reset."""
+        fb, lib = self._fused_buffers(env.device), _ffi.lib()
         st = self.problems.as_struct(self.N, self.H)
         nav = _ffi.MpcNavState(self.problems.cur_idx.data_ptr(), self.start_idx.data_ptr(), self.actions_done.data_ptr(),
                                self.at_goal.data_ptr(), self.give_up, self.final_steps)
-        rs = _ffi.RolloutState(env.s0.data_ptr(), env.s1.data_ptr(), env.steps.data_ptr(), env.ep_ret.data_ptr(),
-                               env.ou_x.data_ptr())
+        rs = env.rollout_state()
         log_s = chunk.as_struct() if chunk is not None else None
         ring_s = ring.as_struct() if ring is not None else None
         with torch.cuda.device(env.device):
             _ffi.check(lib.ssc_mpc_score(ctypes.byref(st), _ffi.ptr(S), _ffi.ptr(fb["scores"]), _ffi.ptr(fb["best"]),
-                                         _ffi.ptr(fb["best_score"]), _ffi.ptr(fb["ws"]), fb["ws"].numel(), _stream()))
-            _ffi.check(lib.ssc_mpc_rollout_step(
-                ctypes.byref(env.params), ctypes.byref(st), ctypes.byref(nav), _ffi.ptr(fb["A"]), _ffi.ptr(fb["best"]),
+                                         _ffi.ptr(fb["best_score"]), _ffi.ptr(fb["ws"]), fb["ws"].numel(), _ffi.stream()))
+            _ffi.check(step_fn(
+                ctypes.byref(env.params), ctypes.byref(st), ctypes.byref(nav), *lead, _ffi.ptr(fb["A"]), _ffi.ptr(fb["best"]),
                 float(self.noise_amount), self.seed, self.problem_id0, ctypes.byref(rs),
                 ctypes.byref(log_s) if log_s is not None else None,
                 ctypes.byref(ring_s) if ring_s is not None else None,
                 _ffi.ptr(env.stats), env._seed, env.env_id0, _ffi.ptr(fb["t"]), _ffi.ptr(fb["k"]), _ffi.ptr(fb["ticket"]),
-                _ffi.ptr(fb["plan"]), _stream()))
+                _ffi.ptr(fb["plan"]), _ffi.stream()))

@@ -64,9 +64,6 @@ class ObsRms:
         nbytes = int(self.lib.ssc_obs_rms_update_workspace_bytes(self.obs_dim))
         self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def update_chunk(self, chunk, k0=0, K=None):
         """RunningMeanStd.update with the obs0 of steps [k0, K) of a TransitionChunk (every env)."""
         K = chunk.K if K is None else int(K)
@@ -74,14 +71,14 @@ class ObsRms:
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.ssc_obs_rms_update(self.obs_dim, ctypes.byref(log), int(k0), K, chunk.N,
                                                    _ffi.ptr(self.block), _ffi.ptr(self._ws), self._ws.numel(),
-                                                   self._stream()))
+                                                   _ffi.stream(self.device)))
 
     def update_rows(self, x):
         """RunningMeanStd.update with the rows of x [m, obs_dim] (a host array or a tensor)."""
         t = torch.as_tensor(x, dtype=torch.float32, device=self.device).reshape(-1, self.obs_dim).contiguous()
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.ssc_obs_rms_update_rows(self.obs_dim, t.shape[0], _ffi.ptr(t), _ffi.ptr(self.block),
-                                                        _ffi.ptr(self._ws), self._ws.numel(), self._stream()))
+                                                        _ffi.ptr(self._ws), self._ws.numel(), _ffi.stream(self.device)))
 
     def mean_std(self):
         """Host fp32 (mean, std): the values the kernels derive from the block."""

@@ -288,9 +288,6 @@ class DeviceReplayBuffer:
 
     size = __len__
 
-    def _stream(self):
-        return self._ctypes.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
-
     def ring_struct(self):
         r = self._ffi.ReplayRing()
         r.s, r.a, r.r, r.t, r.s2 = (x.data_ptr() for x in (self.s, self.a, self.r, self.t, self.s2))
@@ -321,7 +318,7 @@ class DeviceReplayBuffer:
         ring = self.ring_struct()
         with self._torch.cuda.device(self.device):
             self._ffi.check(self.lib.ssc_replay_append(self._ctypes.byref(ring), self._ctypes.byref(log), K, chunk.N,
-                                                       self.count, float(reward_scale), self._stream()))
+                                                       self.count, float(reward_scale), self._ffi.stream(self.device)))
         self.count += K * chunk.N
 
     def append_shards(self, shards, n_total, reward_scale=1.0):
@@ -340,7 +337,7 @@ class DeviceReplayBuffer:
                 log = chunk.as_struct()
                 self._ffi.check(self.lib.ssc_replay_append_shard(self._ctypes.byref(ring), self._ctypes.byref(log), K, chunk.N,
                                                                  self.count, int(n_total), int(env_off), float(reward_scale),
-                                                                 self._stream()))
+                                                                 self._ffi.stream(self.device)))
         self.count += K * int(n_total)
 
     def sample_indices(self, n_batches, batch_size):
@@ -350,7 +347,7 @@ class DeviceReplayBuffer:
         idx = self._torch.empty((n_batches, batch_size), dtype=self._torch.int32, device=self.device)
         with self._torch.cuda.device(self.device):
             self._ffi.check(self.lib.ssc_replay_sample(self.seed, self._batches_drawn, len(self), n_batches, batch_size,
-                                                       self._ffi.ptr(idx), self._stream()))
+                                                       self._ffi.ptr(idx), self._ffi.stream(self.device)))
         self._batches_drawn += n_batches
         return idx
 
@@ -399,7 +396,7 @@ class DeviceReplayBuffer:
         with torch.cuda.device(self.device):
             ffi.check(self.lib.ssc_replay_smart_start_indices(ct.byref(ring), self.count, self.n_envs, n_ss, self.seed ^ 0x5353,
                                                               self._queries, ffi.ptr(idx), ffi.ptr(n_out), ffi.ptr(ws), nb,
-                                                              self._stream()))
+                                                              self._ffi.stream(self.device)))
         self._queries += 1
         got = idx[idx >= 0].long()
         return got if got.numel() > 0 else None
@@ -414,7 +411,7 @@ class DeviceReplayBuffer:
         ring = self.ring_struct()
         with torch.cuda.device(self.device):
             ffi.check(self.lib.ssc_replay_episode_path(ct.byref(ring), self.count, self.n_envs, ffi.ptr(bi), self.max_path_len,
-                                                       ffi.ptr(self._path), ffi.ptr(self._path_len), self._stream()))
+                                                       ffi.ptr(self._path), ffi.ptr(self._path_len), self._ffi.stream(self.device)))
         rows = int(self._path_len.item())          # the ONE host read of a smart-start query: the path length
         if rows == 0:
             raise ValueError(": (   -   the episode start of this record is no longer in the ring")

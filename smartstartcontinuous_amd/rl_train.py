@@ -251,7 +251,7 @@ class DecaySchedule:
         import ctypes
         import torch
         from . import _ffi
-        self._ffi, self._ct, self._torch = _ffi, ctypes, torch
+        self._ffi, self._torch = _ffi, torch
         self.device = torch.device(device)
         self.per_generation = float(per_generation)
         self.n = len(entries)
@@ -269,11 +269,11 @@ class DecaySchedule:
     def update(self, finished, finished0=0.0):
         """Enqueue the decay on the current stream; ``finished``: device fp64 view of the finished-episode counter,
         ``finished0``: what it read when the loop started."""
-        ffi, ct, torch = self._ffi, self._ct, self._torch
+        ffi, torch = self._ffi, self._torch
         with torch.cuda.device(self.device):
             ffi.check(ffi.lib().ssc_decay_schedule(ffi.ptr(finished), float(finished0), self.per_generation, self.n, self._factor, self._floor,
                                                    ffi.ptr(self.state), self._out_ptrs,
-                                                   ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                   ffi.stream(self.device)))
 
     def read(self):
         """(generations applied, [current values]) -- a device -> host read (synchronises the current stream)."""
@@ -306,6 +306,29 @@ def update_obs_rms(agent, chunk, last_steps=None):
     if k <= 0:                                    # append_chunk stored nothing
         return
     rms.update_chunk(chunk, chunk.K - k, chunk.K)
+
+
+def vec_loop_buffers(env, chunk_steps, replay_capacity, ring_capacity, seed, track_episodes):
+    """What a vectorised loop keeps in HBM -> (episode ring, transition chunk, device replay ring)."""
+    from .replay_buffer import DeviceReplayBuffer
+    from .vec_env import EpisodeRing, TransitionChunk
+    replay = DeviceReplayBuffer(replay_capacity, env.obs_dim, 1, env.device, seed=seed, track_episodes=track_episodes,
+                                n_envs=env.n, max_path_len=(env.spec.max_episode_steps or 1000) + 1)
+    return EpisodeRing(ring_capacity, env.device), TransitionChunk(env.obs_dim, chunk_steps, env.n, env.device), replay
+
+
+def adapt_and_perturb(agent, replay, dst=None, cycle=True):
+    """The next chunk's acting copy ``dst`` (default ``agent.perturbed_actor_flat``): the stddev adapted on the obs0 of ONE
+    fresh replay batch (ddpg_editted.py:360-376), then actor + noise of the adapted stddev -- in one launch
+    (``agent.param_noise_cycle``) when ``cycle``, else ``adapt_param_noise`` + a perturbation.  Only the perturbation
+    while the ring holds fewer than ``batch_size`` records.  Stream-ordered, no host read."""
+    if len(replay) >= agent.batch_size:
+        obs0 = replay.s.index_select(0, replay.sample_indices(1, agent.batch_size)[0].long())
+        if cycle:
+            agent.param_noise_cycle(obs0, dst=dst)
+            return
+        agent.adapt_param_noise(obs0)
+    agent.perturbed_generation = agent._perturb(agent.perturbed_actor_flat if dst is None else dst)
 
 
 def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
@@ -399,13 +422,8 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         raise NotImplementedError("rl_train_vec_ddpg: overlap=True with param_noise needs an agent with param_noise_cycle "
                                   "(the one-launch adapt and re-perturb)")
     import torch
-    from .replay_buffer import DeviceReplayBuffer
-    from .vec_env import EpisodeRing, TransitionChunk
     summary = Summary("vec_ddpg_" + env.spec.id)
-    ring = EpisodeRing(ring_capacity, env.device)
-    chunk = TransitionChunk(env.obs_dim, chunk_steps, env.n, env.device)
-    replay = DeviceReplayBuffer(replay_capacity, env.obs_dim, 1, env.device, seed=seed, track_episodes=track_episodes,
-                                n_envs=env.n, max_path_len=(env.spec.max_episode_steps or 1000) + 1)
+    ring, chunk, replay = vec_loop_buffers(env, chunk_steps, replay_capacity, ring_capacity, seed, track_episodes)
     losses = []
     if drain_every is None:
         drain_every = default_drain_every(ring_capacity, env.n, chunk_steps)
@@ -475,7 +493,9 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             summary.eval_chunks = [(r + 1) * eval_every - 1 for r in range(host.shape[0])]
 
     if overlap:
-        from .vec_env import ActorPolicy
+        import dataclasses
+        from .agents import views_like
+        from .vec_env import TransitionChunk
         cur = torch.cuda.current_stream(env.device)
         with torch.cuda.device(env.device):              # env.device need not be the process's current device
             act = torch.cuda.Stream(env.device)          # the rollouts' stream
@@ -488,15 +508,8 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         snap_ready = torch.cuda.Event()
         live = agent.as_policy(device_epsilon=True)
 
-        def policy_over(flat):
-            views, o = {}, 0
-            for k, v in agent.weights.items():           # same order and shapes as the flat array (flatten_params)
-                views[k] = flat[o:o + v.numel()].view(v.shape)
-                o += v.numel()
-            return env.policy_desc(ActorPolicy(views, last_layer_tanh=live.last_layer_tanh, precision=live.precision,
-                                               ou_mu=live.ou_mu, ou_sigma=live.ou_sigma, ou_theta=live.ou_theta,
-                                               ou_dt=live.ou_dt, obs_clip=live.obs_clip, d_ou_epsilon=agent.d_epsilon,
-                                               d_obs_rms=rms_snap))
+        def policy_over(flat):                           # the live policy over another flat array and the statistics snapshot
+            return env.policy_desc(dataclasses.replace(live, weights=views_like(flat, agent.weights), d_obs_rms=rms_snap))
 
         if param_noise:                                  # rollout i acts with perturbed copy i & 1
             acting = [agent.perturbed_actor_flat, torch.empty_like(agent.perturbed_actor_flat)]
@@ -534,11 +547,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
             if l is not None:
                 losses.append(l)
             if param_noise:                              # copy b ^ 1 = actor as of the end of train i + noise of the adapted stddev
-                if len(replay) >= agent.batch_size:
-                    rows = replay.sample_indices(1, agent.batch_size)[0].long()
-                    agent.param_noise_cycle(replay.s.index_select(0, rows), dst=acting[b ^ 1])
-                else:
-                    agent.perturbed_generation = agent._perturb(acting[b ^ 1])
+                adapt_and_perturb(agent, replay, dst=acting[b ^ 1])
                 snap_ready.record(cur)
             log_stats(i, acting[b ^ 1] if param_noise else None)   # behind the event: rollout i + 1 does not wait for it
             log_eval(i)                                  # likewise
@@ -570,11 +579,8 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         l = agent.train_from(replay, train_iters)
         if l is not None:
             losses.append(l)
-        if param_noise:
-            if len(replay) >= agent.batch_size:                  # ddpg_editted.py:360-376 on one fresh batch's obs0
-                rows = replay.sample_indices(1, agent.batch_size)[0].long()
-                agent.adapt_param_noise(replay.s.index_select(0, rows))
-            agent.perturb_policy()                               # the next chunk's actor, with the adapted stddev
+        if param_noise:                                          # the next chunk's actor, with the adapted stddev
+            adapt_and_perturb(agent, replay, cycle=False)
         log_stats(i)
         log_eval(i)
         if on_chunk is not None:
@@ -619,14 +625,9 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
         raise NotImplementedError("rl_train_vec_smartstart: a base agent with param_noise needs param_noise_cycle "
                                   "(the one-launch adapt and re-perturb)")
     import torch
-    from .replay_buffer import DeviceReplayBuffer
-    from .vec_env import EpisodeRing, TransitionChunk
     agent = smart.agent
     summary = Summary("vec_smartstart_" + env.spec.id)
-    ring = EpisodeRing(ring_capacity, env.device)
-    chunk = TransitionChunk(env.obs_dim, chunk_steps, env.n, env.device)
-    replay = DeviceReplayBuffer(replay_capacity, env.obs_dim, 1, env.device, seed=seed, track_episodes=True,
-                                n_envs=env.n, max_path_len=(env.spec.max_episode_steps or 1000) + 1)
+    ring, chunk, replay = vec_loop_buffers(env, chunk_steps, replay_capacity, ring_capacity, seed, True)
     losses, generations = [], 0.0
     if overlap_selection:
         main = torch.cuda.current_stream(env.device)
@@ -656,11 +657,7 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
         if overlap_selection:
             learned.record(main)
         if getattr(agent, "param_noise", None) is not None:      # the next chunk's acting copy, with the adapted stddev
-            if len(replay) >= agent.batch_size:
-                rows = replay.sample_indices(1, agent.batch_size)[0].long()
-                agent.param_noise_cycle(replay.s.index_select(0, rows))
-            else:
-                agent.perturb_policy()
+            adapt_and_perturb(agent, replay)
         if l is not None:
             losses.append(l)
         if on_chunk is not None:

@@ -28,6 +28,10 @@ import dataclasses
 import torch
 import torch.distributed as dist
 
+from .agents import views_like
+
+_views_like = views_like      # the name this module had for it; agents.views_like is the one walk over the flat layout
+
 
 def shard_range(n_total, world, rank):
     """Contiguous env-id range [lo, hi) owned by ``rank`` (balanced to within one env)."""
@@ -138,7 +142,7 @@ class TransitionGather:
             ffi, ct = self._ffi, self._ct
             ffi.check(ffi.lib().ssc_pack_transitions(ct.byref(log), self.obs_dim, chunk.K, g, self.n, ffi.ptr(stats),
                                                      ffi.ptr(self.send[slot]),
-                                                     ct.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                     ffi.stream(self.device)))
             return
         obs, act, rew, obs2, done = self._views(self.send[slot])
         obs.copy_(chunk.obs[:, chunk.K - g:, :])
@@ -242,16 +246,6 @@ def broadcast_flat(flat, src=0, group=None):
     return flat
 
 
-def _views_like(flat, like):
-    """dict of views into ``flat`` with the shapes (and order) of the weight dict ``like`` (agents.flatten_params)."""
-    views, o = {}, 0
-    for k, v in like.items():
-        n = v.numel()
-        views[k] = flat[o:o + n].view(v.shape)
-        o += n
-    return views
-
-
 def rl_train_sharded_ddpg(env, agent, num_chunks, chunk_steps, rank, world, learner=0, gather_steps=None,
                           replay_capacity=1 << 20, train_iters=None, seed=0, group=None, ring_capacity=1 << 20,
                           pipelined=False, drain_every=None, on_chunk=None):
@@ -329,7 +323,7 @@ def rl_train_sharded_ddpg(env, agent, num_chunks, chunk_steps, rank, world, lear
     if pipelined:
         wbuf = [agent.actor_sync.clone(), agent.actor_sync.clone()]     # generation g lives in wbuf[g & 1]
         base = agent.as_policy()
-        pds = [env.policy_desc(dataclasses.replace(base, weights=_views_like(b[:-1], agent.weights), d_ou_epsilon=b[-1:]))
+        pds = [env.policy_desc(dataclasses.replace(base, weights=views_like(b[:-1], agent.weights), d_ou_epsilon=b[-1:]))
                for b in wbuf]                                           # the SAME policy the synchronous loop builds
         bcast_done = [None, None]
         learned = [None, None]                                          # learner stream is done with recv[slot] / wrote wbuf[slot]

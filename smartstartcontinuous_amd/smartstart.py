@@ -15,10 +15,7 @@ from . import _ffi
 from .agents import NND_MB_agent, ReplayBufferRLAgent, RLAgent
 from .numerical import volume_of_n_dimensional_hyperellipsoid
 from .replay_buffer import DeviceReplayBuffer, ReplayBuffer
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .vec_env import StepGraphs
 
 
 def kde_scott_bandwidth(data):
@@ -47,7 +44,7 @@ def kde_evaluate(data, points, whitening, norm):
     wh = (ctypes.c_float * (d * d))(*np.asarray(whitening, np.float32).reshape(-1).tolist())
     with torch.cuda.device(data.device):
         _ffi.check(_ffi.lib().ssc_kde_evaluate(d, n, _ffi.ptr(data), m, _ffi.ptr(points), wh, float(norm),
-                                               _ffi.ptr(pdf), _stream()))
+                                               _ffi.ptr(pdf), _ffi.stream()))
     return pdf
 
 
@@ -59,7 +56,7 @@ def ucb_argmax(values, pdf, buffer_len, volume, exploitation_param, exploration_
     with torch.cuda.device(values.device):
         _ffi.check(_ffi.lib().ssc_ucb_argmax(m, _ffi.ptr(values.float().contiguous()), _ffi.ptr(pdf),
                                              float(exploitation_param), float(exploration_param), float(buffer_len),
-                                             float(volume), _ffi.ptr(ucb), _ffi.ptr(best), _stream()))
+                                             float(volume), _ffi.ptr(ucb), _ffi.ptr(best), _ffi.stream()))
     return ucb, best
 
 
@@ -273,7 +270,7 @@ class VecSmartStart:
         self.kde_max_states = kde_max_states
         self.mode_log = None
         self.last_radii = None
-        self._graphs = {}
+        self._graphs = StepGraphs(keep=4)
         self.selections = 0
 
     # ------------------------------------------------------------------------- selection --
@@ -366,42 +363,41 @@ class VecSmartStart:
         a = self.agent
         return a._perturbed_desc if getattr(a, "param_noise", None) is not None else a._desc
 
+    def graph_key(self, K, chunk, ring):
+        """The navigator's key (``NavigatorBatch.graph_key``) plus everything this class's own launches bake into a captured
+        ``fused_step``: the acting actor's descriptor by value (ten pointers, dims, flags), the observation statistics
+        block, the mode / plan-pool / live-list / hand-over tensors, the mode log, the OU scalars and the action bounds.
+        tests/test_gpu_smartstart_vec.py (test_graph_keys_cover_what_the_step_launches_bake_in) lists them all and
+        replaces them one at a time: what a launch starts to use belongs here AND there."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        e, a, p = self.env, self.agent, self.pool
+        rms = getattr(a, "obs_rms", None)
+        return (K, self.nav.graph_key(e, chunk, ring), bytes(self.acting_desc()), None if rms is None else ptr(rms.block),
+                tuple(ptr(x) for x in (self.mode, p.plan_of, p.wp_len, p.pool, p.active, p.live_list, p.n_live, self.live_list,
+                                       self.n_live, self.actor_out, self.d_eps, self.d_eta, self.mode_log)), self.log_modes,
+                float(a.ou["mu"]), float(a.ou["sigma"]), float(a.ou["theta"]), float(a.decaying_ou_action_noise.dt),
+                float(e.action_space.low[0]), float(e.action_space.high[0]))
+
     def fused_step(self, chunk, ring):
         """Enqueue ONE step for every env (five launches); step index and log row are device counters."""
         from . import navigator as nav
         env, b, lib = self.env, self.nav, _ffi.lib()
         fb = b._fused_buffers(env.device)
         with torch.cuda.device(env.device):
-            _ffi.check(lib.ssc_nav_compact(env.n, _ffi.ptr(self.mode), _ffi.ptr(self.live_list), _ffi.ptr(self.n_live), _stream()))
+            _ffi.check(lib.ssc_nav_compact(env.n, _ffi.ptr(self.mode), _ffi.ptr(self.live_list), _ffi.ptr(self.n_live), _ffi.stream()))
             rms = getattr(self.agent, "obs_rms", None)
             desc = self.acting_desc()
             if rms is None:
                 _ffi.check(lib.ssc_actor_forward(ctypes.byref(desc), env.n, _ffi.ptr(fb["plan"]),
-                                                 _ffi.ptr(self.actor_out), _stream()))
+                                                 _ffi.ptr(self.actor_out), _ffi.stream()))
             else:   # normalize_observations: the kernel reads the block at launch (valid inside the captured graph)
                 _ffi.check(lib.ssc_actor_forward_rms(ctypes.byref(desc), env.n, _ffi.ptr(fb["plan"]),
-                                                     _ffi.ptr(self.actor_out), _stream(), _ffi.ptr(rms.block)))
+                                                     _ffi.ptr(self.actor_out), _ffi.stream(), _ffi.ptr(rms.block)))
         sp = nav.mpc_sampling(b.N, b.low, b.high, b.seed, b.problem_id0, 0, t_base=fb["t"], active=self.mode,
                               live_list=self.live_list, n_live=self.n_live)
         S = self.model.do_forward_sim_sampled(fb["plan"], sp, b.P * b.N, b.H, out=b._S, A_out=fb["A"])
-        st = self.pool.as_struct(b.N, b.H)
-        navs = _ffi.MpcNavState(self.pool.cur_idx.data_ptr(), b.start_idx.data_ptr(), b.actions_done.data_ptr(),
-                                b.at_goal.data_ptr(), b.give_up, b.final_steps)
-        rs = _ffi.RolloutState(env.s0.data_ptr(), env.s1.data_ptr(), env.steps.data_ptr(), env.ep_ret.data_ptr(),
-                               env.ou_x.data_ptr())
-        log_s = chunk.as_struct() if chunk is not None else None
-        ring_s = ring.as_struct() if ring is not None else None
         ss = self._step_struct(chunk.K if chunk is not None else 1)
-        with torch.cuda.device(env.device):
-            _ffi.check(lib.ssc_mpc_score(ctypes.byref(st), _ffi.ptr(S), _ffi.ptr(fb["scores"]), _ffi.ptr(fb["best"]),
-                                         _ffi.ptr(fb["best_score"]), _ffi.ptr(fb["ws"]), fb["ws"].numel(), _stream()))
-            _ffi.check(lib.ssc_smartstart_rollout_step(
-                ctypes.byref(env.params), ctypes.byref(st), ctypes.byref(navs), ctypes.byref(ss), _ffi.ptr(fb["A"]),
-                _ffi.ptr(fb["best"]), float(b.noise_amount), b.seed, b.problem_id0, ctypes.byref(rs),
-                ctypes.byref(log_s) if log_s is not None else None,
-                ctypes.byref(ring_s) if ring_s is not None else None,
-                _ffi.ptr(env.stats), env._seed, env.env_id0, _ffi.ptr(fb["t"]), _ffi.ptr(fb["k"]), _ffi.ptr(fb["ticket"]),
-                _ffi.ptr(fb["plan"]), _stream()))
+        b._score_and_step(env, chunk, ring, S, lib.ssc_smartstart_rollout_step, ctypes.byref(ss))
 
     def _state_tensors(self):
         e, b = self.env, self.nav
@@ -417,43 +413,16 @@ class VecSmartStart:
         if (out.K, out.N, out.obs_dim) != (K, env.n, env.obs_dim):
             raise ValueError("out chunk has the wrong shape")
         out.step0, out.env_id0 = env.t, env.env_id0
-        fb = b._fused_buffers(env.device)
-        fb["t"].fill_(env.t)
-        fb["k"].zero_()
-        fb["plan"].copy_(env.observe())
+        b.begin_chunk(env)
         self.d_eps.fill_(float(max(self.agent.decaying_ou_action_noise.epsilon, 0.0)))
         self.d_eta.fill_(self.eta)
-        self.model.refresh_prepared_image()
         if not graph:
             for _ in range(K):
                 self.fused_step(out, ring)
             env.t += K
             return out
-        key = (K, out.obs.data_ptr(), None if ring is None else ring.cursor.data_ptr(), self.acting_desc().W1,
-               tuple(w.data_ptr() for w in self.model.W), None if self.model._image is None else self.model._image.data_ptr(),
-               self.log_modes)
-        if key not in self._graphs:
-            snap = [x.clone() for x in self._state_tensors()]
-            ring_snap = None if ring is None else ring.cursor.clone()
-            side = torch.cuda.Stream(env.device)
-            side.wait_stream(torch.cuda.current_stream(env.device))
-            with torch.cuda.stream(side):
-                self.fused_step(out, ring)           # lazy allocations, weight image, LDS opt-ins outside the capture
-            torch.cuda.current_stream(env.device).wait_stream(side)
-            for dst, src in zip(self._state_tensors(), snap):
-                dst.copy_(src)
-            if ring is not None:
-                ring.cursor.copy_(ring_snap)
-            key = key[:5] + (None if self.model._image is None else self.model._image.data_ptr(),) + key[6:]
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.fused_step(out, ring)
-            for k_old in list(self._graphs)[:max(0, len(self._graphs) - 3)]:
-                del self._graphs[k_old]
-            self._graphs[key] = g
-        g = self._graphs[key]
-        for _ in range(K):
-            g.replay()
+        self._graphs.replay(K, env.device, lambda: self.graph_key(K, out, ring), lambda: self.fused_step(out, ring),
+                            self._state_tensors(), ring)
         env.t += K
         return out
 

@@ -27,10 +27,6 @@ RESET_T0 = (1 << 56) - 1  # RNG step index of the very first reset (oracle/ssc_o
 _MC_EDITTED = re.compile(r"^MountainCarContinuousActionX([0-9.]+)-v(\d+)$")
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def parse_env_id(env_id, power_scalar=None, max_episode_steps=None):
     """-> (kind, power_scalar, max_episode_steps, spec_id).
 
@@ -199,6 +195,41 @@ class EpisodeRing:
         return out, dropped, self._drained
 
 
+class StepGraphs:
+    """"Capture one step, replay it K times": the HIP graphs of a rollout whose step is a chain of launches driven by
+    device counters (MpcPolicy, VecSmartStart), the newest ``keep`` of them, by the key of what a capture bakes in."""
+
+    def __init__(self, keep):
+        self.keep, self.graphs = int(keep), {}
+
+    def replay(self, K, device, key_fn, step_fn, state, ring=None):
+        """K replays of the graph of ``step_fn()`` under ``key_fn()``, captured first if there is none.  ``state``: the
+        tensors one step advances (``ring``: its cursor too)."""
+        key = key_fn()
+        if key not in self.graphs:
+            # warm-up outside the capture (lazy allocations, the weight image, LDS opt-ins) on a side stream, then
+            # restore the state it advanced
+            state = list(state) + ([] if ring is None else [ring.cursor])
+            snap = [x.clone() for x in state]
+            side, cur = torch.cuda.Stream(device), torch.cuda.current_stream(device)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                step_fn()
+            cur.wait_stream(side)
+            for dst, src in zip(state, snap):
+                dst.copy_(src)
+            key = key_fn()            # the warm-up may have allocated the model's weight image / workspace
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                step_fn()
+            for old in list(self.graphs)[:max(0, len(self.graphs) - (self.keep - 1))]:
+                del self.graphs[old]
+            self.graphs[key] = g
+        g = self.graphs[key]
+        for _ in range(K):
+            g.replay()
+
+
 class VecEnv:
     """N independent environments on one GPU.
 
@@ -261,7 +292,7 @@ class VecEnv:
                 mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             _ffi.check(self.lib.ssc_env_reset(ctypes.byref(self.params), self.n, _ffi.ptr(mask), _ffi.ptr(self.s0),
                                               _ffi.ptr(self.s1), _ffi.ptr(self.steps), _ffi.ptr(self.ep_ret),
-                                              _ffi.ptr(self.ou_x), self._seed, self.env_id0, t, _stream()))
+                                              _ffi.ptr(self.ou_x), self._seed, self.env_id0, t, _ffi.stream()))
             if mask is None:
                 self._needs_reset = False
             return self.observe()
@@ -269,7 +300,7 @@ class VecEnv:
     def observe(self):
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.ssc_env_observe(ctypes.byref(self.params), self.n, _ffi.ptr(self.s0),
-                                                _ffi.ptr(self.s1), _ffi.ptr(self._obs), _stream()))
+                                                _ffi.ptr(self.s1), _ffi.ptr(self._obs), _ffi.stream()))
         return self._obs.t()
 
     def step(self, actions):
@@ -289,14 +320,14 @@ class VecEnv:
             if self.kind == _ffi.SSC_ENV_MOUNTAINCAR:
                 _ffi.check(self.lib.ssc_mc_step(ctypes.byref(self.params), self.n, _ffi.ptr(self.s0),
                                                 _ffi.ptr(self.s1), _ffi.ptr(a), _ffi.ptr(self._rew),
-                                                _ffi.ptr(self._done), _ffi.ptr(self.steps), _stream()))
+                                                _ffi.ptr(self._done), _ffi.ptr(self.steps), _ffi.stream()))
                 _ffi.check(self.lib.ssc_env_observe(ctypes.byref(self.params), self.n, _ffi.ptr(self.s0),
-                                                    _ffi.ptr(self.s1), _ffi.ptr(self._obs), _stream()))
+                                                    _ffi.ptr(self.s1), _ffi.ptr(self._obs), _ffi.stream()))
             else:
                 _ffi.check(self.lib.ssc_pend_step(ctypes.byref(self.params), self.n, _ffi.ptr(self.s0),
                                                   _ffi.ptr(self.s1), _ffi.ptr(a), _ffi.ptr(self._obs),
                                                   _ffi.ptr(self._rew), _ffi.ptr(self._done), _ffi.ptr(self.steps),
-                                                  _stream()))
+                                                  _ffi.stream()))
         self.t += 1
 
     def render(self, mode="human"):
@@ -323,9 +354,7 @@ class VecEnv:
         pd.kind = _ffi.SSC_POLICY_ACTOR
         a = pd.actor
         a.obs_dim, a.h1, a.h2, a.act_dim = obs_dim, h1, h2, 1
-        a.W1, a.b1, a.W2, a.b2, a.W3, a.b3 = (w[k].data_ptr() for k in ("W1", "b1", "W2", "b2", "W3", "b3"))
-        if "ln1_g" in w:                        # LayerNorm actor (models_editted.py:45-46, 50-51)
-            a.ln1_g, a.ln1_b, a.ln2_g, a.ln2_b = (w[k].data_ptr() for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b"))
+        _ffi.set_net_ptrs(a, w)
         a.last_layer_tanh = int(policy.last_layer_tanh)
         a.obs_clip = float(policy.obs_clip)
         a.precision = {"f32": _ffi.SSC_PREC_F32, "bf16_mfma": _ffi.SSC_PREC_BF16_MFMA}[policy.precision]
@@ -343,6 +372,11 @@ class VecEnv:
                 raise ValueError("d_obs_rms must be the f64 [2 * obs_dim + 1] statistics block on the env's device")
             w["_d_obs_rms"] = r
         return pd, w  # keep the tensors alive for the duration of the launch
+
+    def rollout_state(self, ou=True):
+        """The env state arrays as the kernels take them (``ou=False``: without the OU noise state)."""
+        return _ffi.RolloutState(self.s0.data_ptr(), self.s1.data_ptr(), self.steps.data_ptr(), self.ep_ret.data_ptr(),
+                                 self.ou_x.data_ptr() if ou else None)
 
     def rollout(self, K, policy=None, out=None, ring=None, log=True, policy_desc=None):
         """K fused steps for every env (ssc_rollout).  Returns the TransitionChunk (or None if
@@ -363,15 +397,14 @@ class VecEnv:
             if (chunk.K, chunk.N, chunk.obs_dim) != (K, self.n, self.obs_dim):
                 raise ValueError("out chunk has the wrong shape")
             chunk.step0, chunk.env_id0 = self.t, self.env_id0
-        st = _ffi.RolloutState(self.s0.data_ptr(), self.s1.data_ptr(), self.steps.data_ptr(),
-                               self.ep_ret.data_ptr(), self.ou_x.data_ptr())
+        st = self.rollout_state()
         log_s = chunk.as_struct() if chunk is not None else None
         ring_s = ring.as_struct() if ring is not None else None
         rms = keep.get("_d_obs_rms") if keep else None
         args = (ctypes.byref(self.params), ctypes.byref(pd), self.n, K, ctypes.byref(st),
                 ctypes.byref(log_s) if log_s is not None else None,
                 ctypes.byref(ring_s) if ring_s is not None else None,
-                _ffi.ptr(self.stats), self._seed, self.env_id0, self.t, _stream())
+                _ffi.ptr(self.stats), self._seed, self.env_id0, self.t, _ffi.stream())
         with torch.cuda.device(self.device):
             if rms is None:
                 _ffi.check(self.lib.ssc_rollout(*args))
@@ -380,7 +413,6 @@ class VecEnv:
         self.t += K
         del keep
         return chunk
-
 
     def _rollout_mpc_graph(self, K, nav, out, log, ring):
         """K steps with the MPC navigator choosing every action, each step ONE replay of a captured HIP graph
@@ -396,7 +428,7 @@ class VecEnv:
         # change): a graph dies with the object whose memory it references, and a new NavigatorBatch -- e.g. the same
         # problems with another num_control_samples -- starts with an empty cache instead of inheriting a graph through
         # a recycled id().  What can still change under a live navigator is in the key.
-        cache = nav.__dict__.setdefault("_graphs", {})
+        cache = nav.__dict__.setdefault("_graphs", StepGraphs(keep=8))   # weights / chunks come and go: the newest graphs
         default_chunks = self.__dict__.setdefault("_mpc_chunks", {})
         if log:
             # the graph bakes the log pointers in: without `out` the steps are logged into a chunk kept with the
@@ -405,53 +437,10 @@ class VecEnv:
             if (chunk.K, chunk.N, chunk.obs_dim) != (K, self.n, self.obs_dim):
                 raise ValueError("out chunk has the wrong shape")
             chunk.step0, chunk.env_id0 = self.t, self.env_id0
-        fb = nav._fused_buffers(self.device)
-        fb["t"].fill_(self.t)
-        fb["k"].zero_()
-        fb["plan"].copy_(self.observe())
-        model, pr = nav.model, nav.problems
-        model.refresh_prepared_image()
-        ptr = lambda t: None if t is None else t.data_ptr()
-
-        def make_key():
-            return (nav.P, nav.N, nav.H, self.n, self.kind, bytes(self.params), self._seed, self.env_id0,
-                    tuple(ptr(x) for x in (self.s0, self.s1, self.steps, self.ep_ret, self.ou_x, self.stats)),
-                    None if chunk is None else tuple(ptr(c) for c in (chunk.obs, chunk.act, chunk.rew, chunk.done, chunk.obs2)),
-                    None if ring is None else (ptr(ring.cursor), ptr(ring.env_id), ptr(ring.length), ptr(ring.ret), ring.capacity),
-                    model.precision, tuple(ptr(w) for w in model.W), tuple(ptr(b) for b in model.b),
-                    bytes(model.norm),   # the fp32 path takes the statistics by value: baked into the capture
-                    ptr(model._image), ptr(model._ws),
-                    tuple(ptr(x) for x in (pr.wp, pr.left, pr.wp_off, pr.radii, pr.cur_idx)), pr.theta, pr.gamma, pr.hpf, pr.per_row,
-                    tuple(ptr(x) for x in (nav._S, nav.actions_done, nav.at_goal, nav.start_idx)),
-                    tuple(ptr(fb[k]) for k in sorted(fb)), nav.noise_amount, nav.seed, nav.problem_id0, nav.give_up,
-                    nav.final_steps, tuple(nav.low.tolist()), tuple(nav.high.tolist()))
-        key = make_key()
-        if key not in cache:
-            # warm-up outside the capture (lazy allocations, the weight image, LDS opt-ins) on a side stream, then
-            # restore the state it advanced
-            snap = [x.clone() for x in (self.s0, self.s1, self.steps, self.ep_ret, self.stats, nav.problems.cur_idx,
-                                        nav.actions_done, nav.at_goal, fb["plan"], fb["t"], fb["k"])]
-            ring_snap = None if ring is None else ring.cursor.clone()
-            side = torch.cuda.Stream(self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                nav.fused_step(self, chunk, ring)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            for dst, src in zip((self.s0, self.s1, self.steps, self.ep_ret, self.stats, nav.problems.cur_idx,
-                                 nav.actions_done, nav.at_goal, fb["plan"], fb["t"], fb["k"]), snap):
-                dst.copy_(src)
-            if ring is not None:
-                ring.cursor.copy_(ring_snap)
-            key = make_key()          # the warm-up may have allocated the model's weight image / workspace
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                nav.fused_step(self, chunk, ring)
-            for k in list(cache)[:max(0, len(cache) - 7)]:     # weights / chunks come and go: keep the newest graphs
-                del cache[k]
-            cache[key] = g
-        g = cache[key]
-        for _ in range(K):
-            g.replay()
+        fb = nav.begin_chunk(self)
+        cache.replay(K, self.device, lambda: nav.graph_key(self, chunk, ring), lambda: nav.fused_step(self, chunk, ring),
+                     (self.s0, self.s1, self.steps, self.ep_ret, self.stats, nav.problems.cur_idx, nav.actions_done,
+                      nav.at_goal, fb["plan"], fb["t"], fb["k"]), ring)
         self.t += K
         if chunk is not None and out is None:
             copy = TransitionChunk(self.obs_dim, K, self.n, self.device, packed=chunk.packed)

@@ -161,7 +161,7 @@ def test_sharded_actor_learner_loop_world1_equals_vec_loop(ssc):
     finally:
         dist.destroy_process_group()
     from smartstartcontinuous_amd.replay_buffer import DeviceReplayBuffer
-    from smartstartcontinuous_amd.sharding import _views_like
+    from smartstartcontinuous_amd.agents import views_like
     env_d, agent_d = setup()
     replay_d = DeviceReplayBuffer(4096, 2, 1, env_d.device, seed=3)
     gens = {-2: agent_d.actor_flat.clone(), -1: agent_d.actor_flat.clone()}
@@ -171,7 +171,7 @@ def test_sharded_actor_learner_loop_world1_equals_vec_loop(ssc):
     ring_d, finished = EpisodeRing(1 << 16, env_d.device), 0.0
     for j in range(5):
         pol = agent_d.as_policy()
-        pol.weights = _views_like(gens[j - 2], agent_d.weights)
+        pol.weights = views_like(gens[j - 2], agent_d.weights)
         pol.ou_epsilon = float(eps_gen[j - 2])          # epsilon is part of the generation (rides in the broadcast)
         chunk = env_d.rollout(48, pol, ring=ring_d)
         tail = ssc.TransitionChunk.from_columns(chunk.obs[:, -8:], chunk.act[-8:], chunk.rew[-8:], chunk.obs2[:, -8:], chunk.done[-8:])
@@ -205,7 +205,8 @@ def test_sharded_pipelined_loop_clips_observations_like_the_learner(ssc):
     import torch.distributed as dist
     from smartstartcontinuous_amd.agents import DDPG_Baselines_agent
     from smartstartcontinuous_amd.replay_buffer import DeviceReplayBuffer
-    from smartstartcontinuous_amd.sharding import _views_like, rl_train_sharded_ddpg
+    from smartstartcontinuous_amd.agents import views_like
+    from smartstartcontinuous_amd.sharding import rl_train_sharded_ddpg
     from smartstartcontinuous_amd.vec_env import EpisodeRing
 
     def setup():
@@ -235,7 +236,7 @@ def test_sharded_pipelined_loop_clips_observations_like_the_learner(ssc):
         eps_gen = {-2: agent_d.decaying_ou_action_noise.epsilon, -1: agent_d.decaying_ou_action_noise.epsilon}
         ring_d, finished = EpisodeRing(1 << 16, env_d.device), 0.0
         for j in range(5):
-            pol = dataclasses.replace(agent_d.as_policy(), weights=_views_like(gens[j - 2], agent_d.weights),
+            pol = dataclasses.replace(agent_d.as_policy(), weights=views_like(gens[j - 2], agent_d.weights),
                                       ou_epsilon=float(eps_gen[j - 2]))
             if not clip:
                 pol.obs_clip = 0.0

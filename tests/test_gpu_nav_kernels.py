@@ -33,7 +33,7 @@ def _observe(nav, ps, x, idx, done, want_goal=True):
     goal = torch.full((ps.P,), 9, dtype=torch.uint8, device="cuda") if want_goal else None
     st = ps.as_struct(16, 4)
     _ffi.check(_ffi.lib().ssc_mpc_observe(ctypes.byref(st), _ffi.ptr(ns), _ffi.ptr(ps.cur_idx), _ffi.ptr(done_t), GIVE_UP,
-                                          FINAL_STEPS, _ffi.ptr(goal), nav._stream()))
+                                          FINAL_STEPS, _ffi.ptr(goal), _ffi.stream()))
     return ps.cur_idx.cpu().numpy(), done_t.cpu().numpy(), None if goal is None else goal.cpu().numpy()
 
 
@@ -119,7 +119,7 @@ def test_nav_compact(nav, n, kind):
     mode_t = torch.as_tensor(mode, device="cuda")
     lst = torch.full((n,), -5, dtype=torch.int32, device="cuda")
     count = torch.zeros(1, dtype=torch.int32, device="cuda")
-    _ffi.check(_ffi.lib().ssc_nav_compact(n, _ffi.ptr(mode_t), _ffi.ptr(lst), _ffi.ptr(count), nav._stream()))
+    _ffi.check(_ffi.lib().ssc_nav_compact(n, _ffi.ptr(mode_t), _ffi.ptr(lst), _ffi.ptr(count), _ffi.stream()))
     lst, c = lst.cpu().numpy(), int(count.cpu().numpy()[0])
     want = np.nonzero(mode)[0]
     assert c == len(want)

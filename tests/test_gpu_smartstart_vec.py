@@ -305,3 +305,129 @@ def test_rl_train_vec_smartstart_overlapped_selection(ssc):
     first = lambda pub: next(i for i, v in enumerate(pub) if v > 0)
     # sequential: plans published before chunk 2 rolls (on_chunk index 2); overlapped: selected during chunk 2, on offer from chunk 3
     assert first(a[2]) == first(seq[2]) and a[1][first(a[2])] == 0 and sum(seq[1][:first(seq[2]) + 1]) >= 0
+
+
+def test_vec_smartstart_graph_follows_set_norm(ssc):
+    """The fp32 simulation path takes the dynamics model's statistics BY VALUE: a captured step bakes them in, so they are
+    part of the graph's key.  rollout(graph=True), ``model.set_norm(other statistics)``, rollout(graph=True) again must
+    give the chunks of the same sequence step by step, bit for bit -- and a second chunk that differs from the one the
+    first statistics produce (a replay of the first capture gives exactly that one)."""
+    n, K = 64, 3
+    cols = ("obs", "act", "rew", "done", "obs2")
+
+    def run(graph, change):
+        env, agent, w, (Ws, bs, norm), smart = _setup(ssc, n, 5, 1.0, 13, N=64, H=2, chunk=K)
+        smart.pool.publish(_plans(np.random.default_rng(2), 3, 0))
+        smart.mode.fill_(1)                                  # every env navigates from the first step (plan slot 0, waypoint 0)
+        chunk = ssc.TransitionChunk(2, K, n, env.device)
+        out = []
+        for c in range(2):
+            smart.rollout(K, chunk, graph=graph)
+            torch.cuda.synchronize()
+            out.append([getattr(chunk, col).clone() for col in cols] + [smart.mode_log.clone()])
+            if change:
+                smart.model.set_norm(make_norm(np.random.default_rng(99), 2, 1))
+        return out
+    g, e, same = run(True, True), run(False, True), run(True, False)
+    for c in range(2):
+        for col, a, b in zip(cols, g[c], e[c]):
+            assert torch.equal(a, b), (c, col)
+    assert int(g[1][5].sum()) > 0                                                    # somebody navigated in chunk 2
+    assert all(torch.equal(a, b) for a, b in zip(g[0], same[0]))                      # the same run up to set_norm ...
+    assert not all(torch.equal(a, b) for a, b in zip(g[1][:5], same[1][:5]))          # ... and another one behind it
+
+
+def _item(c):
+    return hasattr(c, "__setitem__")             # list / dict / ndarray / ctypes array: c[k]; anything else: an attribute
+
+
+def _get(c, k):
+    return c[k] if _item(c) else getattr(c, k)
+
+
+def _put(c, k, v):
+    if _item(c):
+        c[k] = v
+    else:
+        setattr(c, k, v)
+
+
+def _other(v):
+    """another value of the same kind: a clone of a tensor (a new address), a tensor where there was none, another scalar"""
+    if torch.is_tensor(v):
+        return v.clone()
+    if isinstance(v, (bool, np.bool_)):
+        return not v
+    if isinstance(v, str):
+        return {"f32": "bf16_mfma"}[v]
+    return v + 1
+
+
+def _assert_key_covers(key_fn, tensors, scalars, pointers=()):
+    """``key_fn()`` changes when any ONE of ``tensors`` (container, name) is replaced by a clone (a slot holding None: by a
+    fresh tensor), any one of ``scalars`` by another value, any one of ``pointers`` (integer fields, None = NULL) by
+    another address -- and is back at the base key when the change is undone."""
+    base = key_fn()
+    assert key_fn() == base
+    for kind, slots in (("tensor", tensors), ("scalar", scalars), ("pointer", pointers)):
+        for c, k in slots:
+            old = _get(c, k)
+            if kind == "tensor" and old is None:
+                new = torch.zeros(256, dtype=torch.uint8, device="cuda")
+            elif kind == "pointer":
+                new = (old or 0) + 256
+            else:
+                new = _other(old)
+            _put(c, k, new)
+            changed = key_fn() != base
+            _put(c, k, old)
+            assert changed, (kind, type(c).__name__, k)
+            assert key_fn() == base, (kind, type(c).__name__, k)
+
+
+def _nav_slots(env, chunk, ring, b):
+    """Every tensor an MPC-policy step's launches (forward simulation, scorer, step kernel) read or write, and every scalar
+    they take by value, as (container, name): the lists ``NavigatorBatch.graph_key`` has to cover."""
+    m, pr, fb = b.model, b.problems, b._fused_buffers(env.device)
+    tensors = [(env, k) for k in ("s0", "s1", "steps", "ep_ret", "ou_x", "stats")]
+    tensors += [(chunk, k) for k in ("obs", "act", "rew", "done", "obs2")]
+    tensors += [(ring, k) for k in ("cursor", "env_id", "length", "ret")]
+    tensors += [(m.W, l) for l in range(len(m.W))] + [(m.b, l) for l in range(len(m.b))] + [(m, "_ws"), (m, "_image")]
+    tensors += [(pr, k) for k in ("wp", "left", "wp_off", "radii", "cur_idx")]
+    tensors += [(b, k) for k in ("_S", "actions_done", "at_goal", "start_idx")] + [(fb, k) for k in sorted(fb)]
+    scalars = [(env.params, name) for name, _ in env.params._fields_]
+    scalars += [(env, "_seed"), (env, "env_id0"), (env, "kind"), (env, "n"), (ring, "capacity"), (m, "precision")]
+    scalars += [(getattr(m.norm, name), 0) for name, _ in m.norm._fields_]
+    scalars += [(pr, k) for k in ("theta", "gamma", "hpf", "per_row")]
+    scalars += [(b, k) for k in ("P", "N", "H", "noise_amount", "seed", "problem_id0", "give_up", "final_steps")]
+    scalars += [(b.low, 0), (b.high, 0)]
+    return tensors, scalars
+
+
+def test_graph_keys_cover_what_the_step_launches_bake_in(ssc):
+    """A captured step bakes in the address of every tensor its launches touch and every by-value scalar: ``graph_key`` of
+    the MPC navigator and of VecSmartStart must change when any one of them does (a stale replay computes silently with
+    the old one).  The lists are HERE; a launch that starts to use something new gets a line here and in ``graph_key``."""
+    from smartstartcontinuous_amd import navigator as nav
+    from smartstartcontinuous_amd.obs_rms import ObsRms
+    n, K = 64, 3
+    env, agent, w, (Ws, bs, norm), smart = _setup(ssc, n, 5, 1.0, 13, N=64, H=2, chunk=K)
+    chunk, ring = ssc.TransitionChunk(2, K, n, env.device), ssc.EpisodeRing(256, "cuda")
+    # the MPC policy's navigator: one problem per env
+    wps, lefts, radii = (list(x) for x in zip(*(_plans(np.random.default_rng(2), 1, 0)[0] for _ in range(n))))
+    batch = nav.NavigatorBatch(smart.model, nav.MpcProblemSet(wps, lefts, radii, [0] * n), num_control_samples=64, horizon=2, seed=3)
+    _assert_key_covers(lambda: batch.graph_key(env, chunk, ring), *_nav_slots(env, chunk, ring, batch))
+    assert batch.graph_key(env, None, None) != batch.graph_key(env, chunk, None) != batch.graph_key(env, chunk, ring)
+    # VecSmartStart: the navigator's lists over the plan pool, plus what its own launches (compaction, actor forward, the
+    # SmartStart step kernel) bake in
+    agent.obs_rms = ObsRms(2, env.device)
+    tensors, scalars = _nav_slots(env, chunk, ring, smart.nav)
+    pool, desc = smart.pool, smart.acting_desc()
+    tensors += [(pool, k) for k in ("plan_of", "wp_len", "pool", "active", "live_list", "n_live")] + [(agent.obs_rms, "block")]
+    tensors += [(smart, k) for k in ("mode", "live_list", "n_live", "actor_out", "d_eps", "d_eta", "mode_log")]
+    scalars += [(desc, k) for k in ("obs_dim", "h1", "h2", "act_dim", "last_layer_tanh", "precision", "obs_clip")]
+    scalars += [(smart, "log_modes"), (agent.ou, "mu"), (agent.ou, "sigma"), (agent.ou, "theta"),
+                (agent.decaying_ou_action_noise, "dt"), (env.action_space.low, 0), (env.action_space.high, 0)]
+    pointers = [(desc, k) for k in ("W1", "b1", "W2", "b2", "W3", "b3", "ln1_g", "ln1_b", "ln2_g", "ln2_b")]
+    _assert_key_covers(lambda: smart.graph_key(K, chunk, ring), tensors, scalars, pointers)
+    assert smart.graph_key(K, chunk, ring) != smart.graph_key(K + 1, chunk, ring)

@@ -393,3 +393,36 @@ def test_vectorised_activity_solver_equals_the_reference_loop():
             acts = acts[np.lexsort((acts[:, 1], acts[:, 0]))]
         for sub_extra in (0, 1):
             assert N.length_weighted_activities_solver(acts, sub_extra) == N._length_weighted_activities_loop(acts.tolist(), sub_extra)
+
+
+@pytest.mark.parametrize("layer_norm", [False, True])
+def test_views_like_is_the_flat_parameter_layout(layer_norm):
+    """agents.views_like -- the one walk over [W1|b1|(beta1|gamma1)|W2|b2|(beta2|gamma2)|W3|b3] -- returns views that SHARE
+    the flat array's storage, in ``param_keys`` order whatever the order of the dict it is given, and is what
+    ``flatten_params`` hands out."""
+    import torch
+    from smartstartcontinuous_amd import agents as A
+    w = A.init_actor_weights(3, 5, 4, 2, torch.Generator().manual_seed(1))
+    if layer_norm:
+        w = A.with_layer_norm(w)                 # (appends the ln* entries BEHIND W3 / b3: not the layout's order)
+    keys = A.param_keys(w)
+    assert keys == (A.LN_PARAM_KEYS if layer_norm else A.PARAM_KEYS)
+    flat, views = A.flatten_params(w, "cpu", extra=1)
+    n = sum(v.numel() for v in w.values())
+    assert flat.numel() == n + 1 and float(flat[-1]) == 0.0
+    other = torch.arange(n, dtype=torch.float32)
+    got = A.views_like(other, dict(reversed(list(w.items()))))
+    assert tuple(got) == tuple(views) == keys
+    o = 0
+    for k in keys:
+        assert got[k].shape == views[k].shape == w[k].shape
+        assert torch.equal(views[k], w[k].float())                                   # flatten_params' views hold the weights
+        assert views[k].data_ptr() == flat.data_ptr() + 4 * o                         # ... inside the flat array, in order
+        assert got[k].data_ptr() == other.data_ptr() + 4 * o
+        assert torch.equal(got[k].reshape(-1), other[o:o + w[k].numel()])
+        o += w[k].numel()
+    got["W2"].fill_(-7.0)                                                             # shared storage: a write shows through
+    a = w["W1"].numel() + w["b1"].numel() + (2 * w["ln1_b"].numel() if layer_norm else 0)
+    assert bool((other[a:a + w["W2"].numel()] == -7.0).all()) and float(other[a - 1]) == a - 1
+    same = A.views_like(flat[:-1], w)
+    assert all(same[k].data_ptr() == views[k].data_ptr() and torch.equal(same[k], views[k]) for k in keys)
