@@ -1,14 +1,13 @@
 // ddpg_device.h -- pieces shared by the DDPG learner kernels (ddpg_train.hip: single-workgroup step interpreter;
-// ddpg_train_fixed.hip: the shipped 64-32 shape compiled straight-line; ddpg_train_wide.hip: any shape, multi-workgroup).
+// ddpg_train_fixed.hip: the shipped 64-32 shape compiled straight-line; ddpg_train_wide.hip: any shape, multi-workgroup):
+// the fp32 MFMA, MpiAdam on one element (moments, the two spellings of the step, the bias-correction clock), and the
+// launchers ddpg_train.hip dispatches to.  The flat parameter layout and the dispatch itself are ddpg_layout.h.
 #pragma once
 
+#include "ddpg_layout.h"
 #include "ssc_device.h"
 
 namespace ssc {
-
-constexpr int kB = 64;       // batch size = lanes of a wave
-constexpr int kP = kB + 4;   // padded LDS row: 16-B aligned rows (float4 access over 4 samples); a stride of
-                             // 68 dwords keeps both ds_read_b128 column gathers and ds_write_b128 conflict-free
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f32x4m __attribute__((ext_vector_type(4)));
@@ -34,14 +33,53 @@ struct AdamCfg {
     float a, beta1, beta2, eps;   // a = stepsize * sqrt(1 - b2^t) / (1 - b1^t) with t already incremented
 };
 
-// ddpg_train_fixed.hip
-bool ddpg_fixed_shape(const ssc_ddpg_desc *d);
+// MpiAdam.update on one element (baselines common/mpi_adam.py [third-party], ddpg_editted.py:326-327): the moments ...
+__device__ __forceinline__ void adam_moments(float &m, float &v, float g, const AdamCfg &c) {
+    m = c.beta1 * m + (1.0f - c.beta1) * g;
+    v = c.beta2 * v + (1.0f - c.beta2) * (g * g);
+}
+// ... and the step added to theta, in two spellings ON PURPOSE.  The single-workgroup kernels (step interpreter, fixed
+// 64-32) take the 1-ulp sqrt / rcp instructions: a 1e-7 relative wobble of a 1e-3-sized step, and no division sequence
+// on their critical path.  The multi-workgroup apply pass (ddpg_wide_apply_kernel, which also finishes the tiled fixed
+// kernel and Pop-Art) is one element per thread with nothing to hide and keeps IEEE sqrtf and division.  Each learner is
+// bit-for-bit reproducible in its own spelling; do not merge them.
+__device__ __forceinline__ float adam_step_fast(float m, float v, const AdamCfg &c) {
+    return (-c.a) * m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) + c.eps);
+}
+__device__ __forceinline__ float adam_step_ieee(float m, float v, const AdamCfg &c) { return (-c.a) * m / (sqrtf(v) + c.eps); }
+
+// MpiAdam's bias-corrected step size in f64 (1 - 0.999^t loses 5 digits in fp32); b1t, b2t = beta1^t, beta2^t
+__device__ __forceinline__ AdamCfg adam_cfg(double lr, double b1t, double b2t, const ssc_ddpg_desc &d) {
+    return AdamCfg{(float)(lr * sqrt(1.0 - b2t) / (1.0 - b1t)), d.beta1, d.beta2, d.epsilon};
+}
+
+// The step counters of the two optimisers and their running beta powers over a launch of several iterations: one ipow
+// per launch, then one multiplication per iteration -- the per-iteration ipow + sqrt + divisions sat on the critical path
+// (3.6 k cycles with every other thread waiting at the barrier).  The wide apply pass is one launch per iteration and
+// calls ipow + adam_cfg itself.
+struct AdamClock {
+    int tA, tC;
+    double b1a, b2a, b1c, b2c;
+    // counters = false: a launch that only produces gradients (the tiled fixed kernel) does not read adam_t
+    __device__ __forceinline__ void init(const ssc_ddpg_desc &d, bool counters = true) {
+        tA = counters ? d.adam_t[0] : 0; tC = counters ? d.adam_t[1] : 0;
+        b1a = ipow((double)d.beta1, tA); b2a = ipow((double)d.beta2, tA);
+        b1c = ipow((double)d.beta1, tC); b2c = ipow((double)d.beta2, tC);
+    }
+    __device__ __forceinline__ void tick(const ssc_ddpg_desc &d) {
+        ++tA; ++tC;
+        b1a *= (double)d.beta1; b2a *= (double)d.beta2; b1c *= (double)d.beta1; b2c *= (double)d.beta2;
+    }
+    __device__ __forceinline__ AdamCfg cfg_actor(const ssc_ddpg_desc &d) const { return adam_cfg((double)d.actor_lr, b1a, b2a, d); }
+    __device__ __forceinline__ AdamCfg cfg_critic(const ssc_ddpg_desc &d) const { return adam_cfg((double)d.critic_lr, b1c, b2c, d); }
+};
+
+// ddpg_train_fixed.hip (ddpg_fixed_shape / ddpg_fixed_tiled_shape: ddpg_layout.h)
 int ddpg_train_fixed(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                      float *d_losses, hipStream_t stream, const double *d_rms);
 
 // the shipped shape at batches of 128, 192, ... (multiples of 64): the straight-line kernel on one 64-row tile per workgroup
 // (gradients only), then the multi-workgroup apply pass of ddpg_train_wide.hip
-bool ddpg_fixed_tiled_shape(const ssc_ddpg_desc *d);
 int ddpg_train_fixed_tiled(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                            float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms);
 

@@ -16,6 +16,7 @@
 //     (forward) or input rows (backward) are dealt to the 4 waves in groups of 4, and a weight is one
 //     broadcast LDS read -- a float4 of 4 consecutive units where the row length allows.
 // fp32, plain FMA chains in k order; MpiAdam's bias-corrected step size is computed in f64.
+#include "actor_device.h"
 #include "ddpg_device.h"
 #include "ssc_host.h"
 #include <cstdlib>
@@ -311,12 +312,12 @@ __device__ __forceinline__ void dense_bwd_mfma(const float *W, int out, int i0, 
 // MpiAdam.update (baselines common/mpi_adam.py [third-party], ddpg_editted.py:326-327): theta in LDS, moments in
 // global memory, same index.
 __device__ __forceinline__ void adam_apply(float *theta, float *m, float *v, int idx, float g, const AdamCfg &c) {
-    const float mi = c.beta1 * m[idx] + (1.0f - c.beta1) * g;
-    const float vi = c.beta2 * v[idx] + (1.0f - c.beta2) * (g * g);
+    float mi = m[idx], vi = v[idx];
+    adam_moments(mi, vi, g, c);
     m[idx] = mi;
     v[idx] = vi;
-    theta[idx] += (-c.a) * mi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vi) + c.eps);   // 1-ulp sqrt / rcp: a 1e-7 relative
-}                                                                                            // wobble of a 1e-3-sized step
+    theta[idx] += adam_step_fast(mi, vi, c);
+}
 
 // dW[i][j] = sum_b X[i][b] dZ[j][b]; db[j] = sum_b dZ[j][b]; applied straight into Adam.
 // (Fetching the moments of 4 elements ahead of their dot products was measured 2x SLOWER: the pass is bound by
@@ -347,11 +348,10 @@ __device__ __forceinline__ void weight_grad_adam(const float *X, const float *dZ
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int idx = offW + (ib * 16 + 4 * kg + r) * out + jb * 16 + cc;
-                const float mi = c.beta1 * m0[r] + (1.0f - c.beta1) * acc[r];
-                const float vi = c.beta2 * v0[r] + (1.0f - c.beta2) * (acc[r] * acc[r]);
-                m[idx] = mi;
-                v[idx] = vi;
-                theta[idx] += (-c.a) * mi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vi) + c.eps);
+                adam_moments(m0[r], v0[r], acc[r], c);
+                m[idx] = m0[r];
+                v[idx] = v0[r];
+                theta[idx] += adam_step_fast(m0[r], v0[r], c);
             }
         }
     }
@@ -396,13 +396,9 @@ __global__ __launch_bounds__(kTrainThreads) void ddpg_train_kernel(TrainArgs g) 
         }
     }
     __syncthreads();
-    int tA = d.adam_t[0], tC = d.adam_t[1];
+    AdamClock clk;
+    clk.init(d);
     float closs = 0.0f;
-    // running beta powers for MpiAdam's bias correction, in f64 (1 - 0.999^t loses 5 digits in fp32): one ipow per
-    // launch, then one multiplication per iteration -- the per-iteration ipow + sqrt + divisions sat on the critical
-    // path (3.6 k cycles with every other thread waiting at the barrier)
-    double b1a = ipow((double)d.beta1, tA), b2a = ipow((double)d.beta2, tA);
-    double b1c = ipow((double)d.beta1, tC), b2c = ipow((double)d.beta2, tC);
     // (requesting the batch rows of iteration it + 1 in the middle of iteration it and parking them in registers was
     // tried: hipcc drains every outstanding load in front of the next __syncthreads(), so the round trips only moved)
     float pf_s[SSC_MAX_STATE], pf_s2[SSC_MAX_STATE], pf_a[SSC_MAX_ACT], pf_r = 0.0f, pf_t = 0.0f;
@@ -444,11 +440,10 @@ __global__ __launch_bounds__(kTrainThreads) void ddpg_train_kernel(TrainArgs g) 
             float *Z = lds + st.z;
             switch (st.kind) {
             case ST_GATHER:   // ReplayBuffer.sample_batch rows
-                ++tA; ++tC;
-                b1a *= (double)d.beta1; b2a *= (double)d.beta2; b1c *= (double)d.beta1; b2c *= (double)d.beta2;
+                clk.tick(d);
                 if (tid == kB) {   // a lane that has nothing to gather: the MpiAdam step sizes of this iteration
-                    cfg_s[0] = AdamCfg{(float)((double)d.actor_lr * sqrt(1.0 - b2a) / (1.0 - b1a)), d.beta1, d.beta2, d.epsilon};
-                    cfg_s[1] = AdamCfg{(float)((double)d.critic_lr * sqrt(1.0 - b2c) / (1.0 - b1c)), d.beta1, d.beta2, d.epsilon};
+                    cfg_s[0] = clk.cfg_actor(d);
+                    cfg_s[1] = clk.cfg_critic(d);
                 }
                 if (tid < kB) {
                     fetch_rows(it);
@@ -456,8 +451,8 @@ __global__ __launch_bounds__(kTrainThreads) void ddpg_train_kernel(TrainArgs g) 
 #pragma unroll
                     for (int c = 0; c < SSC_MAX_STATE; ++c)
                         if (c < d.obs_dim) {   // obs0 / obs1 enter every network clipped (ddpg_editted.py:106-109)
-                            S[c * kP + tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s[c], -d.obs_clip), d.obs_clip) : pf_s[c];
-                            S2[c * kP + tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s2[c], -d.obs_clip), d.obs_clip) : pf_s2[c];
+                            S[c * kP + tid] = clip_obs(pf_s[c], d.obs_clip);
+                            S2[c * kP + tid] = clip_obs(pf_s2[c], d.obs_clip);
                         }
 #pragma unroll
                     for (int c = 0; c < SSC_MAX_ACT; ++c)
@@ -592,22 +587,10 @@ __global__ __launch_bounds__(kTrainThreads) void ddpg_train_kernel(TrainArgs g) 
             gv[st.w + e] = lds[st.m_lds + cnt + e];
         }
     }
-    if (tid == 0) { d.adam_t[0] = tA; d.adam_t[1] = tC; }
+    if (tid == 0) { d.adam_t[0] = clk.tA; d.adam_t[1] = clk.tC; }
 }
 
-// ---- host: LDS carve and the step list of one iteration -----------------------------------------------------------
-struct NetDims {
-    int in, h1, h2, out;     // actor: obs -> h1 -> h2 -> act ; critic: obs -> h1 (+act) -> h2 -> 1
-    int extra;               // rows concatenated to the first hidden layer (critic: act_dim, actor: 0)
-    int oW1() const { return 0; }
-    int ob1() const { return in * h1; }
-    int oW2() const { return ob1() + h1; }
-    int ob2() const { return oW2() + (h1 + extra) * h2; }
-    int oW3() const { return ob2() + h2; }
-    int ob3() const { return oW3() + h2 * out; }
-    int total() const { return ob3() + out; }
-};
-
+// ---- host: the step list of one iteration (the LDS carve it addresses: InterpCarve, ddpg_layout.h) -------------------
 struct StepList {
     TrainArgs &g;
     bool overflow = false;
@@ -619,7 +602,7 @@ struct StepList {
         s.kind = (int16_t)kind; s.barrier = barrier ? 1 : 0; s.tail_from = 0x7fff; s.m_lds = -1;
         return s;
     }
-    void fwd(int theta, const NetDims &n, int layer, int x, int z, int act, bool barrier, int xtail = -1, int tail_from = 0x7fff) {
+    void fwd(int theta, const DdpgNet &n, int layer, int x, int z, int act, bool barrier, int xtail = -1, int tail_from = 0x7fff) {
         Step &s = add(ST_FWD, barrier);
         s.w = theta + (layer == 1 ? n.oW1() : layer == 2 ? n.oW2() : n.oW3());
         s.b = theta + (layer == 1 ? n.ob1() : layer == 2 ? n.ob2() : n.ob3());
@@ -634,36 +617,139 @@ struct StepList {
         s.w = theta_w; s.out = (int16_t)out; s.i0 = (int16_t)i0; s.i1 = (int16_t)i1; s.x = dz; s.z = dx;
         s.xtail = a_rows; s.act = (int16_t)act;
     }
-    void deriv(int a, int dlt, int rows, int act, bool barrier) {
-        Step &s = add(ST_DERIV, barrier);
-        s.x = a; s.z = dlt; s.out = (int16_t)rows; s.act = (int16_t)act;
-    }
-    void wgrad(int net, int offW, int offb, int in, int out, int x, int dz, bool barrier, int xtail = -1, int tail_from = 0x7fff) {
+    void wgrad(int net, int offW, int offb, int in, int out, int x, int dz, bool barrier) {
         Step &s = add(ST_WGRAD, barrier);
         s.net = (int16_t)net; s.w = offW; s.b = offb; s.in = (int16_t)in; s.out = (int16_t)out; s.x = x; s.z = dz;
-        s.xtail = xtail >= 0 ? xtail : x; s.tail_from = (int16_t)tail_from;
+        s.xtail = x; s.tail_from = 0x7fff;
     }
 };
+
+// The single-workgroup step interpreter on a descriptor whose carve fits (ddpg_learner_path); arguments already validated.
+static int ddpg_train_interp(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
+                             float *d_losses, hipStream_t stream) {
+    const DdpgNets nets = ddpg_nets(d);   // (no LayerNorm here: ln = 0)
+    const DdpgNet &A = nets.A, &C = nets.C;
+    const InterpCarve o = ddpg_interp_carve(d);
+    const int act2 = d->last_layer_tanh ? ACT_TANH : ACT_RELU;
+    TrainArgs g{};
+    g.d = *d; g.rp = *rp; g.batch_idx = d_batch_idx; g.n_iters = n_iters; g.losses = d_losses;
+    g.off_S = o.S; g.off_S2 = o.S2; g.off_RT = o.RT; g.off_X2act = o.X2 + C.h1 * kP;
+    g.n_actor = A.total(); g.n_critic = C.total();
+    g.off_theta[0] = o.TA; g.off_theta[1] = o.TC; g.off_theta[2] = o.TTA; g.off_theta[3] = o.TTC;
+    StepList L(g);
+    L.add(ST_GATHER, true);
+    // target_Q = r + (1 - terminal) * gamma * Q'(s2, pi'(s2))      (ddpg_editted.py:132-133)
+    L.fwd(o.TTA, A, 1, o.S2, o.DZ1A, ACT_RELU, false);
+    L.fwd(o.TTC, C, 1, o.S2, o.X2B, ACT_RELU, true);
+    L.fwd(o.TTA, A, 2, o.DZ1A, o.DZ2A, act2, true);
+    L.fwd(o.TTA, A, 3, o.DZ2A, o.X2B + C.h1 * kP, ACT_TANH, true);
+    L.fwd(o.TTC, C, 2, o.X2B, o.CB2, act2, true);
+    L.fwd(o.TTC, C, 3, o.CB2, o.DZB2, ACT_NONE, true);
+    g.steps[g.n_steps - 1].i0 = 1;                              // ... + the target_Q arithmetic on the row (post-op 1)
+    // critic on (s, a) and actor on s                                (:181, :127)
+    L.fwd(o.TC, C, 1, o.S, o.X2, ACT_RELU, false);
+    L.fwd(o.TA, A, 1, o.S, o.U1, ACT_RELU, true);
+    L.fwd(o.TC, C, 2, o.X2, o.CA2, act2, false);
+    L.fwd(o.TA, A, 2, o.U1, o.U2, act2, true);
+    L.fwd(o.TC, C, 3, o.CA2, o.DQ, ACT_NONE, false);
+    g.steps[g.n_steps - 1].i0 = 2;                              // ... + critic loss, DQ becomes d loss / d q (post-op 2)
+    L.fwd(o.TA, A, 3, o.U2, o.PI, ACT_TANH, true);
+    // critic backward: dz2 = (W3 dq) * act'(z2)
+    L.bwd(o.TC + C.oW3(), 1, 0, C.h2, o.DQ, o.DZ2, o.CA2, act2, false);
+    // critic forward on (s, pi(s)) for the actor loss: the same relu(layer 1) rows, the action rows are pi(s)
+    L.fwd(o.TC, C, 2, o.X2, o.CB2, act2, true, o.PI, C.h1);
+    L.bwd(o.TC + C.oW2(), C.h2, 0, C.h1, o.DZ2, o.DZ1, o.X2, ACT_RELU, false);   // ... * relu'(layer 1)
+    L.fwd(o.TC, C, 3, o.CB2, o.DZ3A, ACT_NONE, true);       // q(s, pi) -> DZ3A row 0, then
+    g.steps[g.n_steps - 1].i0 = 3;                          // actor loss, the row becomes dq of -mean Q (post-op 3)
+    L.bwd(o.TC + C.oW3(), 1, 0, C.h2, o.DZ3A, o.DZB2, o.CB2, act2, true);
+    // d(-mean Q)/d(action) = rows h1.. of W2 dzb2 (through the output tanh), then back through the actor
+    L.bwd(o.TC + C.oW2(), C.h2, C.h1, C.h1 + d->act_dim, o.DZB2, o.DZ3A, o.PI, ACT_TANH, true);
+    L.bwd(o.TA + A.oW3(), A.out, 0, A.h2, o.DZ3A, o.DZ2A, o.U2, act2, true);
+    L.bwd(o.TA + A.oW2(), A.h2, 0, A.h1, o.DZ2A, o.DZ1A, o.U1, ACT_RELU, false);
+    L.add(ST_LOSSES, true);                                  // every read of the old parameters is done after this barrier
+    L.wgrad(1, C.oW1(), C.ob1(), C.in, C.h1, o.S, o.DZ1, false);
+    L.wgrad(1, C.oW2(), C.ob2(), C.h1 + d->act_dim, C.h2, o.X2, o.DZ2, false);
+    L.wgrad(1, C.oW3(), C.ob3(), C.h2, 1, o.CA2, o.DQ, false);
+    L.wgrad(0, A.oW1(), A.ob1(), A.in, A.h1, o.S, o.DZ1A, false);
+    L.wgrad(0, A.oW2(), A.ob2(), A.h1, A.h2, o.U1, o.DZ2A, false);
+    L.wgrad(0, A.oW3(), A.ob3(), A.h2, A.out, o.U2, o.DZ3A, true);
+    L.add(ST_TUPDATE, true);
+    if (L.overflow) return set_error(SSC_EINVAL, "ssc_ddpg_train: step list overflow");
+    // Adam moments of the small layers move into what is left of the LDS (smallest layers first)
+    int p = o.floats, free_floats = kInterpLdsFloats - p;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int si = 0; si < g.n_steps; ++si) {
+            Step &st = g.steps[si];
+            if (st.kind != ST_WGRAD || st.m_lds >= 0) continue;
+            const int cnt = st.in * st.out + st.out;
+            if ((pass == 0 && cnt > 256) || cnt > 640 || 2 * cnt > free_floats) continue;
+            st.m_lds = p;
+            p += 2 * cnt;
+            free_floats -= 2 * cnt;
+        }
+
+    const size_t lds = (size_t)p * sizeof(float);
+    if (lds > 64 * 1024) {
+        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_train_kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                           "hipFuncSetAttribute(ddpg_train_kernel)");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(ddpg_train_kernel, dim3(1), dim3(kTrainThreads), lds, stream, g);
+    return check_launch("ssc_ddpg_train");
+}
 
 }  // namespace ssc
 
 using namespace ssc;
 
-extern "C" size_t ssc_ddpg_train_workspace_bytes(const ssc_ddpg_desc *d) {
-    if (d == nullptr || d->batch_size < 1 || d->batch_size > 4096 || d->obs_dim < 1 || d->act_dim < 1 || d->actor_h1 < 1 ||
-        d->actor_h2 < 1 || d->critic_h1 < 1 || d->critic_h2 < 1)
-        return 256;
-    return ddpg_wide_workspace_bytes(d);
+// The checks every entry point shares: the shapes, then -- n_iters == 0 has nothing to launch -- the pointers.  have_ws =
+// false (ssc_ddpg_train) also refuses what only the multi-workgroup kernels run.  Returns DDPG_GO, or what the call returns.
+enum { DDPG_GO = 1 };
+static int ddpg_check(const char *who, const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
+                      int32_t n_iters, bool have_ws = true) {
+    SSC_REQUIRE(d && rp, "%s: NULL descriptor", who);
+    SSC_REQUIRE(n_iters >= 0, "%s: n_iters < 0", who);
+    SSC_REQUIRE(d->batch_size >= 1, "%s: batch_size %d", who, d->batch_size);
+    SSC_REQUIRE(d->obs_dim >= 1 && d->obs_dim <= SSC_MAX_STATE && d->act_dim >= 1 && d->act_dim <= SSC_MAX_ACT,
+                "%s: obs_dim/act_dim out of range", who);
+    SSC_REQUIRE(d->actor_h1 >= 1 && d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1, "%s: bad hidden sizes", who);
+    SSC_REQUIRE(d->critic_l2_reg >= 0.0f, "%s: critic_l2_reg < 0", who);
+    if (!have_ws && !ddpg_narrow(d))
+        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: batch_size %d / hidden layers wider than 64 / LayerNorm / critic_l2_reg / "
+                                           "clip_norm run the multi-workgroup kernels, which need a workspace: call ssc_ddpg_train_ws", d->batch_size);
+    if (n_iters == 0) return SSC_OK;
+    SSC_REQUIRE(d->actor && d->critic && d->target_actor && d->target_critic && d->adam_m_actor && d->adam_v_actor &&
+                    d->adam_m_critic && d->adam_v_critic && d->adam_t,
+                "%s: NULL parameter / optimiser pointer", who);
+    SSC_REQUIRE(rp->s && rp->a && rp->r && rp->t && rp->s2 && rp->capacity > 0 && d_batch_idx, "%s: NULL replay pointer", who);
+    return DDPG_GO;
 }
 
-// Which kernel serves a shape: the shipped 64-32 / batch-64 shape has a kernel of its own (ddpg_train_fixed.hip); other
-// nets <= 64 wide at batch 64 run the single-workgroup step interpreter below; everything else -- wider layers (the
-// reference's 128-64 and 200-100 grid), other batch sizes -- the multi-workgroup kernels of ddpg_train_wide.hip, which
-// need a workspace.  SSC_DDPG_INTERPRETER=1 / SSC_DDPG_WIDE=1 force a path (A/B measurements, and the tests that
-// check every path against the oracle on the shipped shape).
+// Which learner serves the call is ddpg_learner_path (ddpg_layout.h); SSC_DDPG_INTERPRETER=1 / SSC_DDPG_WIDE=1 force one.
 static int ddpg_train_any(const char *who, const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
                           int32_t n_iters, float *d_losses, void *d_ws, size_t ws_bytes, bool have_ws, ssc_stream_t stream,
-                          const double *d_rms = nullptr);
+                          const double *d_rms = nullptr) {
+    const int rc = ddpg_check(who, d, rp, d_batch_idx, n_iters, have_ws);
+    if (rc != DDPG_GO) return rc;
+    const char *force_i = getenv("SSC_DDPG_INTERPRETER"), *force_w = getenv("SSC_DDPG_WIDE");
+    const bool want_interp = force_i && force_i[0] == '1', want_wide = force_w && force_w[0] == '1';
+    hipStream_t s = as_stream(stream);
+    switch (ddpg_learner_path(d, have_ws, d_rms != nullptr, want_interp, want_wide)) {
+    case DDPG_FIXED: return ddpg_train_fixed(d, rp, d_batch_idx, n_iters, d_losses, s, d_rms);
+    case DDPG_FIXED_TILED: return ddpg_train_fixed_tiled(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, s, d_rms);
+    case DDPG_INTERPRETER: return ddpg_train_interp(d, rp, d_batch_idx, n_iters, d_losses, s);
+    case DDPG_WIDE: return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, s, d_rms);
+    case DDPG_NEEDS_WORKSPACE: break;   // (of the narrow shapes ddpg_check let through: the interpreter's carve does not fit)
+    }
+    return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: these layer sizes need %zu B of LDS on the single-workgroup path; "
+                                       "call ssc_ddpg_train_ws", (size_t)ddpg_interp_carve(d).floats * sizeof(float));
+}
+
+extern "C" int ssc_ddpg_train(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
+                              int32_t n_iters, float *d_losses, ssc_stream_t stream) {
+    return ddpg_train_any("ssc_ddpg_train", d, rp, d_batch_idx, n_iters, d_losses, nullptr, 0, false, stream);
+}
 
 extern "C" int ssc_ddpg_train_ws(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                                  float *d_losses, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream) {
@@ -679,15 +765,6 @@ extern "C" int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *d, const ssc_replay_vi
                           d_rms);
 }
 
-static bool ddpg_desc_sized(const ssc_ddpg_desc *d) {
-    return d != nullptr && d->batch_size >= 1 && d->batch_size <= 4096 && d->obs_dim >= 1 && d->act_dim >= 1 && d->actor_h1 >= 1 &&
-           d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1;
-}
-
-extern "C" size_t ssc_ddpg_train_popart_workspace_bytes(const ssc_ddpg_desc *d) {
-    return ddpg_desc_sized(d) ? ddpg_popart_workspace_bytes(d) : 256;
-}
-
 // normalize_returns + enable_popart (ddpg_editted.py:201-217, 291-301): the step with the return statistics d_ret_rms,
 // on the multi-workgroup kernels whatever the shape (ddpg_train_wide.hip)
 extern "C" int ssc_ddpg_train_ws_popart(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
@@ -696,155 +773,22 @@ extern "C" int ssc_ddpg_train_ws_popart(const ssc_ddpg_desc *d, const ssc_replay
     const char *who = "ssc_ddpg_train_ws_popart";
     if (d_ret_rms == nullptr)
         return ddpg_train_any(who, d, rp, d_batch_idx, n_iters, d_losses, d_workspace, workspace_bytes, true, stream, d_rms);
-    SSC_REQUIRE(d && rp, "%s: NULL descriptor", who);
-    SSC_REQUIRE(n_iters >= 0, "%s: n_iters < 0", who);
-    SSC_REQUIRE(d->batch_size >= 1, "%s: batch_size %d", who, d->batch_size);
-    SSC_REQUIRE(d->obs_dim >= 1 && d->obs_dim <= SSC_MAX_STATE && d->act_dim >= 1 && d->act_dim <= SSC_MAX_ACT,
-                "%s: obs_dim/act_dim out of range", who);
-    SSC_REQUIRE(d->actor_h1 >= 1 && d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1, "%s: bad hidden sizes", who);
-    SSC_REQUIRE(d->critic_l2_reg >= 0.0f, "%s: critic_l2_reg < 0", who);
-    if (n_iters == 0) return SSC_OK;
-    SSC_REQUIRE(d->actor && d->critic && d->target_actor && d->target_critic && d->adam_m_actor && d->adam_v_actor &&
-                    d->adam_m_critic && d->adam_v_critic && d->adam_t,
-                "%s: NULL parameter / optimiser pointer", who);
-    SSC_REQUIRE(rp->s && rp->a && rp->r && rp->t && rp->s2 && rp->capacity > 0 && d_batch_idx, "%s: NULL replay pointer", who);
+    const int rc = ddpg_check(who, d, rp, d_batch_idx, n_iters);
+    if (rc != DDPG_GO) return rc;
     return ddpg_train_wide_popart(d, rp, d_batch_idx, n_iters, d_losses, d_workspace, workspace_bytes, as_stream(stream), d_rms,
                                   d_ret_rms);
 }
 
-extern "C" int ssc_ddpg_train(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
-                              int32_t n_iters, float *d_losses, ssc_stream_t stream) {
-    return ddpg_train_any("ssc_ddpg_train", d, rp, d_batch_idx, n_iters, d_losses, nullptr, 0, false, stream);
+static bool ddpg_desc_sized(const ssc_ddpg_desc *d) {
+    return d != nullptr && d->batch_size >= 1 && d->batch_size <= 4096 && d->obs_dim >= 1 && d->act_dim >= 1 && d->actor_h1 >= 1 &&
+           d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1;
 }
 
-static int ddpg_train_any(const char *who, const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx,
-                          int32_t n_iters, float *d_losses, void *d_ws, size_t ws_bytes, bool have_ws, ssc_stream_t stream,
-                          const double *d_rms) {
-    SSC_REQUIRE(d && rp, "%s: NULL descriptor", who);
-    SSC_REQUIRE(n_iters >= 0, "%s: n_iters < 0", who);
-    SSC_REQUIRE(d->batch_size >= 1, "%s: batch_size %d", who, d->batch_size);
-    SSC_REQUIRE(d->obs_dim >= 1 && d->obs_dim <= SSC_MAX_STATE && d->act_dim >= 1 && d->act_dim <= SSC_MAX_ACT,
-                "%s: obs_dim/act_dim out of range", who);
-    SSC_REQUIRE(d->actor_h1 >= 1 && d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1,
-                "%s: bad hidden sizes", who);
-    const char *force_i = getenv("SSC_DDPG_INTERPRETER"), *force_w = getenv("SSC_DDPG_WIDE");
-    const bool want_interp = force_i && force_i[0] == '1', want_wide = force_w && force_w[0] == '1' && have_ws;
-    SSC_REQUIRE(d->critic_l2_reg >= 0.0f, "%s: critic_l2_reg < 0", who);
-    // (LayerNorm networks, critic_l2_reg and clip_norm run on the multi-workgroup kernels only)
-    const bool narrow = !d->layer_norm && d->critic_l2_reg == 0.0f && !(d->clip_norm > 0.0f) && d->batch_size == kB && d->actor_h1 <= 64 && d->actor_h2 <= 64 && d->critic_h1 <= 64 && d->critic_h2 <= 64;
-    if (!have_ws && !narrow)
-        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: batch_size %d / hidden layers wider than 64 / LayerNorm / critic_l2_reg / "
-                                           "clip_norm run the multi-workgroup kernels, which need a workspace: call ssc_ddpg_train_ws", d->batch_size);
-    if (n_iters == 0) return SSC_OK;
-    SSC_REQUIRE(d->actor && d->critic && d->target_actor && d->target_critic && d->adam_m_actor && d->adam_v_actor &&
-                    d->adam_m_critic && d->adam_v_critic && d->adam_t,
-                "%s: NULL parameter / optimiser pointer", who);
-    SSC_REQUIRE(rp->s && rp->a && rp->r && rp->t && rp->s2 && rp->capacity > 0 && d_batch_idx,
-                "%s: NULL replay pointer", who);
-    // the shipped 64-32 networks at a batch of several 64-row tiles: the straight-line kernel per tile, then the apply pass
-    if (have_ws && !want_wide && !want_interp && ddpg_fixed_tiled_shape(d))
-        return ddpg_train_fixed_tiled(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), d_rms);
-    if (!narrow || want_wide) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), d_rms);
-    if (ddpg_fixed_shape(d) && !want_interp) return ddpg_train_fixed(d, rp, d_batch_idx, n_iters, d_losses, as_stream(stream), d_rms);
-    // the step interpreter below has no normalising build: with statistics its shapes run on the multi-workgroup kernels
-    // (d_rms comes only through ssc_ddpg_train_ws_rms, which has a workspace)
-    if (d_rms != nullptr) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), d_rms);
-
-    const NetDims A{d->obs_dim, d->actor_h1, d->actor_h2, d->act_dim, 0};
-    const NetDims C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim};
-    const int act2 = d->last_layer_tanh ? ACT_TANH : ACT_RELU;
-    TrainArgs g{};
-    g.d = *d; g.rp = *rp; g.batch_idx = d_batch_idx; g.n_iters = n_iters; g.losses = d_losses;
-    // ---- LDS carve (rows of kP floats), then the parameters --------------------------------------------------
-    int p = 0;
-    auto take = [&](int rows) { const int q = p; p += rows * kP; return q; };
-    const int S = take(d->obs_dim), RT = take(4);                             // RT: r, terminal, y (target Q), -Q(s, pi(s))
-    const int X2 = take(C.h1 + d->act_dim);                                   // critic: relu(layer 1) rows, then the action rows
-    const int CA2 = take(C.h2 > d->obs_dim ? C.h2 : d->obs_dim);              // critic layer 2; before that the next-state rows
-    const int S2 = CA2;                                                       // (read by the target pass's first two steps only)
-    const int DQ = take(1), DZ2 = take(C.h2);
-    const int DZ1 = take(C.h1 + d->act_dim);                                  // critic layer-1 deltas; before that the target pass's X2B
-    const int U1 = take(A.h1), U2 = take(A.h2), PI = take(d->act_dim);
-    const int DZ3A = take(d->act_dim), DZ1A = take(A.h1);
-    const int CB2 = take(C.h2 > A.h2 ? C.h2 : A.h2), DZB2 = take(C.h2);       // also target-pass scratch
-    const int DZ2A = CB2;   // actor layer-2 deltas: written (bwd a3) after the last read of CB2, and in the target pass
-                            // (target actor layer 2) read for the last time before CB2 is written
-    const int X2B = DZ1;
-    g.off_S = S; g.off_S2 = S2; g.off_RT = RT; g.off_X2act = X2 + C.h1 * kP;
-    g.n_actor = A.total(); g.n_critic = C.total();
-    // every parameter vector starts on a 16-byte boundary: the dense passes read weights as float4 (a
-    // misaligned ds_read_b128 was measured 6x slower)
-    auto al4 = [](int x) { return (x + 3) & ~3; };
-    const int TA = al4(p), TC = al4(TA + A.total()), TTA = al4(TC + C.total()), TTC = al4(TTA + A.total());
-    g.off_theta[0] = TA; g.off_theta[1] = TC; g.off_theta[2] = TTA; g.off_theta[3] = TTC;
-    p = TTC + C.total();
-    if ((size_t)p * sizeof(float) > 160 * 1024 - 128) { // 64 B of static LDS (loss partials, Adam step sizes)
-        if (have_ws) return ddpg_train_wide(d, rp, d_batch_idx, n_iters, d_losses, d_ws, ws_bytes, as_stream(stream), nullptr);
-        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: these layer sizes need %zu B of LDS on the single-workgroup path; "
-                                           "call ssc_ddpg_train_ws", (size_t)p * sizeof(float));
-    }
-    // ---- the steps of one iteration ----------------------------------------------------------------------------
-    StepList L(g);
-    L.add(ST_GATHER, true);
-    // target_Q = r + (1 - terminal) * gamma * Q'(s2, pi'(s2))      (ddpg_editted.py:132-133)
-    L.fwd(TTA, A, 1, S2, DZ1A, ACT_RELU, false);
-    L.fwd(TTC, C, 1, S2, X2B, ACT_RELU, true);
-    L.fwd(TTA, A, 2, DZ1A, DZ2A, act2, true);
-    L.fwd(TTA, A, 3, DZ2A, X2B + C.h1 * kP, ACT_TANH, true);
-    L.fwd(TTC, C, 2, X2B, CB2, act2, true);
-    L.fwd(TTC, C, 3, CB2, DZB2, ACT_NONE, true);
-    g.steps[g.n_steps - 1].i0 = 1;                              // ... + the target_Q arithmetic on the row (post-op 1)
-    // critic on (s, a) and actor on s                                (:181, :127)
-    L.fwd(TC, C, 1, S, X2, ACT_RELU, false);
-    L.fwd(TA, A, 1, S, U1, ACT_RELU, true);
-    L.fwd(TC, C, 2, X2, CA2, act2, false);
-    L.fwd(TA, A, 2, U1, U2, act2, true);
-    L.fwd(TC, C, 3, CA2, DQ, ACT_NONE, false);
-    g.steps[g.n_steps - 1].i0 = 2;                              // ... + critic loss, DQ becomes d loss / d q (post-op 2)
-    L.fwd(TA, A, 3, U2, PI, ACT_TANH, true);
-    // critic backward: dz2 = (W3 dq) * act'(z2)
-    L.bwd(TC + C.oW3(), 1, 0, C.h2, DQ, DZ2, CA2, act2, false);
-    // critic forward on (s, pi(s)) for the actor loss: the same relu(layer 1) rows, the action rows are pi(s)
-    L.fwd(TC, C, 2, X2, CB2, act2, true, PI, C.h1);
-    L.bwd(TC + C.oW2(), C.h2, 0, C.h1, DZ2, DZ1, X2, ACT_RELU, false);   // ... * relu'(layer 1)
-    L.fwd(TC, C, 3, CB2, DZ3A, ACT_NONE, true);             // q(s, pi) -> DZ3A row 0, then
-    g.steps[g.n_steps - 1].i0 = 3;                          // actor loss, the row becomes dq of -mean Q (post-op 3)
-    L.bwd(TC + C.oW3(), 1, 0, C.h2, DZ3A, DZB2, CB2, act2, true);
-    // d(-mean Q)/d(action) = rows h1.. of W2 dzb2 (through the output tanh), then back through the actor
-    L.bwd(TC + C.oW2(), C.h2, C.h1, C.h1 + d->act_dim, DZB2, DZ3A, PI, ACT_TANH, true);
-    L.bwd(TA + A.oW3(), A.out, 0, A.h2, DZ3A, DZ2A, U2, act2, true);
-    L.bwd(TA + A.oW2(), A.h2, 0, A.h1, DZ2A, DZ1A, U1, ACT_RELU, false);
-    L.add(ST_LOSSES, true);                                  // every read of the old parameters is done after this barrier
-    L.wgrad(1, C.oW1(), C.ob1(), C.in, C.h1, S, DZ1, false);
-    L.wgrad(1, C.oW2(), C.ob2(), C.h1 + d->act_dim, C.h2, X2, DZ2, false);
-    L.wgrad(1, C.oW3(), C.ob3(), C.h2, 1, CA2, DQ, false);
-    L.wgrad(0, A.oW1(), A.ob1(), A.in, A.h1, S, DZ1A, false);
-    L.wgrad(0, A.oW2(), A.ob2(), A.h1, A.h2, U1, DZ2A, false);
-    L.wgrad(0, A.oW3(), A.ob3(), A.h2, A.out, U2, DZ3A, true);
-    L.add(ST_TUPDATE, true);
-    if (L.overflow) return set_error(SSC_EINVAL, "ssc_ddpg_train: step list overflow");
-    // Adam moments of the small layers move into what is left of the LDS (smallest layers first)
-    {
-        int free_floats = (160 * 1024 - 128) / 4 - p;
-        for (int pass = 0; pass < 2; ++pass)
-            for (int si = 0; si < g.n_steps; ++si) {
-                Step &st = g.steps[si];
-                if (st.kind != ST_WGRAD || st.m_lds >= 0) continue;
-                const int cnt = st.in * st.out + st.out;
-                if ((pass == 0 && cnt > 256) || cnt > 640 || 2 * cnt > free_floats) continue;
-                st.m_lds = p;
-                p += 2 * cnt;
-                free_floats -= 2 * cnt;
-            }
-    }
-
-    const size_t lds = (size_t)p * sizeof(float);
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_train_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                           "hipFuncSetAttribute(ddpg_train_kernel)");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(ddpg_train_kernel, dim3(1), dim3(kTrainThreads), lds, as_stream(stream), g);
-    return check_launch("ssc_ddpg_train");
+extern "C" size_t ssc_ddpg_train_workspace_bytes(const ssc_ddpg_desc *d) {
+    return ddpg_desc_sized(d) ? ddpg_wide_workspace_bytes(d) : 256;
 }
+
+extern "C" size_t ssc_ddpg_train_popart_workspace_bytes(const ssc_ddpg_desc *d) {
+    return ddpg_desc_sized(d) ? ddpg_popart_workspace_bytes(d) : 256;
+}
+

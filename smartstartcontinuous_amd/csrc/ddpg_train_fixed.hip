@@ -39,7 +39,7 @@ namespace ssc {
 namespace {
 
 constexpr int kT = 512, kNW = kT / 64;
-constexpr int H1 = 64, H2 = 32;
+constexpr int H1 = kFixedH1, H2 = kFixedH2;
 constexpr int W2S = H2 + 4;   // LDS row stride of a W2 matrix.  The backward pass reads COLUMN slices of it (lane = input row): at
                               // stride 32 all 16 lanes of a k group sit on one bank, at 36 they spread over 8 (2-way).  The forward
                               // pass wants rows 4 apart to sit 16 banks apart (see fwd_item): 36 = 4 mod 32 does that too, like kP
@@ -49,7 +49,8 @@ constexpr int al4(int x) { return (x + 3) & ~3; }
 template <int O, int IN2>
 struct Net {
     static constexpr int W1 = 0, b1 = O * H1, W2 = b1 + H1, b2 = al4(W2 + IN2 * W2S), W3 = b2 + H2, b3 = W3 + H2, size = al4(b3 + 1);
-    static constexpr int gW1 = 0, gb1 = O * H1, gW2 = gb1 + H1, gb2 = gW2 + IN2 * H2, gW3 = gb2 + H2, gb3 = gW3 + H2, gsize = gb3 + 1;
+    static constexpr DdpgNet G{O, H1, H2, 1, IN2 - H1, 0};   // the flat vector: ddpg_layout.h
+    static constexpr int gW1 = G.oW1(), gb1 = G.ob1(), gW2 = G.oW2(), gb2 = G.ob2(), gW3 = G.oW3(), gb3 = G.ob3(), gsize = G.total();
     __device__ static int to_lds(int e) {   // flat index -> image index
         if (e < gW2) return e;
         if (e < gb2) { const int k = e - gW2; return W2 + (k >> 5) * W2S + (k & 31); }
@@ -203,10 +204,9 @@ __device__ __forceinline__ float wave_sum(float v) {
 // update_target_net on the same element (:338-339).  th / tg: the old values of theta and target (read by the caller,
 // all of a lane's elements at once: one LDS round trip, not one per element); moments in registers.
 __device__ __forceinline__ void adam_target(float &th, float &tg, float &m, float &v, float g, const AdamCfg &c, float tau) {
-    m = c.beta1 * m + (1.0f - c.beta1) * g;
-    v = c.beta2 * v + (1.0f - c.beta2) * (g * g);
-    th += (-c.a) * m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) + c.eps);   // 1-ulp sqrt / rcp: a 1e-7 relative wobble
-    tg = (1.0f - tau) * tg + tau * th;                                              // of a 1e-3-sized step
+    adam_moments(m, v, g, c);
+    th += adam_step_fast(m, v, c);
+    tg = (1.0f - tau) * tg + tau * th;
 }
 
 // the four elements (i = 16 ib + 4 kg + r, j = 16 jb + c) of a weight-gradient tile
@@ -330,10 +330,8 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms..
     if (!TILED && ec.on) { mc = d.adam_m_critic[ec.gidx]; vc = d.adam_v_critic[ec.gidx]; }
     if (!TILED && ea.on) { ma = d.adam_m_actor[ea.gidx]; va = d.adam_v_actor[ea.gidx]; }
 
-    int tA = TILED ? 0 : d.adam_t[0], tC = TILED ? 0 : d.adam_t[1];
-    // running beta powers for MpiAdam's bias correction, in f64 (1 - 0.999^t loses 5 digits in fp32)
-    double b1a = ipow((double)d.beta1, tA), b2a = ipow((double)d.beta2, tA);
-    double b1c = ipow((double)d.beta1, tC), b2c = ipow((double)d.beta2, tC);
+    AdamClock clk;
+    clk.init(d, !TILED);
 
     // ---- batch pipeline: indices two iterations ahead, rows one iteration ahead (wave 0, lane = sample) ----------
     float pf_s[O], pf_s2[O], pf_a = 0.0f, pf_r = 0.0f, pf_t = 0.0f;
@@ -363,11 +361,10 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms..
         uint64_t cp_prev = __builtin_amdgcn_s_memtime();
 #endif
         // ---- L0: ReplayBuffer.sample_batch rows; MpiAdam step sizes --------------------------------------------------
-        ++tA; ++tC;
-        b1a *= (double)d.beta1; b2a *= (double)d.beta2; b1c *= (double)d.beta1; b2c *= (double)d.beta2;
+        clk.tick(d);
         if (!TILED && tid == kB) {
-            cfg_s[0] = AdamCfg{(float)((double)d.actor_lr * sqrt(1.0 - b2a) / (1.0 - b1a)), d.beta1, d.beta2, d.epsilon};
-            cfg_s[1] = AdamCfg{(float)((double)d.critic_lr * sqrt(1.0 - b2c) / (1.0 - b1c)), d.beta1, d.beta2, d.epsilon};
+            cfg_s[0] = clk.cfg_actor(d);
+            cfg_s[1] = clk.cfg_critic(d);
         }
         if (tid < kB) {
 #pragma unroll
@@ -376,8 +373,8 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms..
                     row(R::S + k)[tid] = nrm.apply(pf_s[k], k, d.obs_clip);
                     row(R::S2 + k)[tid] = nrm.apply(pf_s2[k], k, d.obs_clip);
                 } else {
-                    row(R::S + k)[tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s[k], -d.obs_clip), d.obs_clip) : pf_s[k];
-                    row(R::S2 + k)[tid] = d.obs_clip > 0.0f ? fminf(fmaxf(pf_s2[k], -d.obs_clip), d.obs_clip) : pf_s2[k];
+                    row(R::S + k)[tid] = clip_obs(pf_s[k], d.obs_clip);
+                    row(R::S2 + k)[tid] = clip_obs(pf_s2[k], d.obs_clip);
                 }
             }
             row(R::X2 + H1)[tid] = pf_a;
@@ -576,7 +573,7 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms..
     }
     if (ec.on) { d.adam_m_critic[ec.gidx] = mc; d.adam_v_critic[ec.gidx] = vc; }
     if (ea.on) { d.adam_m_actor[ea.gidx] = ma; d.adam_v_actor[ea.gidx] = va; }
-    if (tid == 0) { d.adam_t[0] = tA; d.adam_t[1] = tC; }
+    if (tid == 0) { d.adam_t[0] = clk.tA; d.adam_t[1] = clk.tC; }
 }
 
 template <int O, bool TANH2, bool TILED = false, class... Rms>
@@ -593,20 +590,6 @@ int launch_fixed(const FixedArgs &g, hipStream_t stream, unsigned tiles = 1, Rms
 }
 
 }  // namespace
-
-bool ddpg_fixed_shape(const ssc_ddpg_desc *d) {
-    return d->batch_size == kB && (d->obs_dim == 2 || d->obs_dim == 3) && d->act_dim == 1 && d->actor_h1 == H1 && d->actor_h2 == H2 &&
-           d->critic_h1 == H1 && d->critic_h2 == H2;
-}
-
-static bool fixed_nets(const ssc_ddpg_desc *d) {
-    return (d->obs_dim == 2 || d->obs_dim == 3) && d->act_dim == 1 && d->actor_h1 == H1 && d->actor_h2 == H2 && d->critic_h1 == H1 &&
-           d->critic_h2 == H2 && !d->layer_norm;
-}
-
-bool ddpg_fixed_tiled_shape(const ssc_ddpg_desc *d) {
-    return fixed_nets(d) && d->batch_size > kB && d->batch_size % kB == 0 && d->batch_size <= 4096;
-}
 
 // arguments already validated by ssc_ddpg_train_ws; the workspace is sized by ddpg_wide_workspace_bytes (16-row partials:
 // four times what the 64-row tiles write)

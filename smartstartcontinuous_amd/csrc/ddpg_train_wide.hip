@@ -696,8 +696,7 @@ __global__ __launch_bounds__(256) void ddpg_wide_apply_kernel(ApplyArgs a) {
         const int net = threadIdx.x;
         const int t = a.d.adam_t[net] + a.it + 1;
         const double b1 = ipow((double)a.d.beta1, t), b2 = ipow((double)a.d.beta2, t);
-        const double lr = net == 0 ? (double)a.d.actor_lr : (double)a.d.critic_lr;
-        cfg[net] = AdamCfg{(float)(lr * sqrt(1.0 - b2) / (1.0 - b1)), a.d.beta1, a.d.beta2, a.d.epsilon};
+        cfg[net] = adam_cfg(net == 0 ? (double)a.d.actor_lr : (double)a.d.critic_lr, b1, b2, a.d);
     }
     __syncthreads();
     const int p = blockIdx.x * 256 + threadIdx.x;
@@ -732,9 +731,8 @@ __global__ __launch_bounds__(256) void ddpg_wide_apply_kernel(ApplyArgs a) {
         const AdamCfg c = cfg[net];
         // MpiAdam.update (baselines common/mpi_adam.py [third-party], ddpg_editted.py:326-327), update_target_net (:338-339)
         float m = mm[q], v = vv[q], th = theta[q], tg = target[q];
-        m = c.beta1 * m + (1.0f - c.beta1) * g;
-        v = c.beta2 * v + (1.0f - c.beta2) * (g * g);
-        th += (-c.a) * m / (sqrtf(v) + c.eps);
+        adam_moments(m, v, g, c);
+        th += adam_step_ieee(m, v, c);   // (IEEE sqrt and division here, by design: ddpg_device.h)
         tg = (1.0f - a.d.tau) * tg + a.d.tau * th;
         mm[q] = m; vv[q] = v; theta[q] = th; target[q] = tg;
     }
@@ -756,27 +754,14 @@ __global__ void ddpg_wide_finish_kernel(int32_t *adam_t, int32_t n_iters) {
     adam_t[1] += n_iters;
 }
 
-struct WNet {
-    int in, h1, h2, out, extra;   // extra: rows concatenated to the first hidden layer (critic: act_dim)
-    int ln;                       // 1: [W1|b1|beta1|gamma1|W2|b2|beta2|gamma2|W3|b3] (ssc_ddpg_desc::layer_norm)
-    int oW1() const { return 0; }
-    int ob1() const { return in * h1; }
-    int obe1() const { return ob1() + h1; }           // LayerNorm beta, then gamma (ln only)
-    int og1() const { return obe1() + h1; }
-    int oW2() const { return ob1() + h1 + (ln ? 2 * h1 : 0); }
-    int ob2() const { return oW2() + (h1 + extra) * h2; }
-    int obe2() const { return ob2() + h2; }
-    int og2() const { return obe2() + h2; }
-    int oW3() const { return ob2() + h2 + (ln ? 2 * h2 : 0); }
-    int ob3() const { return oW3() + h2 * out; }
-    int total() const { return ob3() + out; }
-};
-
+static int wide_batch_check(const char *who, const ssc_ddpg_desc *d) {
+    if (d->batch_size >= 1 && d->batch_size <= 4096) return SSC_OK;
+    return set_error(SSC_EUNSUPPORTED, "%s: batch_size %d not in 1..4096", who, d->batch_size);
+}
 static int wide_blocks(const ssc_ddpg_desc *d) { return (d->batch_size + kWR - 1) / kWR; }
 static int wide_params(const ssc_ddpg_desc *d) {
-    const int ln = d->layer_norm ? 1 : 0;
-    const WNet A{d->obs_dim, d->actor_h1, d->actor_h2, d->act_dim, 0, ln}, C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim, ln};
-    return A.total() + C.total();
+    const DdpgNets n = ddpg_nets(d);
+    return n.A.total() + n.C.total();
 }
 
 static bool wide_prepared(const ssc_ddpg_desc *d) { return d->critic_l2_reg != 0.0f || d->clip_norm > 0.0f; }
@@ -800,8 +785,9 @@ WidePartials ddpg_wide_partials(const ssc_ddpg_desc *d, void *d_workspace, int n
 }
 
 void ddpg_wide_apply(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks, int it, float *d_losses_it, hipStream_t stream) {
-    const int ln = d->layer_norm ? 1 : 0;
-    const WNet A{d->obs_dim, d->actor_h1, d->actor_h2, d->act_dim, 0, ln}, C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim, ln};
+    const DdpgNets ac = ddpg_nets(d);
+    const DdpgNet &A = ac.A, &C = ac.C;
+    const int ln = A.ln;
     const int nA = A.total(), nC = C.total();
     const WidePartials wp = ddpg_wide_partials(d, d_workspace, n_blocks);
     ApplyArgs ap{};
@@ -821,7 +807,7 @@ void ddpg_wide_apply(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks, in
     for (int k = 0; k < 3; ++k) { ap.reg_lo[k] = lo[k]; ap.reg_hi[k] = hi[k]; }
     int nv = 0;
     for (int n = 0; n < 2; ++n) {
-        const WNet &N = n == 0 ? A : C;
+        const DdpgNet &N = n == 0 ? A : C;
         const int base = n == 0 ? 0 : nA;
         ap.var_lo[nv++] = base + N.oW1(); ap.var_lo[nv++] = base + N.ob1();
         if (ln) { ap.var_lo[nv++] = base + N.obe1(); ap.var_lo[nv++] = base + N.og1(); }
@@ -846,8 +832,9 @@ enum : int { WIDE_FULL = 0, WIDE_POP_TARGET, WIDE_POP_GRAD };
 
 static int wide_build(const ssc_ddpg_desc *d, const ssc_replay_view *rp, int mode, void *d_workspace, WideArgs &g, size_t &lds_bytes) {
     const bool tgt = mode != WIDE_POP_GRAD, trn = mode != WIDE_POP_TARGET;
-    const int ln = d->layer_norm ? 1 : 0;
-    const WNet A{d->obs_dim, d->actor_h1, d->actor_h2, d->act_dim, 0, ln}, C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim, ln};
+    const DdpgNets ac = ddpg_nets(d);
+    const DdpgNet &A = ac.A, &C = ac.C;
+    const int ln = A.ln;
     const int od = d->obs_dim, ad = d->act_dim;
     const int act2 = d->last_layer_tanh ? EPI_TANH : EPI_RELU, mask2 = d->last_layer_tanh ? EPI_MASK_TANH : EPI_MASK_RELU;
     // with LayerNorm the contractions of the hidden layers leave the pre-normalisation sums and the LayerNorm op applies
@@ -880,11 +867,11 @@ static int wide_build(const ssc_ddpg_desc *d, const ssc_replay_view *rp, int mod
     // the small-parameter image: per net the flat vector without its h1 x h2 block, i.e. [W1 | b1] and
     // [W2 action rows | b2 | W3 | b3]; img(net, flat offset) = LDS offset of that element
     const float *theta[4] = {d->target_actor, d->target_critic, d->critic, d->actor};     // ta, tc, c, a
-    const WNet *nets[4] = {&A, &C, &C, &A};
+    const DdpgNet *nets[4] = {&A, &C, &C, &A};
     int img_lo[4], img_hi[4];
     g.tab.n_seg = 0; g.tab.n_big = 0;
     for (int n = 0; n < 4; ++n) {
-        const WNet &N = *nets[n];
+        const DdpgNet &N = *nets[n];
         const int head = N.h1 * N.h2;
         const bool used = n < 2 ? tgt : trn;     // a network the launch leaves out keeps its place in the image, uncopied
         img_lo[n] = p;
@@ -911,14 +898,14 @@ static int wide_build(const ssc_ddpg_desc *d, const ssc_replay_view *rp, int mod
     // LayerNorm ops behind the current level's contractions; net n's gamma / beta of hidden layer `layer`
     auto ln_fwd = [&](int n, int layer, int x_off, int act, int xhat_off, int rstd_off) {
         if (!ln || !(n < 2 ? tgt : trn)) return;
-        const WNet &N = *nets[n];
+        const DdpgNet &N = *nets[n];
         WLn &L = g.tab.ln[nln++];
         L = WLn{0, x_off, xhat_off, rstd_off, img(n, layer == 1 ? N.og1() : N.og2()), img(n, layer == 1 ? N.obe1() : N.obe2()),
                 layer == 1 ? N.h1 : N.h2, act, -1, -1};
     };
     auto ln_bwd = [&](int n, int layer, int x_off, int xhat_off, int rstd_off, int gbase) {   // gbase < 0: no parameter gradients
         if (!ln || !(n < 2 ? tgt : trn)) return;
-        const WNet &N = *nets[n];
+        const DdpgNet &N = *nets[n];
         WLn &L = g.tab.ln[nln++];
         L = WLn{1, x_off, xhat_off, rstd_off, img(n, layer == 1 ? N.og1() : N.og2()), -1, layer == 1 ? N.h1 : N.h2, EPI_NONE,
                 gbase < 0 ? -1 : gbase + (layer == 1 ? N.og1() : N.og2()), gbase < 0 ? -1 : gbase + (layer == 1 ? N.obe1() : N.obe2())};
@@ -1022,8 +1009,7 @@ template <class... Rms> static int wide_lds_attr(size_t lds) {
 
 int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                     float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms) {
-    if (d->batch_size < 1 || d->batch_size > 4096)
-        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train: batch_size %d not in 1..4096", d->batch_size);
+    if (int rc = wide_batch_check("ssc_ddpg_train", d)) return rc;
     const size_t need = ddpg_wide_workspace_bytes(d);
     SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= need,
                 "ssc_ddpg_train_ws: workspace %zu < %zu bytes (ssc_ddpg_train_workspace_bytes)", workspace_bytes, need);
@@ -1126,8 +1112,7 @@ static int wide_popart_iters(const ssc_ddpg_desc *d, WideArgs &gt, WideArgs &gg,
 int ddpg_train_wide_popart(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                            float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms,
                            double *d_ret_rms) {
-    if (d->batch_size < 1 || d->batch_size > 4096)
-        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_train_ws_popart: batch_size %d not in 1..4096", d->batch_size);
+    if (int rc = wide_batch_check("ssc_ddpg_train_ws_popart", d)) return rc;
     const PopLayout L = popart_layout(d, d_workspace);
     SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= L.bytes,
                 "ssc_ddpg_train_ws_popart: workspace %zu < %zu bytes (ssc_ddpg_train_popart_workspace_bytes)", workspace_bytes, L.bytes);
@@ -1135,8 +1120,7 @@ int ddpg_train_wide_popart(const ssc_ddpg_desc *d, const ssc_replay_view *rp, co
     size_t lds = 0;
     if (int rc = wide_build(d, rp, WIDE_POP_TARGET, d_workspace, gt, lds)) return rc;
     if (int rc = wide_build(d, rp, WIDE_POP_GRAD, d_workspace, gg, lds)) return rc;
-    const int ln = d->layer_norm ? 1 : 0;
-    const WNet C{d->obs_dim, d->critic_h1, d->critic_h2, 1, d->act_dim, ln};
+    const DdpgNet C = ddpg_nets(d).C;
     RenormArgs rn{};
     rn.ret_rms = d_ret_rms; rn.part = L.part; rn.scal = L.scal;
     rn.cW3 = d->critic + C.oW3(); rn.cb3 = d->critic + C.ob3();

@@ -337,6 +337,8 @@ __global__ __launch_bounds__(kCycleThreads) void param_noise_cycle_kernel(CycleA
 }
 
 // offset of a parameter segment of `count` floats inside the flat array, or -1 when it does not lie inside it
+// (this maps the CALLER's pointers back to offsets, whatever order they come in; the flat layout the learners write --
+// [W1|b1|(beta1|gamma1)|W2|b2|(beta2|gamma2)|W3|b3] -- is defined in ddpg_layout.h)
 int32_t segment(const float *p, int64_t count, const float *src, int64_t n) {
     if (p == nullptr || p < src) return -1;
     const int64_t off = p - src;

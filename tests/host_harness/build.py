@@ -7,6 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 SRC = os.path.join(ROOT, "tests", "host_harness", "harness.hip")
 OUT = os.path.join(ROOT, "tests", "_build", "libssc_host_harness.so")
 DEPS = [SRC, os.path.join(ROOT, "smartstartcontinuous_amd", "csrc", "ssc_device.h"),
+        os.path.join(ROOT, "smartstartcontinuous_amd", "csrc", "ddpg_layout.h"),
         os.path.join(ROOT, "include", "ssc.h")]
 
 

@@ -2,6 +2,7 @@
 // smartstartcontinuous_amd/csrc/ssc_device.h on the CPU so that `-m "not gpu"` tests can check
 // the device math (RNG keying, step ordering, fp32 error budget) against the oracle without a GPU.
 // TEST INFRASTRUCTURE: never loaded by the product.
+#include "ddpg_layout.h"
 #include "ssc_device.h"
 
 using namespace ssc;
@@ -61,6 +62,20 @@ void h_tanh_fast(int64_t n, const float *x, float *out) {
 
 void h_gaussian(int64_t n, const uint32_t *x0, const uint32_t *x1, float *out) {
     for (int64_t i = 0; i < n; ++i) out[i] = gaussian_f32(x0[i], x1[i]);
+}
+
+// ddpg_layout.h: offsets of [W1, b1, ln1_b, ln1_g, W2, b2, ln2_b, ln2_g, W3, b3] and total() of the actor (net 0) or the
+// critic (net 1) of a descriptor
+void h_ddpg_layout(const ssc_ddpg_desc *d, int net, int32_t *out) {
+    const DdpgNets n = ddpg_nets(d);
+    const DdpgNet &N = net == 0 ? n.A : n.C;
+    const int32_t o[11] = {N.oW1(), N.ob1(), N.obe1(), N.og1(), N.oW2(), N.ob2(), N.obe2(), N.og2(), N.oW3(), N.ob3(), N.total()};
+    for (int i = 0; i < 11; ++i) out[i] = o[i];
+}
+
+// 0 FIXED, 1 FIXED_TILED, 2 INTERPRETER, 3 WIDE, 4 NEEDS_WORKSPACE
+int h_ddpg_learner_path(const ssc_ddpg_desc *d, int have_ws, int have_rms, int want_interp, int want_wide) {
+    return (int)ddpg_learner_path(d, have_ws != 0, have_rms != 0, want_interp != 0, want_wide != 0);
 }
 
 }  // extern "C"
