@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--overlap", action="store_true",
                     help="vec: roll chunk i+1 on a second stream while the learner works on chunk i (one chunk stale)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--population", type=int, default=None, metavar="P",
+                    help="vec: P agents with seeds SEED .. SEED + P - 1 on envs of their own, trained by one learner launch per chunk "
+                         "(rl_train_vec_ddpg_population); prints each seed's late-window return")
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--normalize-observations", action="store_true",
                     help="DDPG normalize_observations: networks see running-statistics-normalised observations")
@@ -74,6 +77,25 @@ def main():
                     summary.append_record(*one.episodes[0])
                 if (episode + 1) % args.stats_every == 0 and len(agent.replay_buffer) >= agent.batch_size:
                     print("  stats:", ", ".join("%s %.6g" % kv for kv in agent.get_stats().items()))
+    elif args.population is not None:
+        if args.param_noise is not None or args.stats_every is not None or args.eval_every is not None or args.overlap:
+            ap.error("--population runs the synchronous loop without parameter noise, diagnostics and evaluation")
+        env_id = "MountainCarContinuousActionX%s-v0" % args.power_scalar
+        seeds = [args.seed + p for p in range(args.population)]
+        envs = [ssc.VecEnv(env_id, args.envs, seed=s, env_id0=p * args.envs) for p, s in enumerate(seeds)]
+        agents = [make_agent(ssc.SingleEnvView(ssc.VecEnv(env_id, 1, seed=s)), s, args.normalize_observations, None, args.popart)
+                  for s in seeds]
+        runs = ssc.rl_train_vec_ddpg_population(envs, agents, num_chunks=args.chunks, chunk_steps=250, replay_capacity=1 << 20,
+                                                train_iters=50, seed=seeds)
+        for s, (summary, losses, replay) in zip(seeds, runs):
+            late = [ret for _steps, ret in summary.episodes[-max(1, len(summary) // 4):]]
+            print("seed %d: %d finished episodes, late-window return %.2f (last quarter of them), last critic/actor loss %.4g / %.4g"
+                  % (s, len(summary), float(np.mean(late)) if late else float("nan"), *losses[-1][-1].tolist()))
+        if args.save_dir:
+            os.makedirs(args.save_dir, exist_ok=True)
+            for s, (summary, _l, _r) in zip(seeds, runs):
+                print("summary written to", summary.save(args.save_dir, post_fix=s))
+        return
     else:
         env = ssc.VecEnv("MountainCarContinuousActionX%s-v0" % args.power_scalar, args.envs, seed=args.seed)
         agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations,

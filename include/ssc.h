@@ -663,6 +663,47 @@ int ssc_ddpg_train_ws_popart(const ssc_ddpg_desc *ddpg, const ssc_replay_view *r
                              double *d_ret_rms /* [sum | sumsq | count], read and written */);
 
 /* ---------------------------------------------------------------------------------------
+ * A population of independent DDPG agents in one learner launch
+ * -------------------------------------------------------------------------------------
+ * The reference fans seeds x hyper-parameter grids out over processes (experimenter.py); the device-side counterpart for
+ * the shipped shape: agent p's n_iters iterations run in workgroup p of ONE launch, each exactly as ssc_ddpg_train /
+ * ssc_ddpg_train_ws_rms would run them alone -- the same bits.  Workgroups share nothing: no atomics, no workspace.
+ * Every agent must have the shipped shape (64-32 actor and critic, batch 64, act_dim 1, obs_dim 2 or 3; no LayerNorm,
+ * critic_l2_reg or clip_norm: otherwise SSC_EUNSUPPORTED with the agent's index in ssc_last_error()); obs_dim and
+ * last_layer_tanh are the same for the whole population, d_rms is NULL for all agents or for none, and no two agents
+ * share any of the nine parameter / optimiser arrays or adam_t (SSC_EINVAL: two workgroups would race on it).  Everything
+ * else -- rings, indices, losses, gamma, tau, learning rates, obs_clip, n_iters -- is per agent.
+ * The two structs are declared tag first; tests/test_ddpg_many_host.py holds their sizes and offsets to the ctypes mirrors. */
+struct ssc_ddpg_many_item {
+    ssc_ddpg_desc   ddpg;          /* this agent's arrays and hyper-parameters */
+    ssc_replay_view replay;        /* this agent's ring */
+    const int32_t  *d_batch_idx;   /* [n_iters][64] */
+    float          *d_losses;      /* [n_iters][2] or NULL */
+    const double   *d_rms;         /* normalize_observations block or NULL -- all agents or none */
+    int32_t         n_iters;       /* >= 0, per agent; 0: the agent is left exactly as it is */
+};
+typedef struct ssc_ddpg_many_item ssc_ddpg_many_item;
+
+/* h_items: host array [n_agents], validated here before any HIP call.  d_items: the caller's device copy of the same
+ * bytes, complete on `stream` before this call (caller-owned like every buffer; the library copies nothing).  All
+ * n_iters == 0: SSC_OK without a launch. */
+int ssc_ddpg_train_many(const ssc_ddpg_many_item *h_items, const ssc_ddpg_many_item *d_items, int32_t n_agents,
+                        ssc_stream_t stream);
+
+struct ssc_replay_sample_key {
+    uint64_t seed, counter0;
+    int64_t size;
+};
+typedef struct ssc_replay_sample_key ssc_replay_sample_key;
+
+/* ssc_replay_sample for n_agents rings in one launch: d_idx [n_agents][n_batches][batch_size], agent p's rows drawn with
+ * h_keys[p] exactly as ssc_replay_sample(seed, counter0, size, n_batches, batch_size, ..) draws them.  batch_size 1..64
+ * (the one-wave kernel; larger: SSC_EUNSUPPORTED), every size >= batch_size.  d_keys: the device copy of h_keys, complete
+ * on `stream` before this call. */
+int ssc_replay_sample_many(const ssc_replay_sample_key *h_keys, const ssc_replay_sample_key *d_keys, int32_t n_agents,
+                           int32_t n_batches, int32_t batch_size, int32_t *d_idx, ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Adaptive parameter-space noise (ddpg_editted.py:47-60, 151-166, 255-259, 360-385)
  * -------------------------------------------------------------------------------------
  * A perturbed actor is a second flat parameter array [W1|b1|(beta1|gamma1)|W2|b2|(beta2|gamma2)|W3|b3] that the

@@ -146,6 +146,25 @@ class ReplayRing(Structure):
                 ("ep_steps", c_void_p), ("ep_run", c_void_p)]
 
 
+class DdpgManyItem(Structure):
+    _fields_ = [("ddpg", DdpgDesc), ("replay", ReplayView), ("d_batch_idx", c_void_p), ("d_losses", c_void_p),
+                ("d_rms", c_void_p), ("n_iters", c_int32)]
+
+
+class ReplaySampleKey(Structure):
+    _fields_ = [("seed", c_uint64), ("counter0", c_uint64), ("size", c_int64)]
+
+
+# C struct -> its ctypes mirror: the struct-layout table (the tests compare sizeof / offsetof as the C compiler sees them)
+STRUCTS = {
+    "ssc_env_params": EnvParams, "ssc_actor_desc": ActorDesc, "ssc_ou_desc": OuDesc, "ssc_policy_desc": PolicyDesc,
+    "ssc_rollout_state": RolloutState, "ssc_transition_log": TransitionLog, "ssc_episode_ring": EpisodeRing,
+    "ssc_mlp_desc": MlpDesc, "ssc_norm": Norm, "ssc_mpc_problems": MpcProblems, "ssc_mpc_sampling": MpcSampling,
+    "ssc_mpc_nav_state": MpcNavState, "ssc_smartstart_step": SmartStartStep, "ssc_critic_desc": CriticDesc,
+    "ssc_ddpg_desc": DdpgDesc, "ssc_replay_view": ReplayView, "ssc_replay_ring": ReplayRing,
+    "ssc_mlp_train_desc": MlpTrainDesc, "ssc_ddpg_many_item": DdpgManyItem, "ssc_replay_sample_key": ReplaySampleKey,
+}
+
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
 # (tests/test_abi.py cross-checks the header against this table and the built library).
 _SIGNATURES = {
@@ -203,6 +222,9 @@ _SIGNATURES = {
     "ssc_ddpg_train_popart_workspace_bytes": (c_size_t, [POINTER(DdpgDesc)]),
     "ssc_ddpg_train_ws_popart": (c_int, [POINTER(DdpgDesc), POINTER(ReplayView), c_void_p, c_int32, c_void_p, c_void_p,
                                          c_size_t, c_void_p, c_void_p, c_void_p]),
+    # a population of agents in one launch: host items / keys (validated) + the caller's device copy of the same bytes
+    "ssc_ddpg_train_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_replay_sample_many": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     # adaptive parameter-space noise: perturb a flat actor, adapt the device stddev
     "ssc_param_noise_perturb": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint64,
                                         c_uint64, c_void_p]),

@@ -811,6 +811,181 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         return losses
 
 
+class DDPGPopulation:
+    """P independent :class:`DDPG_Baselines_agent` objects -- seeds x hyper-parameter grids, what the reference fans out
+    over processes (experimenter.py) -- trained by ONE learner launch, one workgroup per agent (``ssc_ddpg_train_many``),
+    on batch indices drawn by one launch (``ssc_replay_sample_many``).  The agents are wrapped, not copied: every result is
+    bit for bit what ``agent.train_from`` / ``agent.train_on`` gives agent by agent.
+
+    The launch serves the shipped shape only (64-32 actor and critic, batch 64, one action, obs_dim 2 or 3, no LayerNorm /
+    critic_l2_reg / clip_norm / Pop-Art; one obs_dim and lastLayerTanh for all, normalize_observations for all or for
+    none, no array shared by two agents) and only while neither ``SSC_DDPG_INTERPRETER`` nor ``SSC_DDPG_WIDE`` is set.
+    Any other population runs the per-agent calls one after the other; ``fused`` tells which way the last call went.
+
+    Index and loss tensors and the pinned-host and device copies of the launch descriptors stay with the population and
+    are rebuilt only when a pointer, an iteration count or a ring changes: in steady state a call uploads the P sampling
+    keys and nothing else.  The loss tensors a call returns are therefore views of one buffer the NEXT call overwrites
+    (``copy=True`` returns views of a fresh copy instead)."""
+
+    B = 64
+
+    def __init__(self, agents):
+        self.agents = list(agents)
+        if not self.agents:
+            raise ValueError("a population needs at least one agent")
+        self.device = self.agents[0].device
+        if any(a.device != self.device for a in self.agents):
+            raise ValueError("the agents of a population live on one device")
+        self.lib = _ffi.lib()
+        self.fused = None
+        self._sig = None
+        self._items_event = self._keys_event = None
+
+    def __len__(self):
+        return len(self.agents)
+
+    # ---- which way a call goes -------------------------------------------------------------------
+    @staticmethod
+    def _forced_elsewhere():
+        """the A/B switches of ddpg_train_any keep their meaning: they send every agent to another learner"""
+        return any((os.environ.get(k) or "")[:1] == "1" for k in ("SSC_DDPG_INTERPRETER", "SSC_DDPG_WIDE"))
+
+    @classmethod
+    def _shipped_shape(cls, a):
+        c = a._critic_desc
+        return (a.batch_size == cls.B and a.obs_dim in (2, 3) and a.act_dim == 1 and (a.h1, a.h2) == (64, 32)
+                and (c.h1, c.h2) == (64, 32) and "ln1_g" not in a.weights and a.critic_l2_reg == 0.0 and a.clip_norm is None
+                and not a.popart)
+
+    @staticmethod
+    def _arrays(a):
+        return (a.actor_flat, a.critic_flat, a.target_actor_flat, a.target_critic_flat, *a._adam_actor, *a._adam_critic, a._adam_t)
+
+    def _fusable(self, ptrs):
+        ag = self.agents
+        return (not self._forced_elsewhere() and all(self._shipped_shape(a) for a in ag)
+                and all(a.obs_dim == ag[0].obs_dim and a.lastLayerTanh == ag[0].lastLayerTanh for a in ag)
+                and all((a.obs_rms is None) == (ag[0].obs_rms is None) for a in ag)
+                and len(set(ptrs)) == len(ptrs))
+
+    # ---- the two public calls --------------------------------------------------------------------
+    def _iters(self, n_iters):
+        if n_iters is None:
+            return [int(a.num_train_iterations) for a in self.agents]
+        if isinstance(n_iters, (int, np.integer)):
+            return [int(n_iters)] * len(self.agents)
+        n = [int(x) for x in n_iters]
+        if len(n) != len(self.agents) or min(n) < 0:
+            raise ValueError("n_iters: None, one count, or one count >= 0 per agent")
+        return n
+
+    def train_from(self, replays, n_iters=None, copy=False):
+        """``agent.train_from(replay, n_iters)`` for every (agent, :class:`DeviceReplayBuffer`) pair -> list of the loss
+        tensors [n_iters_p, 2]; None for an agent whose ring holds fewer than ``batch_size`` records (it is left exactly as
+        it is).  ``n_iters``: None (each agent's ``num_train_iterations``), one count, or one per agent.  Every ring's index
+        stream (``seed``, batches drawn so far) moves exactly as its own ``sample_indices`` would move it."""
+        replays = list(replays)
+        if len(replays) != len(self.agents):
+            raise ValueError("one replay ring per agent")
+        n = [k if len(r) >= a.batch_size else 0 for k, r, a in zip(self._iters(n_iters), replays, self.agents)]
+        views = [(r.s, r.a, r.r, r.t, r.s2) for r in replays]
+        if not self._prepare(views, n, None):
+            return [a.train_from(r, k) if k > 0 else None for a, r, k in zip(self.agents, replays, n)]
+        st = self._state
+        if st["active"]:
+            with torch.cuda.device(self.device):
+                if self._keys_event is not None:
+                    self._keys_event.synchronize()           # the last upload has left the pinned keys
+                for slot, p in enumerate(st["active"]):
+                    k = st["keys"][slot]
+                    k.seed, k.counter0, k.size = replays[p].take_sample_key(n[p], self.B)
+                st["d_keys"].copy_(st["h_keys"], non_blocking=True)
+                self._keys_event = torch.cuda.Event()
+                self._keys_event.record()
+                _ffi.check(self.lib.ssc_replay_sample_many(st["h_keys"].data_ptr(), st["d_keys"].data_ptr(), len(st["active"]),
+                                                           st["n_max"], self.B, _ffi.ptr(st["idx"]), _ffi.stream(self.device)))
+        return self._launch(copy)
+
+    def train_on(self, views, batch_idx, n_iters, copy=False):
+        """The index-explicit form: ``views[p]`` = agent p's (s, a, r, t, s2) device arrays, ``batch_idx[p]`` int32
+        [n_iters[p], 64] (ignored where ``n_iters[p]`` is 0) -> list of loss tensors, None where ``n_iters[p]`` is 0."""
+        n = self._iters(n_iters)
+        views, batch_idx = [tuple(v) for v in views], list(batch_idx)
+        if len(views) != len(self.agents) or len(batch_idx) != len(self.agents):
+            raise ValueError("one set of replay arrays and one index tensor per agent")
+        for a, k, idx in zip(self.agents, n, batch_idx):
+            if k > 0 and (tuple(idx.shape) != (k, a.batch_size) or idx.dtype != torch.int32 or not idx.is_contiguous()):
+                raise ValueError(f"batch_idx must be contiguous int32 [{k}, {a.batch_size}]")
+        if not self._prepare(views, n, batch_idx):
+            return [a.train_on(*v, idx, k) if k > 0 else None for a, v, idx, k in zip(self.agents, views, batch_idx, n)]
+        return self._launch(copy)
+
+    # ---- descriptors -----------------------------------------------------------------------------
+    def _prepare(self, views, n, batch_idx):
+        """Decide the way of this call and bring the launch descriptors up to date -> ``fused``."""
+        ag = self.agents
+        ptrs = [t.data_ptr() for a in ag for t in self._arrays(a)]
+        rms = [None if a.obs_rms is None else a._rms_block().data_ptr() for a in ag]
+        sig = (self._forced_elsewhere(), tuple(ptrs), tuple(rms), tuple(n),
+               tuple((v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(), v[4].data_ptr(), v[0].shape[0]) for v in views),
+               None if batch_idx is None else tuple(idx.data_ptr() if k > 0 else 0 for idx, k in zip(batch_idx, n)),
+               tuple((a.gamma, a.tau, a.actor_lr, a.critic_lr, a.obs_dim, a.lastLayerTanh, a.batch_size) for a in ag),
+               torch.cuda.current_stream(self.device).cuda_stream)
+        if sig == self._sig:
+            return self.fused
+        self._sig, self._state = sig, None
+        self.fused = self._fusable(ptrs)
+        if not self.fused:
+            return False
+        P, B = len(ag), self.B
+        active = [p for p in range(P) if n[p] > 0]
+        st = dict(active=active, n=list(n), n_max=max(n) if active else 0)
+        with torch.cuda.device(self.device):
+            st["losses"] = torch.empty((sum(n), 2), dtype=torch.float32, device=self.device)
+            if batch_idx is None and active:      # our own draw: rows [slot][n_max][64], agent p reads its first n[p] batches
+                st["idx"] = torch.empty((len(active), st["n_max"], B), dtype=torch.int32, device=self.device)
+                st["h_keys"] = torch.empty(len(active) * ctypes.sizeof(_ffi.ReplaySampleKey), dtype=torch.uint8).pin_memory()
+                st["d_keys"] = torch.empty(st["h_keys"].numel(), dtype=torch.uint8, device=self.device)
+                st["keys"] = (_ffi.ReplaySampleKey * len(active)).from_address(st["h_keys"].data_ptr())
+            items = (_ffi.DdpgManyItem * P)()
+            off, rows = 0, []
+            for p, a in enumerate(ag):
+                it, v = items[p], views[p]
+                it.ddpg = a.ddpg_desc()
+                it.replay = _ffi.ReplayView(*(x.data_ptr() for x in v), v[0].shape[0])
+                it.n_iters = n[p]
+                rows.append(st["losses"][off:off + n[p]] if n[p] > 0 else None)
+                if n[p] > 0:
+                    it.d_losses = rows[-1].data_ptr()
+                    it.d_batch_idx = (st["idx"][active.index(p)] if batch_idx is None else batch_idx[p]).data_ptr()
+                it.d_rms = rms[p]
+                off += n[p]
+            st["rows"], nbytes = rows, ctypes.sizeof(items)
+            if self._items_event is not None:
+                self._items_event.synchronize()
+            st["h_items"] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            ctypes.memmove(st["h_items"].data_ptr(), items, nbytes)
+            st["d_items"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            st["d_items"].copy_(st["h_items"], non_blocking=True)
+            self._items_event = torch.cuda.Event()
+            self._items_event.record()
+        self._state = st
+        return True
+
+    def _launch(self, copy):
+        st = self._state
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_ddpg_train_many(st["h_items"].data_ptr(), st["d_items"].data_ptr(), len(self.agents),
+                                                    _ffi.stream(self.device)))
+            if not copy:
+                return list(st["rows"])
+            block, out, off = st["losses"].clone(), [], 0
+            for k in st["n"]:
+                out.append(block[off:off + k] if k > 0 else None)
+                off += k
+            return out
+
+
 # ---------------------------------------------------------------------------- navigator --
 def add_noise(data_inp, noiseToSignal, rng=None):
     """NN_Dynamics_Model/helper_funcs.py:10-17: per column, Gaussian noise of std ``mean(column) * noiseToSignal``

@@ -83,6 +83,10 @@ int ddpg_train_fixed(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const in
 int ddpg_train_fixed_tiled(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                            float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms);
 
+// a population of batch-64 agents of the shipped shape, one workgroup each (ssc_ddpg_train_many validated the items)
+int ddpg_train_fixed_many(const ssc_ddpg_many_item *d_items, int32_t n_agents, int obs_dim, bool last_layer_tanh, bool rms,
+                          hipStream_t stream);
+
 // ddpg_train_wide.hip: any layer sizes / batch sizes, batch tiled over workgroups
 size_t ddpg_wide_workspace_bytes(const ssc_ddpg_desc *d);
 // The apply pass over `n_blocks` gradient partials laid out [n_blocks][n_params] at the start of the workspace, loss

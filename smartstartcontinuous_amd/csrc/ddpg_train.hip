@@ -19,7 +19,11 @@
 #include "actor_device.h"
 #include "ddpg_device.h"
 #include "ssc_host.h"
+#include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <utility>
+#include <vector>
 
 namespace ssc {
 
@@ -777,6 +781,48 @@ extern "C" int ssc_ddpg_train_ws_popart(const ssc_ddpg_desc *d, const ssc_replay
     if (rc != DDPG_GO) return rc;
     return ddpg_train_wide_popart(d, rp, d_batch_idx, n_iters, d_losses, d_workspace, workspace_bytes, as_stream(stream), d_rms,
                                   d_ret_rms);
+}
+
+// A population in one launch, one workgroup per agent (ddpg_train_fixed.hip).  Everything is decided on the host copy of
+// the items before any HIP call.
+extern "C" int ssc_ddpg_train_many(const ssc_ddpg_many_item *h_items, const ssc_ddpg_many_item *d_items, int32_t n_agents,
+                                   ssc_stream_t stream) {
+    SSC_REQUIRE(n_agents >= 1, "ssc_ddpg_train_many: n_agents %d < 1", n_agents);
+    SSC_REQUIRE(h_items != nullptr && d_items != nullptr, "ssc_ddpg_train_many: NULL item array");
+    const ssc_ddpg_desc &d0 = h_items[0].ddpg;
+    const bool rms = h_items[0].d_rms != nullptr;
+    bool any = false;
+    std::vector<std::pair<const void *, int>> owned;   // (array, agent) of every parameter / optimiser array
+    owned.reserve((size_t)n_agents * 10);
+    for (int p = 0; p < n_agents; ++p) {
+        const ssc_ddpg_many_item &it = h_items[p];
+        const ssc_ddpg_desc *d = &it.ddpg;
+        char who[48];
+        snprintf(who, sizeof who, "ssc_ddpg_train_many: agent %d", p);
+        const int rc = ddpg_check(who, d, &it.replay, it.d_batch_idx, it.n_iters);
+        if (rc != DDPG_GO && rc != SSC_OK) return rc;
+        if (!ddpg_fixed_shape(d) || !ddpg_narrow(d))
+            return set_error(SSC_EUNSUPPORTED, "%s: only the shipped shape trains as a population (64-32 actor and critic, batch 64, "
+                                               "act_dim 1, obs_dim 2 or 3, no LayerNorm / critic_l2_reg / clip_norm); train it alone "
+                                               "with ssc_ddpg_train_ws", who);
+        SSC_REQUIRE(d->obs_dim == d0.obs_dim && (d->last_layer_tanh != 0) == (d0.last_layer_tanh != 0),
+                    "%s: obs_dim %d / last_layer_tanh %d differ from agent 0's %d / %d (one kernel instantiation per launch)", who,
+                    d->obs_dim, d->last_layer_tanh, d0.obs_dim, d0.last_layer_tanh);
+        SSC_REQUIRE((it.d_rms != nullptr) == rms, "%s: d_rms is %s, agent 0's is not (statistics for all agents or for none)", who,
+                    it.d_rms ? "set" : "NULL");
+        any = any || it.n_iters > 0;
+        for (const void *a : {(const void *)d->actor, (const void *)d->critic, (const void *)d->target_actor,
+                              (const void *)d->target_critic, (const void *)d->adam_m_actor, (const void *)d->adam_v_actor,
+                              (const void *)d->adam_m_critic, (const void *)d->adam_v_critic, (const void *)d->adam_t})
+            if (a != nullptr) owned.emplace_back(a, p);   // (NULL: an agent with n_iters == 0 may bring none)
+    }
+    // two workgroups on one array would race without a sign of it
+    std::sort(owned.begin(), owned.end());
+    for (size_t k = 1; k < owned.size(); ++k)
+        SSC_REQUIRE(owned[k].first != owned[k - 1].first, "ssc_ddpg_train_many: agents %d and %d share a parameter / optimiser array",
+                    owned[k - 1].second, owned[k].second);
+    if (!any) return SSC_OK;
+    return ddpg_train_fixed_many(d_items, n_agents, d0.obs_dim, d0.last_layer_tanh != 0, rms, as_stream(stream));
 }
 
 static bool ddpg_desc_sized(const ssc_ddpg_desc *d) {

@@ -246,8 +246,11 @@ __device__ __forceinline__ float small_grad(const float *lds, const SmallElem &e
 //
 // Rms (normalize_observations): the RunningMeanStd block; its loads go out with the parameter images, mean / std are
 // derived once per launch, and obs0 / obs1 enter the networks as clip((x - mean) / std) (actor_device.h).
+//
+// The body of a workgroup, shared by the kernels below: `g` is the launch's kernarg (ddpg_train_fixed_kernel) or this
+// workgroup's agent out of a population (ddpg_train_fixed_many_kernel).
 template <int O, bool TANH2, bool TILED, class... Rms>
-__global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms... rms) {
+__device__ __forceinline__ void ddpg_train_fixed_body(const FixedArgs g, Rms... rms) {
     using NA = Net<O, H1>;
     using NC = Net<O, H1 + 1>;
     using R = Rows<O>;
@@ -576,6 +579,43 @@ __global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms..
     if (tid == 0) { d.adam_t[0] = clk.tA; d.adam_t[1] = clk.tC; }
 }
 
+template <int O, bool TANH2, bool TILED, class... Rms>
+__global__ __launch_bounds__(kT) void ddpg_train_fixed_kernel(FixedArgs g, Rms... rms) {
+    ddpg_train_fixed_body<O, TANH2, TILED>(g, rms...);
+}
+
+// A population (ssc_ddpg_train_many): workgroup p runs agent p's iterations exactly as the kernel above runs them in a
+// launch of its own.  The item sits at a workgroup-uniform address and is read before anything is written, so its fetch is
+// scalar loads into SGPRs -- where the kernarg of the single launch lives too.  Workgroups share nothing: the host refuses
+// two agents on one parameter / optimiser array.  The image fills the LDS: one workgroup per CU, more than 256 agents queue.
+// Known cost: pointers read out of the item are generic to the compiler, so the body's global accesses are FLAT
+// instructions here; they count on lgkmcnt too and the body's LDS-only barriers wait for the batch prefetch (~0.5 us / iteration).
+template <int O, bool TANH2, bool RMS>
+__global__ __launch_bounds__(kT) void ddpg_train_fixed_many_kernel(const ssc_ddpg_many_item *__restrict__ items) {
+    const ssc_ddpg_many_item item = items[blockIdx.x];
+    if (item.n_iters == 0) return;
+    const FixedArgs g{item.ddpg, item.replay, item.d_batch_idx, item.d_losses, item.n_iters, 1.0f / (float)kB, nullptr, nullptr};
+    if constexpr (RMS) ddpg_train_fixed_body<O, TANH2, false>(g, item.d_rms);
+    else ddpg_train_fixed_body<O, TANH2, false>(g);
+}
+
+constexpr size_t fixed_lds_bytes(int O) {
+    return O == 2 ? ((size_t)Rows<2>::total * kP + 2 * (Net<2, H1>::size + Net<2, H1 + 1>::size)) * sizeof(float)
+                  : ((size_t)Rows<3>::total * kP + 2 * (Net<3, H1>::size + Net<3, H1 + 1>::size)) * sizeof(float);
+}
+
+template <int O, bool TANH2, bool RMS>
+int launch_fixed_many(const ssc_ddpg_many_item *d_items, int32_t n_agents, hipStream_t stream) {
+    constexpr size_t lds = fixed_lds_bytes(O);
+    static_assert(lds <= 160 * 1024 - 256, "activation rows + parameter images must fit the LDS");
+    int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_train_fixed_many_kernel<O, TANH2, RMS>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                       "hipFuncSetAttribute(ddpg_train_fixed_many_kernel)");
+    if (rc) return rc;
+    hipLaunchKernelGGL((ddpg_train_fixed_many_kernel<O, TANH2, RMS>), dim3((unsigned)n_agents), dim3(kT), lds, stream, d_items);
+    return check_launch("ssc_ddpg_train_many");
+}
+
 template <int O, bool TANH2, bool TILED = false, class... Rms>
 int launch_fixed(const FixedArgs &g, hipStream_t stream, unsigned tiles = 1, Rms... rms) {
     const size_t lds = ((size_t)Rows<O>::total * kP + 2 * (Net<O, H1>::size + Net<O, H1 + 1>::size)) * sizeof(float);
@@ -628,6 +668,16 @@ int ddpg_train_fixed(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const in
     }
     if (d->obs_dim == 2) return t2 ? launch_fixed<2, true>(g, stream) : launch_fixed<2, false>(g, stream);
     return t2 ? launch_fixed<3, true>(g, stream) : launch_fixed<3, false>(g, stream);
+}
+
+// arguments already validated by ssc_ddpg_train_many: obs_dim, last_layer_tanh and rms hold for every agent
+int ddpg_train_fixed_many(const ssc_ddpg_many_item *d_items, int32_t n_agents, int obs_dim, bool t2, bool rms, hipStream_t stream) {
+    if (rms) {
+        if (obs_dim == 2) return t2 ? launch_fixed_many<2, true, true>(d_items, n_agents, stream) : launch_fixed_many<2, false, true>(d_items, n_agents, stream);
+        return t2 ? launch_fixed_many<3, true, true>(d_items, n_agents, stream) : launch_fixed_many<3, false, true>(d_items, n_agents, stream);
+    }
+    if (obs_dim == 2) return t2 ? launch_fixed_many<2, true, false>(d_items, n_agents, stream) : launch_fixed_many<2, false, false>(d_items, n_agents, stream);
+    return t2 ? launch_fixed_many<3, true, false>(d_items, n_agents, stream) : launch_fixed_many<3, false, false>(d_items, n_agents, stream);
 }
 
 }  // namespace ssc

@@ -240,10 +240,8 @@ __global__ __launch_bounds__(kBlock) void episode_path_kernel(EpisodePathArgs a)
 // rounds: in a round every unresolved slot draws its next attempt and accepts unless the candidate equals an
 // already accepted index or the candidate of a lower-numbered unresolved slot of the same round
 // (oracle: replay_sample_indices).
-__global__ __launch_bounds__(64) void replay_sample_kernel(uint64_t seed, uint64_t counter0, int64_t size, int32_t batch,
-                                                            int32_t *__restrict__ idx) {
+__device__ __forceinline__ void replay_sample_wave(uint64_t seed, uint64_t bid, int64_t size, int32_t batch, int32_t *__restrict__ idx) {
     const int lane = threadIdx.x;
-    const uint64_t bid = counter0 + blockIdx.x;
     const bool slot = lane < batch;
     bool done = !slot;
     uint32_t val = 0xFFFFFFFFu;
@@ -260,7 +258,21 @@ __global__ __launch_bounds__(64) void replay_sample_kernel(uint64_t seed, uint64
         }
         if (!done && !clash) { val = cand; done = true; }
     }
-    if (slot) idx[(int64_t)blockIdx.x * batch + lane] = (int32_t)val;
+    if (slot) idx[lane] = (int32_t)val;
+}
+
+__global__ __launch_bounds__(64) void replay_sample_kernel(uint64_t seed, uint64_t counter0, int64_t size, int32_t batch,
+                                                            int32_t *__restrict__ idx) {
+    replay_sample_wave(seed, counter0 + blockIdx.x, size, batch, idx + (int64_t)blockIdx.x * batch);
+}
+
+// The same wave for a population of rings: blockIdx.y = agent, whose (seed, counter0, size) come from keys[agent] (a
+// workgroup-uniform read) and whose batches go to rows [agent][blockIdx.x] of idx -- the Philox keys, hence the indices,
+// of ssc_replay_sample called once per ring.
+__global__ __launch_bounds__(64) void replay_sample_many_kernel(const ssc_replay_sample_key *__restrict__ keys, int32_t batch,
+                                                                 int32_t *__restrict__ idx) {
+    const ssc_replay_sample_key k = keys[blockIdx.y];
+    replay_sample_wave(k.seed, k.counter0 + blockIdx.x, k.size, batch, idx + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * batch);
 }
 
 // Batches of 65 .. 4096 indices (the multi-workgroup learner's batch sizes): ONE workgroup per batch, slot s served by
@@ -473,6 +485,26 @@ int ssc_replay_sample(uint64_t seed, uint64_t counter0, int64_t size, int32_t n_
     hipLaunchKernelGGL(replay_sample_kernel, dim3(n_batches), dim3(64), 0, as_stream(stream), seed, counter0, size,
                        batch_size, d_idx);
     return check_launch("ssc_replay_sample");
+}
+
+int ssc_replay_sample_many(const ssc_replay_sample_key *h_keys, const ssc_replay_sample_key *d_keys, int32_t n_agents,
+                           int32_t n_batches, int32_t batch_size, int32_t *d_idx, ssc_stream_t stream) {
+    SSC_REQUIRE(n_agents >= 1, "ssc_replay_sample_many: n_agents %d < 1", n_agents);
+    SSC_REQUIRE(h_keys != nullptr && d_keys != nullptr, "ssc_replay_sample_many: NULL key array");
+    SSC_REQUIRE(n_batches >= 0 && batch_size >= 1, "ssc_replay_sample_many: n_batches %d / batch_size %d", n_batches, batch_size);
+    if (batch_size > 64)
+        return set_error(SSC_EUNSUPPORTED, "ssc_replay_sample_many: batch_size %d > 64 (the one-wave kernel; ssc_replay_sample draws "
+                                           "larger batches ring by ring)", batch_size);
+    if (n_agents > 65535)
+        return set_error(SSC_EUNSUPPORTED, "ssc_replay_sample_many: %d agents > 65535 (one grid row each)", n_agents);
+    for (int p = 0; p < n_agents; ++p)
+        SSC_REQUIRE(h_keys[p].size >= batch_size && h_keys[p].size <= 0x7fffffffLL,
+                    "ssc_replay_sample_many: agent %d: %lld records cannot give %d distinct indices", p, (long long)h_keys[p].size,
+                    batch_size);
+    if (n_batches == 0) return SSC_OK;
+    SSC_REQUIRE(d_idx != nullptr, "ssc_replay_sample_many: d_idx NULL");
+    hipLaunchKernelGGL(replay_sample_many_kernel, dim3(n_batches, n_agents), dim3(64), 0, as_stream(stream), d_keys, batch_size, d_idx);
+    return check_launch("ssc_replay_sample_many");
 }
 
 }  // extern "C"

@@ -351,6 +351,16 @@ class DeviceReplayBuffer:
         self._batches_drawn += n_batches
         return idx
 
+    def take_sample_key(self, n_batches, batch_size):
+        """(seed, counter0, size) under which :meth:`sample_indices` would draw its next ``n_batches`` batches, and the
+        batch counter advanced as if it had: for a caller that draws them itself, with the batches of other rings in one
+        launch (``ssc_replay_sample_many``; ``agents.DDPGPopulation``)."""
+        if len(self) < batch_size:
+            raise ValueError("fewer records than one batch (the reference trains only once len >= batch_size)")
+        key = (self.seed, self._batches_drawn, len(self))
+        self._batches_drawn += int(n_batches)
+        return key
+
     def sample_batch(self, batch_size):
         """(s, a, r, t, s2) device tensors of one batch -- the ReplayBuffer.sample_batch tuple."""
         i = self.sample_indices(1, batch_size)[0].long()

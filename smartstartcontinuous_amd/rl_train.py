@@ -591,6 +591,74 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     return summary, losses, replay
 
 
+def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
+                                 replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
+                                 drain_every=None, on_chunk=None, stats_every=None, eval_env=None, eval_every=None,
+                                 eval_steps=None):
+    """The synchronous :func:`rl_train_vec_ddpg` for P (env, agent) pairs -- seeds x hyper-parameter grids, the reference's
+    experimenter.py fan-out -- with ONE learner launch per chunk for the whole population
+    (:class:`agents.DDPGPopulation`): per chunk every pair rolls out, decays its epsilon, appends to its own replay ring
+    and updates its observation statistics exactly as the single loop does, then ``population.train_from`` trains all
+    agents.  Every pair's parameters, losses, Summary and final epsilon are bit for bit those of its own
+    ``rl_train_vec_ddpg`` run with the same arguments.  ``seed``: one replay seed for all pairs or one per pair.
+    A population the one launch does not serve (see :class:`agents.DDPGPopulation`: another shape, Pop-Art, mixed
+    normalize_observations, ...) trains agent by agent.  The rollouts and appends are still P launches each.
+
+    Not in this form: ``overlap``, agents with parameter-space noise, ``stats_every`` and ``eval_env``
+    (NotImplementedError).  ``on_chunk(i, chunks, envs)`` gets the lists.  Returns [(Summary, losses per chunk, replay)]
+    per pair."""
+    from .agents import DDPGPopulation
+    envs, agents = list(envs), list(agents)
+    if len(envs) != len(agents) or not agents:
+        raise ValueError("one env per agent, at least one pair")
+    for what, on in (("overlap=True", overlap), ("stats_every", stats_every is not None),
+                     ("eval_env / eval_every / eval_steps", not (eval_env is None and eval_every is None and eval_steps is None)),
+                     ("an agent with parameter-space noise", any(getattr(a, "param_noise", None) is not None for a in agents))):
+        if on:
+            raise NotImplementedError(f"rl_train_vec_ddpg_population: {what} is not part of the population loop; "
+                                      "run that pair through rl_train_vec_ddpg")
+    P = len(agents)
+    seeds = [int(seed)] * P if isinstance(seed, (int, np.integer)) else [int(s) for s in seed]
+    if len(seeds) != P:
+        raise ValueError("seed: one value or one per pair")
+    population = DDPGPopulation(agents)
+    summaries = [Summary("vec_ddpg_" + env.spec.id) for env in envs]
+    bufs = [vec_loop_buffers(env, chunk_steps, replay_capacity, ring_capacity, s, track_episodes) for env, s in zip(envs, seeds)]
+    rings, chunks, replays = ([b[k] for b in bufs] for k in range(3))
+    losses = [[] for _ in range(P)]
+    every = [default_drain_every(ring_capacity, env.n, chunk_steps) if drain_every is None else drain_every for env in envs]
+    schedules = [epsilon_schedule(agent, env.n, env.device) for env, agent in zip(envs, agents)]
+    finished0 = [float(env.stats[3].item()) for env in envs]
+    dropped = [0] * P
+
+    def drain(p):
+        (_ids, lens, rets), d = rings[p].drain()
+        dropped[p] += d
+        summaries[p].extend_records(lens, rets)
+
+    pds = [env.policy_desc(agent.as_policy(device_epsilon=True)) for env, agent in zip(envs, agents)]
+    for i in range(num_chunks):
+        for p, (env, agent) in enumerate(zip(envs, agents)):
+            out = env.rollout(chunk_steps, out=chunks[p], ring=rings[p], policy_desc=pds[p])
+            schedules[p].update(env.stats[3:4], finished0[p])
+            replays[p].append_chunk(out, reward_scale=agent.reward_scale, last_steps=replay_last_steps)
+            update_obs_rms(agent, out, replay_last_steps)
+        for p, l in enumerate(population.train_from(replays, train_iters, copy=True)):
+            if l is not None:
+                losses[p].append(l)
+        if on_chunk is not None:
+            on_chunk(i, chunks, envs)
+        for p in range(P):
+            if (i + 1) % every[p] == 0:
+                drain(p)
+    for p, agent in enumerate(agents):
+        drain(p)
+        summaries[p].dropped_episode_records = dropped[p]
+        _g, (eps,) = schedules[p].read()
+        agent.decaying_ou_action_noise.epsilon = eps
+    return [(summaries[p], losses[p], replays[p]) for p in range(P)]
+
+
 def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capacity=1 << 20, train_iters=None,
                             replay_last_steps=None, seed=0, ring_capacity=1 << 20, refresh_every=1, graph=True,
                             on_chunk=None, aggregate_every=0, aggregate_kwargs=None, overlap_selection=False):
