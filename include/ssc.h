@@ -704,6 +704,109 @@ int ssc_replay_sample_many(const ssc_replay_sample_key *h_keys, const ssc_replay
                            int32_t n_batches, int32_t batch_size, int32_t *d_idx, ssc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The rest of a population chunk in one launch each: rollout, epsilon decay, replay append and
+ * observation statistics of P (env set, agent) PAIRS
+ * -------------------------------------------------------------------------------------
+ * Each entry point below replaces P calls of a single one and writes, bit for bit, what those calls write (one
+ * exception: the f64 reward sum d_stats[0] of a pair with more than one workgroup is an atomic sum in both forms, so its
+ * last bits depend on arrival order in both).  The conventions are ssc_ddpg_train_many's: a host array that is validated
+ * before any HIP call, the caller's device copy of the same bytes, complete on `stream` before the call; the library
+ * copies nothing; the pair's index -- or both indices -- is in ssc_last_error().  The structs are declared tag first;
+ * tests/test_rollout_many_host.py holds their sizes and offsets to the ctypes mirrors.
+ *
+ * What changes with every chunk lives in a second, small array used like ssc_replay_sample_key: 16 bytes per pair, so that
+ * a steady-state chunk uploads the cursors and nothing else.  ssc_rollout_many reads step0, ssc_replay_append_many
+ * replay_start, from the same array. */
+struct ssc_pair_cursor {
+    uint64_t step0;        /* ssc_rollout's step0 of this chunk */
+    int64_t  replay_start; /* ssc_replay_append's start: records appended to the pair's ring so far */
+};
+typedef struct ssc_pair_cursor ssc_pair_cursor;
+
+/* What one ssc_rollout_rms call takes, except step0 (the pair's cursor) and K (one value for the population). */
+struct ssc_rollout_many_item {
+    ssc_env_params     params;
+    ssc_policy_desc    policy;
+    int64_t            n;        /* >= 1, per pair */
+    ssc_rollout_state  state;
+    ssc_transition_log log;      /* read when has_log */
+    ssc_episode_ring   ring;     /* read when has_ring */
+    int32_t            has_log;  /* all pairs or none */
+    int32_t            has_ring; /* per pair */
+    double            *d_stats;  /* [4] or NULL */
+    uint64_t           seed, env_id0;
+    const double      *d_rms;    /* normalize_observations block or NULL -- all pairs or none */
+};
+typedef struct ssc_rollout_many_item ssc_rollout_many_item;
+
+/* ssc_rollout_rms for n_pairs pairs in one launch: grid row p runs pair p's workgroups (grid x = the largest pair's
+ * workgroup count; the others' surplus workgroups exit at once).  Replaces one ssc_rollout / ssc_rollout_rms per pair.
+ * The launch serves ONE kernel instantiation, the ones the population loop's agents select today: SSC_POLICY_ACTOR at
+ * SSC_PREC_BF16_MFMA with h1 <= 64, h2 <= 32, act_dim 1, no LayerNorm (anything else, the random policy included:
+ * SSC_EUNSUPPORTED naming the pair) -- on MountainCar the straight-line fused policy (unit action bounds, noise on, inert
+ * or normalised clip) or the generic MFMA policy, on Pendulum the generic one.  Uniform over the population (SSC_EINVAL
+ * naming the first pair that differs from pair 0): the env kind, which of the two policies ssc_rollout would choose,
+ * last_layer_tanh for the fused policy, d_rms (all or none), has_log (all or none).  One pair whose log columns are not
+ * within 4 GB above obs[0] sends all pairs to the generic log stores (the same values).  Free per pair: n, env
+ * constants, OU constants and d_epsilon, action bounds inside the class, obs_clip, seed, env_id0, has_ring.
+ * No two pairs share a state column, a log column, an episode ring array or cursor, or a d_stats block (SSC_EINVAL naming
+ * both).  K == 0: SSC_OK without a launch. */
+int ssc_rollout_many(const ssc_rollout_many_item *h_items, const ssc_rollout_many_item *d_items,
+                     const ssc_pair_cursor *h_cursors, const ssc_pair_cursor *d_cursors, int32_t n_pairs, int32_t K,
+                     ssc_stream_t stream);
+
+/* What one ssc_replay_append call takes; start is the pair's cursor (replay_start).  K is already reduced to the steps to
+ * store and the log pointers advanced past the steps to skip (DeviceReplayBuffer.append_chunk's last_steps). */
+struct ssc_replay_append_item {
+    ssc_replay_ring    ring;
+    ssc_transition_log log;
+    int32_t            K;
+    int64_t            n;
+    float              reward_scale;
+};
+typedef struct ssc_replay_append_item ssc_replay_append_item;
+
+/* ssc_replay_append for n_pairs rings in one launch (replaces one call per pair): record positions are exactly
+ * (start + k * n + e) % capacity.  obs_dim is one value for the population and the episode index (ep_steps / ep_run) is
+ * kept for all rings or for none (SSC_EINVAL naming the pair); every item passes ssc_replay_append's checks and no ring
+ * array is shared by two pairs (SSC_EINVAL naming both).  Nothing to append anywhere: SSC_OK without a launch. */
+int ssc_replay_append_many(const ssc_replay_append_item *h_items, const ssc_replay_append_item *d_items,
+                           const ssc_pair_cursor *h_cursors, const ssc_pair_cursor *d_cursors, int32_t n_pairs,
+                           ssc_stream_t stream);
+
+/* One ssc_decay_schedule call's arguments by value (factor / floor are part of the item). */
+struct ssc_decay_item {
+    const double *d_finished;
+    double        finished0, per_generation;
+    int32_t       n_sched;   /* 0..4 */
+    double        factor[4], floor[4];
+    double       *d_state;   /* [1 + n_sched] */
+    float        *d_out[4];  /* each may be NULL */
+};
+typedef struct ssc_decay_item ssc_decay_item;
+
+/* ssc_decay_schedule for n_pairs schedule sets in one launch, one thread each (replaces one call per pair).  Nothing in
+ * an item changes from chunk to chunk: no cursor.  No d_state shared by two pairs. */
+int ssc_decay_schedule_many(const ssc_decay_item *h_items, const ssc_decay_item *d_items, int32_t n_pairs, ssc_stream_t stream);
+
+/* What one ssc_obs_rms_update call takes, with the pair's own workspace. */
+struct ssc_obs_rms_item {
+    ssc_transition_log log;
+    int32_t            k0, K;
+    int64_t            n;
+    double            *d_rms;
+    void              *d_workspace;
+    size_t             workspace_bytes; /* >= ssc_obs_rms_update_workspace_bytes(obs_dim) */
+};
+typedef struct ssc_obs_rms_item ssc_obs_rms_item;
+
+/* ssc_obs_rms_update for n_pairs blocks in two launches (replaces two per pair): every pair's rows are partitioned exactly
+ * as its own call partitions them (the partition is derived from (n, K - k0) alone) and summed in the same order, so every
+ * bit of every block is that of the single call.  No statistics block or workspace shared by two pairs. */
+int ssc_obs_rms_update_many(int32_t obs_dim, const ssc_obs_rms_item *h_items, const ssc_obs_rms_item *d_items, int32_t n_pairs,
+                            ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Adaptive parameter-space noise (ddpg_editted.py:47-60, 151-166, 255-259, 360-385)
  * -------------------------------------------------------------------------------------
  * A perturbed actor is a second flat parameter array [W1|b1|(beta1|gamma1)|W2|b2|(beta2|gamma2)|W3|b3] that the

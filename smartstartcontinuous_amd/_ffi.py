@@ -155,6 +155,30 @@ class ReplaySampleKey(Structure):
     _fields_ = [("seed", c_uint64), ("counter0", c_uint64), ("size", c_int64)]
 
 
+class PairCursor(Structure):
+    _fields_ = [("step0", c_uint64), ("replay_start", c_int64)]
+
+
+class RolloutManyItem(Structure):
+    _fields_ = [("params", EnvParams), ("policy", PolicyDesc), ("n", c_int64), ("state", RolloutState), ("log", TransitionLog),
+                ("ring", EpisodeRing), ("has_log", c_int32), ("has_ring", c_int32), ("d_stats", c_void_p), ("seed", c_uint64),
+                ("env_id0", c_uint64), ("d_rms", c_void_p)]
+
+
+class ReplayAppendItem(Structure):
+    _fields_ = [("ring", ReplayRing), ("log", TransitionLog), ("K", c_int32), ("n", c_int64), ("reward_scale", c_float)]
+
+
+class DecayItem(Structure):
+    _fields_ = [("d_finished", c_void_p), ("finished0", c_double), ("per_generation", c_double), ("n_sched", c_int32),
+                ("factor", c_double * 4), ("floor", c_double * 4), ("d_state", c_void_p), ("d_out", c_void_p * 4)]
+
+
+class ObsRmsItem(Structure):
+    _fields_ = [("log", TransitionLog), ("k0", c_int32), ("K", c_int32), ("n", c_int64), ("d_rms", c_void_p),
+                ("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
 # C struct -> its ctypes mirror: the struct-layout table (the tests compare sizeof / offsetof as the C compiler sees them)
 STRUCTS = {
     "ssc_env_params": EnvParams, "ssc_actor_desc": ActorDesc, "ssc_ou_desc": OuDesc, "ssc_policy_desc": PolicyDesc,
@@ -163,6 +187,8 @@ STRUCTS = {
     "ssc_mpc_nav_state": MpcNavState, "ssc_smartstart_step": SmartStartStep, "ssc_critic_desc": CriticDesc,
     "ssc_ddpg_desc": DdpgDesc, "ssc_replay_view": ReplayView, "ssc_replay_ring": ReplayRing,
     "ssc_mlp_train_desc": MlpTrainDesc, "ssc_ddpg_many_item": DdpgManyItem, "ssc_replay_sample_key": ReplaySampleKey,
+    "ssc_pair_cursor": PairCursor, "ssc_rollout_many_item": RolloutManyItem, "ssc_replay_append_item": ReplayAppendItem,
+    "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem,
 }
 
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
@@ -225,6 +251,11 @@ _SIGNATURES = {
     # a population of agents in one launch: host items / keys (validated) + the caller's device copy of the same bytes
     "ssc_ddpg_train_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "ssc_replay_sample_many": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    # the rest of a population chunk, one launch each: host items / cursors (validated) + the caller's device copies
+    "ssc_rollout_many": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "ssc_replay_append_many": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_decay_schedule_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_obs_rms_update_many": (c_int, [c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     # adaptive parameter-space noise: perturb a flat actor, adapt the device stddev
     "ssc_param_noise_perturb": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_uint64,
                                         c_uint64, c_void_p]),

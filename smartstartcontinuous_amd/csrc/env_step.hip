@@ -4,6 +4,11 @@
 // 65 536 envs one step touches 1.6 MB and is launch/L2-bound -- the
 // HBM-bound path is the fused K-step kernel in rollout.hip.  Elementwise, one thread per
 // env, coalesced dword accesses over the SoA state columns.
+#include <algorithm>
+#include <cstdio>
+#include <utility>
+#include <vector>
+
 #include "ssc_device.h"
 #include "ssc_host.h"
 
@@ -149,8 +154,7 @@ struct DecayArgs {
     float *out[4];
 };
 
-__global__ void decay_schedule_kernel(DecayArgs a) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void decay_schedule_one(const DecayArgs &a) {
     const double target = floor((*a.finished - a.finished0) / a.per_generation);
     const double applied = a.state[0];
     int64_t todo = (int64_t)(target - applied);
@@ -166,6 +170,25 @@ __global__ void decay_schedule_kernel(DecayArgs a) {
         if (a.out[i] != nullptr) *a.out[i] = (float)v;
     }
     if (todo > 0) a.state[0] = applied + (double)todo;
+}
+
+__global__ void decay_schedule_kernel(DecayArgs a) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    decay_schedule_one(a);
+}
+
+// ssc_decay_schedule_many: thread p runs pair p's schedule set (the item is DecayArgs field by field)
+__global__ __launch_bounds__(64) void decay_schedule_many_kernel(const ssc_decay_item *__restrict__ items, int32_t n_pairs) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n_pairs) return;
+    const ssc_decay_item &it = items[p];
+    if (it.n_sched == 0) return;     // (ssc_decay_schedule launches nothing for it)
+    DecayArgs a;
+    a.finished = it.d_finished; a.finished0 = it.finished0; a.per_generation = it.per_generation; a.n_sched = it.n_sched;
+    a.state = it.d_state;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { a.factor[i] = it.factor[i]; a.floor_[i] = it.floor[i]; a.out[i] = it.d_out[i]; }
+    decay_schedule_one(a);
 }
 
 }  // namespace ssc
@@ -273,6 +296,31 @@ int ssc_decay_schedule(const double *d_finished, double finished0, double per_ge
     }
     hipLaunchKernelGGL(decay_schedule_kernel, dim3(1), dim3(64), 0, as_stream(stream), a);
     return check_launch("ssc_decay_schedule");
+}
+
+int ssc_decay_schedule_many(const ssc_decay_item *h_items, const ssc_decay_item *d_items, int32_t n_pairs, ssc_stream_t stream) {
+    SSC_REQUIRE(n_pairs >= 1, "ssc_decay_schedule_many: n_pairs %d < 1", n_pairs);
+    SSC_REQUIRE(h_items != nullptr && d_items != nullptr, "ssc_decay_schedule_many: NULL item array");
+    std::vector<std::pair<const void *, int>> owned;   // (d_state, pair)
+    owned.reserve((size_t)n_pairs);
+    bool any = false;
+    for (int p = 0; p < n_pairs; ++p) {
+        const ssc_decay_item &it = h_items[p];
+        SSC_REQUIRE(it.d_finished != nullptr && it.d_state != nullptr, "ssc_decay_schedule_many: pair %d: NULL device pointer", p);
+        SSC_REQUIRE(it.n_sched >= 0 && it.n_sched <= 4, "ssc_decay_schedule_many: pair %d: n_sched = %d not in 0..4", p, it.n_sched);
+        SSC_REQUIRE(it.per_generation > 0.0, "ssc_decay_schedule_many: pair %d: per_generation must be positive", p);
+        for (int i = 0; i < it.n_sched; ++i)
+            SSC_REQUIRE(it.factor[i] >= 0.0, "ssc_decay_schedule_many: pair %d: negative factor", p);
+        any = any || it.n_sched > 0;
+        owned.emplace_back(it.d_state, p);
+    }
+    std::sort(owned.begin(), owned.end());
+    for (size_t k = 1; k < owned.size(); ++k)
+        SSC_REQUIRE(owned[k].first != owned[k - 1].first, "ssc_decay_schedule_many: pairs %d and %d share a d_state", owned[k - 1].second,
+                    owned[k].second);
+    if (!any) return SSC_OK;
+    hipLaunchKernelGGL(decay_schedule_many_kernel, dim3(blocks_for(n_pairs, 64)), dim3(64), 0, as_stream(stream), d_items, n_pairs);
+    return check_launch("ssc_decay_schedule_many");
 }
 
 }  // extern "C"

@@ -8,6 +8,11 @@
 //                       HBM-bound: 25 B read + 25 B written per record (MountainCar).
 //   ssc_replay_sample   minibatch indices, uniform WITHOUT replacement inside a batch (random.sample,
 //                       replay_buffer.py:79-83), one wave per batch, Philox-keyed (bit-exact with the oracle).
+#include <algorithm>
+#include <cstdio>
+#include <utility>
+#include <vector>
+
 #include "ssc_device.h"
 #include "ssc_host.h"
 
@@ -56,9 +61,10 @@ struct AppendRow {
     }
 };
 
+// blocks (of its own grid row) bx of the plain append: one thread per record
 template <int OD>
-__global__ __launch_bounds__(kBlock) void replay_append_kernel(ReplayAppendArgs g) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+__device__ __forceinline__ void replay_append_body(const ReplayAppendArgs &g, unsigned bx) {
+    const int64_t i = (int64_t)bx * kBlock + threadIdx.x;
     if (i >= g.count) return;
     const int64_t j = g.first + i;           // record number inside the chunk: step-major, then env
     const int64_t k = j / g.n, e = j - k * g.n;
@@ -68,12 +74,17 @@ __global__ __launch_bounds__(kBlock) void replay_append_kernel(ReplayAppendArgs 
     row.store(g, pos);
 }
 
+template <int OD>
+__global__ __launch_bounds__(kBlock) void replay_append_kernel(ReplayAppendArgs g) {
+    replay_append_body<OD>(g, blockIdx.x);
+}
+
 // The same append with the episode index (ssc_replay_ring::ep_steps / ep_run): one thread per env walks its column
 // of the chunk in step order (coalesced across envs on both sides), counting the steps of its running episode -- four
 // steps' reads in flight at a time.
 template <int OD>
-__global__ __launch_bounds__(kBlock) void replay_append_indexed_kernel(ReplayAppendArgs g, int32_t K) {
-    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+__device__ __forceinline__ void replay_append_indexed_body(const ReplayAppendArgs &g, int32_t K, unsigned bx) {
+    const int64_t e = (int64_t)bx * kBlock + threadIdx.x;
     if (e >= g.n) return;
     int32_t run = g.ring.ep_run[g.env_off + e];
     constexpr int kU = 4;
@@ -99,6 +110,40 @@ __global__ __launch_bounds__(kBlock) void replay_append_indexed_kernel(ReplayApp
         }
     }
     g.ring.ep_run[g.env_off + e] = run;
+}
+
+template <int OD>
+__global__ __launch_bounds__(kBlock) void replay_append_indexed_kernel(ReplayAppendArgs g, int32_t K) {
+    replay_append_indexed_body<OD>(g, K, blockIdx.x);
+}
+
+// What replay_append_impl hands the kernels for an unsharded append (n_total == n), from the call's arguments: on the host
+// for the single launch, on the device from a pair's item for ssc_replay_append_many -- integer arithmetic only.
+__host__ __device__ __forceinline__ void pack_append(const ssc_replay_ring &ring, const ssc_transition_log &log, int32_t K, int64_t n,
+                                                     int64_t start, float reward_scale, ReplayAppendArgs &g) {
+    g.ring = ring; g.log = log; g.n = n; g.n_total = n; g.env_off = 0;
+    g.row_stride = log.row_stride ? log.row_stride : n;
+    g.done_row_stride = log.done_row_stride ? log.done_row_stride : n;
+    const int64_t total = (int64_t)K * n;
+    g.count = total < ring.capacity ? total : ring.capacity;  // older records of the chunk would be overwritten anyway
+    g.first = total - g.count;
+    g.start = start; g.reward_scale = reward_scale;
+}
+
+// P appends in one launch (ssc_replay_append_many): blockIdx.y is the pair, whose item and cursor (workgroup-uniform: scalar
+// loads) give the arguments its own launch would get; grid x is the largest pair's block count and surplus blocks leave.
+template <int OD, bool INDEXED>
+__global__ __launch_bounds__(kBlock) void replay_append_many_kernel(const ssc_replay_append_item *__restrict__ items,
+                                                                    const ssc_pair_cursor *__restrict__ cursors) {
+    const ssc_replay_append_item &it = items[blockIdx.y];
+    const int64_t total = (int64_t)it.K * it.n;
+    if (total == 0) return;
+    const int64_t work = INDEXED ? it.n : (total < it.ring.capacity ? total : it.ring.capacity);
+    if ((int64_t)blockIdx.x * kBlock >= work) return;
+    ReplayAppendArgs g;
+    pack_append(it.ring, it.log, it.K, it.n, cursors[blockIdx.y].replay_start, it.reward_scale, g);
+    if constexpr (INDEXED) replay_append_indexed_body<OD>(g, it.K, blockIdx.x);
+    else replay_append_body<OD>(g, blockIdx.x);
 }
 
 // ---- smart-start index queries --------------------------------------------------------------------------------
@@ -355,8 +400,10 @@ using namespace ssc;
 
 extern "C" {
 
-static int replay_append_impl(const char *fn, const ssc_replay_ring *ring, const ssc_transition_log *log, int32_t K, int64_t n,
-                              int64_t start, int64_t n_total, int64_t env_off, float reward_scale, ssc_stream_t stream) {
+// the checks of one append that come before its arguments are packed; *work: there is something to append
+static int replay_append_check(const char *fn, const ssc_replay_ring *ring, const ssc_transition_log *log, int32_t K, int64_t n,
+                               int64_t start, int64_t n_total, int64_t env_off, bool *work) {
+    *work = false;
     SSC_REQUIRE(ring != nullptr && log != nullptr, "%s: NULL descriptor", fn);
     SSC_REQUIRE(ring->capacity > 0 && ring->obs_dim >= 1 && ring->obs_dim <= SSC_MAX_OBS && ring->act_dim == 1,
                 "%s: capacity %lld / obs_dim %d / act_dim %d not supported", fn, (long long)ring->capacity,
@@ -369,20 +416,24 @@ static int replay_append_impl(const char *fn, const ssc_replay_ring *ring, const
     SSC_REQUIRE(log->act && log->rew && log->done, "%s: NULL log column", fn);
     for (int c = 0; c < ring->obs_dim; ++c)
         SSC_REQUIRE(log->obs[c] && log->obs2[c], "%s: NULL obs column %d", fn, c);
+    *work = true;
+    return SSC_OK;
+}
+
+static int replay_append_impl(const char *fn, const ssc_replay_ring *ring, const ssc_transition_log *log, int32_t K, int64_t n,
+                              int64_t start, int64_t n_total, int64_t env_off, float reward_scale, ssc_stream_t stream) {
+    bool work;
+    if (int rc = replay_append_check(fn, ring, log, K, n, start, n_total, env_off, &work)) return rc;
+    if (!work) return SSC_OK;
     ReplayAppendArgs g;
-    g.ring = *ring; g.log = *log; g.n = n; g.n_total = n_total; g.env_off = env_off;
-    g.row_stride = log->row_stride ? log->row_stride : n;
-    g.done_row_stride = log->done_row_stride ? log->done_row_stride : n;
-    const int64_t total = (int64_t)K * n;
-    if (n_total == n) {
-        g.count = total < ring->capacity ? total : ring->capacity;  // older records of the chunk would be overwritten anyway
-    } else {
+    pack_append(*ring, *log, K, n, start, reward_scale, g);
+    if (n_total != n) {                  // a shard: every record of it is kept
         SSC_REQUIRE((int64_t)K * n_total <= ring->capacity, "%s: %d steps of %lld envs do not fit a ring of %lld records", fn, K,
                     (long long)n_total, (long long)ring->capacity);
-        g.count = total;
+        g.n_total = n_total; g.env_off = env_off;
+        g.count = (int64_t)K * n;
+        g.first = 0;
     }
-    g.first = total - g.count;
-    g.start = start; g.reward_scale = reward_scale;
     SSC_REQUIRE((ring->ep_steps == nullptr) == (ring->ep_run == nullptr), "%s: ep_steps and ep_run come together", fn);
     if (ring->ep_steps != nullptr) {
         SSC_REQUIRE(start % n_total == 0, "%s: an indexed ring takes whole steps of n = %lld envs (start = %lld)", fn,
@@ -407,6 +458,68 @@ int ssc_replay_append_shard(const ssc_replay_ring *ring, const ssc_transition_lo
                             int64_t start, int64_t n_total, int64_t env_off, float reward_scale, ssc_stream_t stream) {
     SSC_REQUIRE(n_total >= 1, "ssc_replay_append_shard: n_total = %lld", (long long)n_total);
     return replay_append_impl("ssc_replay_append_shard", ring, log, K, n, start, n_total, env_off, reward_scale, stream);
+}
+
+static int launch_append_many(bool indexed, int obs_dim, const ssc_replay_append_item *d_items, const ssc_pair_cursor *d_cursors,
+                              int32_t n_pairs, int64_t work_max, hipStream_t s) {
+    const dim3 grid(blocks_for(work_max), (unsigned)n_pairs);
+#define SSC_APPEND_MANY(OD, IDX) hipLaunchKernelGGL((replay_append_many_kernel<OD, IDX>), grid, dim3(kBlock), 0, s, d_items, d_cursors)
+    if (indexed) {
+        if (obs_dim == 2) SSC_APPEND_MANY(2, true);
+        else if (obs_dim == 3) SSC_APPEND_MANY(3, true);
+        else SSC_APPEND_MANY(0, true);
+    } else {
+        if (obs_dim == 2) SSC_APPEND_MANY(2, false);
+        else if (obs_dim == 3) SSC_APPEND_MANY(3, false);
+        else SSC_APPEND_MANY(0, false);
+    }
+#undef SSC_APPEND_MANY
+    return check_launch("ssc_replay_append_many");
+}
+
+int ssc_replay_append_many(const ssc_replay_append_item *h_items, const ssc_replay_append_item *d_items,
+                           const ssc_pair_cursor *h_cursors, const ssc_pair_cursor *d_cursors, int32_t n_pairs,
+                           ssc_stream_t stream) {
+    SSC_REQUIRE(n_pairs >= 1, "ssc_replay_append_many: n_pairs %d < 1", n_pairs);
+    SSC_REQUIRE(h_items != nullptr && d_items != nullptr, "ssc_replay_append_many: NULL item array");
+    SSC_REQUIRE(h_cursors != nullptr && d_cursors != nullptr, "ssc_replay_append_many: NULL cursor array");
+    if (n_pairs > 65535) return set_error(SSC_EUNSUPPORTED, "ssc_replay_append_many: %d pairs > 65535 (one grid row each)", n_pairs);
+    const ssc_replay_ring &r0 = h_items[0].ring;
+    const bool indexed = r0.ep_steps != nullptr;
+    int64_t work_max = 0;
+    std::vector<std::pair<const void *, int>> owned;   // (ring array, pair)
+    owned.reserve((size_t)n_pairs * 7);
+    for (int p = 0; p < n_pairs; ++p) {
+        const ssc_replay_append_item &it = h_items[p];
+        const ssc_replay_ring *ring = &it.ring;
+        char who[56];
+        snprintf(who, sizeof who, "ssc_replay_append_many: pair %d", p);
+        const int64_t start = h_cursors[p].replay_start;
+        bool work;
+        if (int rc = replay_append_check(who, ring, &it.log, it.K, it.n, start, it.n, 0, &work)) return rc;
+        SSC_REQUIRE(ring->obs_dim == r0.obs_dim, "%s: obs_dim %d differs from pair 0's %d (one kernel instantiation per launch)", who,
+                    ring->obs_dim, r0.obs_dim);
+        SSC_REQUIRE((ring->ep_steps == nullptr) == (ring->ep_run == nullptr), "%s: ep_steps and ep_run come together", who);
+        SSC_REQUIRE((ring->ep_steps != nullptr) == indexed, "%s: the episode index is %s, pair 0's is not (kept for all rings or for none)",
+                    who, ring->ep_steps ? "kept" : "not kept");
+        for (const void *q : {(const void *)ring->s, (const void *)ring->a, (const void *)ring->r, (const void *)ring->t,
+                              (const void *)ring->s2, (const void *)ring->ep_steps, (const void *)ring->ep_run})
+            if (q != nullptr) owned.emplace_back(q, p);
+        if (!work) continue;
+        if (indexed)
+            SSC_REQUIRE(start % it.n == 0, "%s: an indexed ring takes whole steps of n = %lld envs (start = %lld)", who, (long long)it.n,
+                        (long long)start);
+        const int64_t total = (int64_t)it.K * it.n;
+        const int64_t w = indexed ? it.n : (total < ring->capacity ? total : ring->capacity);
+        if (w > work_max) work_max = w;
+    }
+    // two pairs on one ring array would race without a sign of it
+    std::sort(owned.begin(), owned.end());
+    for (size_t k = 1; k < owned.size(); ++k)
+        SSC_REQUIRE(owned[k].first != owned[k - 1].first || owned[k].second == owned[k - 1].second,
+                    "ssc_replay_append_many: pairs %d and %d share a ring array", owned[k - 1].second, owned[k].second);
+    if (work_max == 0) return SSC_OK;
+    return launch_append_many(indexed, r0.obs_dim, d_items, d_cursors, n_pairs, work_max, as_stream(stream));
 }
 
 static int smart_table_size(int32_t n_ss) {

@@ -13,6 +13,11 @@
 // kernel is HBM-write-bound by construction.  Episode records go to a ring through a
 // wave-aggregated atomic cursor; chunk statistics are reduced wave -> block -> one f64
 // atomic per block.
+#include <algorithm>
+#include <cstdio>
+#include <utility>
+#include <vector>
+
 #include "actor_device.h"
 #ifndef SSC_WIDE_ACTOR_ET
 #define SSC_WIDE_ACTOR_ET 2   // env tiles per wave of the LDS-staged wide actor (1: two waves per SIMD at 65 536 envs)
@@ -53,6 +58,7 @@ struct McEnv {
     using Const = McConst;
     static constexpr int OBS = 2;
     float pos, vel;
+    static SSC_HD Const make_const(const ssc_env_params &p) { return make_mc_const(p); }
     __device__ void load(float a, float b) { pos = a; vel = b; }
     __device__ void observe(float (&o)[OBS]) const { o[0] = pos; o[1] = vel; }
     __device__ void step(const Const &c, float a, float &rew, bool &goal) { mc_step_one(c, pos, vel, a, rew, goal); }
@@ -65,6 +71,7 @@ struct PendEnv {
     using Const = PendConst;
     static constexpr int OBS = 3;
     float th, thdot;
+    static SSC_HD Const make_const(const ssc_env_params &p) { return make_pend_const(p); }
     __device__ void load(float a, float b) { th = a; thdot = b; }
     __device__ void observe(float (&o)[OBS]) const { pend_observe_one(th, thdot, o[0], o[1], o[2]); }
     __device__ void step(const Const &c, float a, float &rew, bool &goal) {
@@ -368,11 +375,15 @@ struct Rollout {
         {
             if (done) {
                 if (ra.has_ring && active && owner) {
-                    const uint32_t slot = atomicAdd(ra.ring.cursor, 1u);
+                    // explicit global-address-space pointers: read out of a population item (rollout_many_kernel) the ring
+                    // pointers are generic, and the record would be the one FLAT access inside the step loop
+                    // (atomicAdd is this relaxed agent-scope add)
+                    const uint32_t slot = __hip_atomic_fetch_add((SSC_GLOBAL uint32_t *)ra.ring.cursor, 1u, __ATOMIC_RELAXED,
+                                                                 __HIP_MEMORY_SCOPE_AGENT);
                     if (slot < (uint32_t)ra.ring.capacity) {
-                        ra.ring.env_id[slot] = (int64_t)env_id;
-                        ra.ring.length[slot] = el;
-                        ra.ring.ret[slot] = ep_ret;
+                        ((SSC_GLOBAL int64_t *)ra.ring.env_id)[slot] = (int64_t)env_id;
+                        ((SSC_GLOBAL int32_t *)ra.ring.length)[slot] = el;
+                        ((SSC_GLOBAL float *)ra.ring.ret)[slot] = ep_ret;
                     }
                 }
                 n_eps += 1;
@@ -386,8 +397,12 @@ struct Rollout {
     }
 };
 
-template <class EnvT, class PolT, bool LOG, bool ONEBASE = false, class... Rms>
-__global__ __launch_bounds__(kBlock) void rollout_kernel(typename EnvT::Const ec, PolicyArgs pa, RolloutArgs ra, Rms... rms) {
+// The whole launch of one (env set, policy): workgroup blockIdx.x of ITS grid row.  Shared by rollout_kernel (arguments in
+// the kernarg) and rollout_many_kernel (arguments derived from the pair's item).  The arguments come BY VALUE: by const
+// reference hipcc schedules the random policy's step loop differently than it did when this was the kernel itself (same
+// instructions, another order); by value the single kernels compile to what they were.
+template <class EnvT, class PolT, bool LOG, bool ONEBASE, class... Rms>
+__device__ __forceinline__ void rollout_body(const typename EnvT::Const ec, const PolicyArgs pa, const RolloutArgs ra, Rms... rms) {
     constexpr int LPE = PolT::kLanesPerEnv;
     constexpr int kEnvsPerBlock = kBlock / LPE;
     // LPE == 2: a wave covers 32 envs, env j of the wave lives on lanes j and j+32
@@ -509,8 +524,13 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(typename EnvT::Const ec
     }
 }
 
+template <class EnvT, class PolT, bool LOG, bool ONEBASE = false, class... Rms>
+__global__ __launch_bounds__(kBlock) void rollout_kernel(typename EnvT::Const ec, PolicyArgs pa, RolloutArgs ra, Rms... rms) {
+    rollout_body<EnvT, PolT, LOG, ONEBASE, Rms...>(ec, pa, ra, rms...);
+}
+
 // Can the fp32 columns of the log be addressed from obs[0] with 32-bit offsets?  (always for a packed chunk)
-static void set_one_base(RolloutArgs &ra, int obs_dim) {
+static SSC_HD void set_one_base(RolloutArgs &ra, int obs_dim) {
     const float *cols[2 * SSC_MAX_OBS + 2];
     int nc = 0;
     for (int c = 0; c < obs_dim; ++c) cols[nc++] = ra.log.obs[c];
@@ -524,6 +544,71 @@ static void set_one_base(RolloutArgs &ra, int obs_dim) {
         if (p < b0 || (p - b0) + (uint64_t)ra.n * 4u > 0xFFFFFFFFull) { ra.one_base = 0; break; }
         ra.col_off[c] = (uint32_t)(p - b0);
     }
+}
+
+// One call's arguments as the kernels take them: what rollout() packs on the host for the single launch and what
+// rollout_many_kernel packs from its pair's item -- the same assignments, and the one rounding among them (act_span) is
+// one IEEE subtraction on either side, so a pair's workgroups see the bits its own launch would hand them.  No checks:
+// those are the host's (rollout_check).
+static SSC_HD void pack_args(const ssc_policy_desc &pol, int64_t n, int32_t K, const ssc_rollout_state &st,
+                             const ssc_transition_log *log, const ssc_episode_ring *ring, double *stats, uint64_t seed,
+                             uint64_t env_id0, uint64_t step0, int obs_dim, PolicyArgs &pa, RolloutArgs &ra) {
+    ra.n = n;
+    ra.K = K;
+    ra.st = st;
+    ra.has_log = log != nullptr;
+    ra.has_ring = ring != nullptr;
+    ra.one_base = 0;
+    if (log) {
+        ra.log = *log;
+        if (ra.log.row_stride == 0) ra.log.row_stride = n;
+        if (ra.log.done_row_stride == 0) ra.log.done_row_stride = n;
+        set_one_base(ra, obs_dim);
+    } else {
+        ra.log = ssc_transition_log{};
+    }
+    if (ring) ra.ring = *ring;
+    else ra.ring = ssc_episode_ring{};
+    ra.stats = stats;
+    ra.seed = seed;
+    ra.env_id0 = env_id0;
+    ra.step0 = step0;
+
+    pa = PolicyArgs{};
+    pa.act_low = pol.act_low;
+    pa.act_high = pol.act_high;
+    pa.act_span = pol.act_high - pol.act_low;
+    if (pol.kind == SSC_POLICY_ACTOR) {
+        const ssc_actor_desc &a = pol.actor;
+        pa.actor = ActorWeights{a.W1, a.b1, a.W2, a.b2, a.W3, a.b3, a.obs_dim, a.h1, a.h2, a.last_layer_tanh, a.obs_clip,
+                                a.ln1_g, a.ln1_b, a.ln2_g, a.ln2_b};
+        pa.ou_mu = pol.ou.mu;
+        pa.ou_sigma = pol.ou.sigma;
+        pa.ou_theta = pol.ou.theta;
+        pa.ou_dt = pol.ou.dt;
+        pa.ou_eps = pol.ou.epsilon;
+        pa.d_eps = pol.ou.d_epsilon;
+    }
+}
+
+// A population of (env set, policy) pairs in one launch (ssc_rollout_many): blockIdx.y is the pair, whose workgroups run
+// rollout_body exactly as the pair's own launch would.  The item and the cursor sit at workgroup-uniform addresses and are
+// read before anything is written: scalar loads into SGPRs, where the kernarg of the single launch lives too.  Grid x is
+// the LARGEST pair's block count: the workgroups a smaller pair does not have leave at once.  Pairs share nothing (the
+// host refuses two pairs on one array); a pair's atomics on its own d_stats and ring cursor are those of its own launch.
+// Pointers read out of the item are generic to the compiler: the state loads / stores around the step loop are FLAT
+// instructions here, the log stores inside it go through lane_ptr and stay global_store.
+template <class EnvT, class PolT, bool LOG, bool ONEBASE, class... Rms>
+__global__ __launch_bounds__(kBlock) void rollout_many_kernel(const ssc_rollout_many_item *__restrict__ items,
+                                                              const ssc_pair_cursor *__restrict__ cursors, int32_t K) {
+    const ssc_rollout_many_item &it = items[blockIdx.y];
+    if ((int64_t)blockIdx.x * (kBlock / PolT::kLanesPerEnv) >= it.n) return;
+    PolicyArgs pa;
+    RolloutArgs ra;
+    pack_args(it.policy, it.n, K, it.state, LOG ? &it.log : nullptr, it.has_ring ? &it.ring : nullptr, it.d_stats, it.seed,
+              it.env_id0, cursors[blockIdx.y].step0, EnvT::OBS, pa, ra);
+    const typename EnvT::Const ec = EnvT::make_const(it.params);
+    rollout_body<EnvT, PolT, LOG, ONEBASE, Rms...>(ec, pa, ra, static_cast<Rms>(it.d_rms)...);
 }
 
 template <class EnvT, class PolT, class... Rms>
@@ -547,6 +632,14 @@ static int launch_rollout(const typename EnvT::Const &ec, const PolicyArgs &pa, 
 }
 
 int validate_mc_params(const ssc_env_params *p, const char *who);  // env_step.hip
+
+// Does a MountainCar bf16-MFMA actor run the straight-line fused policy?  (dispatch_policy, and ssc_rollout_many for its pairs)
+static bool mc_fused_policy(const McConst &ec, const ssc_actor_desc &a, const PolicyArgs &pa, bool norm) {
+    const float obs_bound = fmaxf(fmaxf(fabsf(ec.min_position), fabsf(ec.max_position)), fabsf(ec.max_speed));
+    const bool clip_inert = !(a.obs_clip > 0.0f) || a.obs_clip >= obs_bound;
+    return a.h1 <= 64 && a.h2 <= 32 && pa.act_low == -1.0f && pa.act_high == 1.0f && (pa.ou_eps > 0.0f || pa.d_eps != nullptr) &&
+           (clip_inert || norm);
+}
 
 // Rms: empty, or the RunningMeanStd block of normalize_observations (every actor policy then has a NORM instantiation)
 template <class EnvT, class... Rms>
@@ -575,9 +668,7 @@ static int dispatch_policy(const typename EnvT::Const &ec, const ssc_policy_desc
             // (MountainCar observations are bounded by the env's own clamps: an observation clip at or beyond them
             // -- DDPG's (-5, 5) against |pos| <= 1.2, |vel| <= 0.07 -- never acts, so the fused policy skips it; a normalised
             // observation has no such bound, and the NORM instantiation clips)
-            const float obs_bound = fmaxf(fmaxf(fabsf(ec.min_position), fabsf(ec.max_position)), fabsf(ec.max_speed));
-            const bool clip_inert = !(a.obs_clip > 0.0f) || a.obs_clip >= obs_bound;
-            if (a.h1 <= 64 && a.h2 <= 32 && pa.act_low == -1.0f && pa.act_high == 1.0f && (pa.ou_eps > 0.0f || pa.d_eps != nullptr) && (clip_inert || N)) {
+            if (mc_fused_policy(ec, a, pa, N)) {
                 if (a.last_layer_tanh) return launch_rollout<EnvT, ActorPolicyFused<true, N>>(ec, pa, ra, stream, rms...);
                 return launch_rollout<EnvT, ActorPolicyFused<false, N>>(ec, pa, ra, stream, rms...);
             }
@@ -810,75 +901,59 @@ __global__ __launch_bounds__(kBlock) void mpc_rollout_step_kernel(typename EnvT:
 
 using namespace ssc;
 
+// the checks of one rollout call, in two parts: rollout() returns SSC_OK between them when there is nothing to run
+static int rollout_check_sizes(const char *who, const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n, int32_t K,
+                               const ssc_rollout_state *state) {
+    SSC_REQUIRE(p && policy && state, "%s: NULL descriptor", who);
+    SSC_REQUIRE(n >= 0 && K >= 0, "%s: n = %lld, K = %d", who, (long long)n, K);
+    SSC_REQUIRE(n <= ((int64_t)1 << 30), "%s: n = %lld > 2^30 envs per launch", who, (long long)n);
+    SSC_REQUIRE(policy->kind == SSC_POLICY_RANDOM || policy->kind == SSC_POLICY_ACTOR,
+                "%s: unknown policy kind %d", who, policy->kind);
+    return SSC_OK;
+}
+
+static int rollout_check_arrays(const char *who, const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n,
+                                const ssc_rollout_state *state, const ssc_transition_log *log, const ssc_episode_ring *ring) {
+    SSC_REQUIRE(state->s0 && state->s1 && state->steps && state->ep_ret, "%s: NULL state column", who);
+    SSC_REQUIRE(policy->act_low <= policy->act_high, "%s: act_low > act_high", who);
+    const int obs_dim = (p->kind == SSC_ENV_MOUNTAINCAR) ? 2 : 3;
+    if (log) {
+        for (int c = 0; c < obs_dim; ++c)
+            SSC_REQUIRE(log->obs[c] && log->obs2[c], "%s: NULL log obs column %d", who, c);
+        SSC_REQUIRE(log->act && log->rew && log->done, "%s: NULL log column", who);
+        SSC_REQUIRE(log->row_stride >= 0 && log->done_row_stride >= 0, "%s: negative row stride", who);
+        SSC_REQUIRE((log->row_stride == 0 || log->row_stride >= n) && (log->done_row_stride == 0 || log->done_row_stride >= n),
+                    "%s: row stride < n", who);
+    }
+    if (ring)
+        SSC_REQUIRE(ring->env_id && ring->length && ring->ret && ring->cursor && ring->capacity >= 0,
+                    "%s: bad episode ring", who);
+    if (policy->kind == SSC_POLICY_ACTOR) {
+        const ssc_actor_desc &a = policy->actor;
+        SSC_REQUIRE(a.W1 && a.b1 && a.W2 && a.b2 && a.W3 && a.b3, "%s: NULL actor weight pointer", who);
+        SSC_REQUIRE(a.h1 > 0 && a.h2 > 0, "%s: bad actor sizes", who);
+        const bool ln = a.ln1_g != nullptr;
+        SSC_REQUIRE(ln == (a.ln1_b != nullptr) && ln == (a.ln2_g != nullptr) && ln == (a.ln2_b != nullptr),
+                    "%s: the four LayerNorm pointers come together", who);
+        if (ln && a.precision != SSC_PREC_F32)
+            return set_error(SSC_EUNSUPPORTED, "%s: LayerNorm actors run on the fp32 policy (precision SSC_PREC_F32)", who);
+        SSC_REQUIRE(!(policy->ou.epsilon > 0.0f || policy->ou.d_epsilon != nullptr) || state->ou_x != nullptr,
+                    "%s: OU noise needs state->ou_x", who);
+    }
+    return SSC_OK;
+}
+
 template <class... Rms>
 static int rollout(const ssc_env_params *p, const ssc_policy_desc *policy, int64_t n, int32_t K,
                    const ssc_rollout_state *state, const ssc_transition_log *log,
                    const ssc_episode_ring *ring, double *d_stats, uint64_t seed, uint64_t env_id0,
                    uint64_t step0, ssc_stream_t stream, Rms... rms) {
-    SSC_REQUIRE(p && policy && state, "ssc_rollout: NULL descriptor");
-    SSC_REQUIRE(n >= 0 && K >= 0, "ssc_rollout: n = %lld, K = %d", (long long)n, K);
-    SSC_REQUIRE(n <= ((int64_t)1 << 30), "ssc_rollout: n = %lld > 2^30 envs per launch", (long long)n);
-    SSC_REQUIRE(policy->kind == SSC_POLICY_RANDOM || policy->kind == SSC_POLICY_ACTOR,
-                "ssc_rollout: unknown policy kind %d", policy->kind);
+    if (int rc = rollout_check_sizes("ssc_rollout", p, policy, n, K, state)) return rc;
     if (n == 0 || K == 0) return SSC_OK;
-    SSC_REQUIRE(state->s0 && state->s1 && state->steps && state->ep_ret, "ssc_rollout: NULL state column");
-    SSC_REQUIRE(policy->act_low <= policy->act_high, "ssc_rollout: act_low > act_high");
-    const int obs_dim = (p->kind == SSC_ENV_MOUNTAINCAR) ? 2 : 3;
+    if (int rc = rollout_check_arrays("ssc_rollout", p, policy, n, state, log, ring)) return rc;
     RolloutArgs ra;
-    ra.n = n;
-    ra.K = K;
-    ra.st = *state;
-    ra.has_log = log != nullptr;
-    ra.has_ring = ring != nullptr;
-    ra.one_base = 0;
-    if (log) {
-        ra.log = *log;
-        for (int c = 0; c < obs_dim; ++c)
-            SSC_REQUIRE(log->obs[c] && log->obs2[c], "ssc_rollout: NULL log obs column %d", c);
-        SSC_REQUIRE(log->act && log->rew && log->done, "ssc_rollout: NULL log column");
-        SSC_REQUIRE(log->row_stride >= 0 && log->done_row_stride >= 0, "ssc_rollout: negative row stride");
-        if (ra.log.row_stride == 0) ra.log.row_stride = n;
-        if (ra.log.done_row_stride == 0) ra.log.done_row_stride = n;
-        SSC_REQUIRE(ra.log.row_stride >= n && ra.log.done_row_stride >= n, "ssc_rollout: row stride < n");
-        set_one_base(ra, obs_dim);
-    } else {
-        ra.log = ssc_transition_log{};
-    }
-    if (ring) {
-        ra.ring = *ring;
-        SSC_REQUIRE(ring->env_id && ring->length && ring->ret && ring->cursor && ring->capacity >= 0,
-                    "ssc_rollout: bad episode ring");
-    } else {
-        ra.ring = ssc_episode_ring{};
-    }
-    ra.stats = d_stats;
-    ra.seed = seed;
-    ra.env_id0 = env_id0;
-    ra.step0 = step0;
-
-    PolicyArgs pa{};
-    pa.act_low = policy->act_low;
-    pa.act_high = policy->act_high;
-    pa.act_span = policy->act_high - policy->act_low;
-    if (policy->kind == SSC_POLICY_ACTOR) {
-        const ssc_actor_desc &a = policy->actor;
-        SSC_REQUIRE(a.W1 && a.b1 && a.W2 && a.b2 && a.W3 && a.b3, "ssc_rollout: NULL actor weight pointer");
-        SSC_REQUIRE(a.h1 > 0 && a.h2 > 0, "ssc_rollout: bad actor sizes");
-        pa.actor = ActorWeights{a.W1, a.b1, a.W2, a.b2, a.W3, a.b3, a.obs_dim, a.h1, a.h2, a.last_layer_tanh, a.obs_clip,
-                                a.ln1_g, a.ln1_b, a.ln2_g, a.ln2_b};
-        const bool ln = a.ln1_g != nullptr;
-        SSC_REQUIRE(ln == (a.ln1_b != nullptr) && ln == (a.ln2_g != nullptr) && ln == (a.ln2_b != nullptr),
-                    "ssc_rollout: the four LayerNorm pointers come together");
-        if (ln && a.precision != SSC_PREC_F32)
-            return set_error(SSC_EUNSUPPORTED, "ssc_rollout: LayerNorm actors run on the fp32 policy (precision SSC_PREC_F32)");
-        pa.ou_mu = policy->ou.mu;
-        pa.ou_sigma = policy->ou.sigma;
-        pa.ou_theta = policy->ou.theta;
-        pa.ou_dt = policy->ou.dt;
-        pa.ou_eps = policy->ou.epsilon;
-        pa.d_eps = policy->ou.d_epsilon;
-        SSC_REQUIRE(!(pa.ou_eps > 0.0f || pa.d_eps != nullptr) || state->ou_x != nullptr, "ssc_rollout: OU noise needs state->ou_x");
-    }
+    PolicyArgs pa;
+    pack_args(*policy, n, K, *state, log, ring, d_stats, seed, env_id0, step0, (p->kind == SSC_ENV_MOUNTAINCAR) ? 2 : 3, pa, ra);
     if (p->kind == SSC_ENV_MOUNTAINCAR) {
         if (int rc = validate_mc_params(p, "ssc_rollout")) return rc;
         return dispatch_policy<McEnv>(make_mc_const(*p), policy, pa, ra, as_stream(stream), rms...);
@@ -903,6 +978,132 @@ extern "C" int ssc_rollout_rms(const ssc_env_params *p, const ssc_policy_desc *p
                                uint64_t step0, ssc_stream_t stream, const double *d_rms) {
     if (d_rms == nullptr) return rollout(p, policy, n, K, state, log, ring, d_stats, seed, env_id0, step0, stream);
     return rollout(p, policy, n, K, state, log, ring, d_stats, seed, env_id0, step0, stream, d_rms);
+}
+
+// ---- a population of pairs in one launch ----------------------------------------------------------------------
+namespace {
+
+template <class EnvT, class PolT, class... Rms>
+int launch_rollout_many(const ssc_rollout_many_item *d_items, const ssc_pair_cursor *d_cursors, int32_t n_pairs, int32_t K,
+                        int64_t n_max, bool has_log, bool one_base, hipStream_t stream) {
+    const dim3 grid(blocks_for(n_max, kBlock / PolT::kLanesPerEnv), (unsigned)n_pairs);
+    if (has_log && one_base)   // (the actor policies: launch_rollout's kOneBase)
+        hipLaunchKernelGGL((rollout_many_kernel<EnvT, PolT, true, true, Rms...>), grid, dim3(kBlock), 0, stream, d_items, d_cursors, K);
+    else if (has_log)
+        hipLaunchKernelGGL((rollout_many_kernel<EnvT, PolT, true, false, Rms...>), grid, dim3(kBlock), 0, stream, d_items, d_cursors, K);
+    else
+        hipLaunchKernelGGL((rollout_many_kernel<EnvT, PolT, false, false, Rms...>), grid, dim3(kBlock), 0, stream, d_items, d_cursors, K);
+    return check_launch("ssc_rollout_many");
+}
+
+// the policy class dispatch_policy chooses for a served pair
+enum ManyClass { MANY_FUSED = 0, MANY_MFMA = 1 };
+
+template <class EnvT, class... Rms>
+int dispatch_rollout_many(ManyClass cls, bool last_tanh, const ssc_rollout_many_item *d_items, const ssc_pair_cursor *d_cursors,
+                          int32_t n_pairs, int32_t K, int64_t n_max, bool has_log, bool one_base, hipStream_t stream) {
+    constexpr int OBS = EnvT::OBS;
+    constexpr bool N = sizeof...(Rms) > 0;
+    if constexpr (OBS == 2) {
+        if (cls == MANY_FUSED) {
+            if (last_tanh)
+                return launch_rollout_many<EnvT, ActorPolicyFused<true, N>, Rms...>(d_items, d_cursors, n_pairs, K, n_max, has_log, one_base, stream);
+            return launch_rollout_many<EnvT, ActorPolicyFused<false, N>, Rms...>(d_items, d_cursors, n_pairs, K, n_max, has_log, one_base, stream);
+        }
+    }
+    return launch_rollout_many<EnvT, ActorPolicy<ActorMfma<OBS, 2, 1, 2>, OBS, N>, Rms...>(d_items, d_cursors, n_pairs, K, n_max, has_log, one_base,
+                                                                                       stream);
+}
+
+}  // namespace
+
+extern "C" int ssc_rollout_many(const ssc_rollout_many_item *h_items, const ssc_rollout_many_item *d_items,
+                                const ssc_pair_cursor *h_cursors, const ssc_pair_cursor *d_cursors, int32_t n_pairs, int32_t K,
+                                ssc_stream_t stream) {
+    SSC_REQUIRE(n_pairs >= 1, "ssc_rollout_many: n_pairs %d < 1", n_pairs);
+    SSC_REQUIRE(h_items != nullptr && d_items != nullptr, "ssc_rollout_many: NULL item array");
+    SSC_REQUIRE(h_cursors != nullptr && d_cursors != nullptr, "ssc_rollout_many: NULL cursor array");
+    SSC_REQUIRE(K >= 0, "ssc_rollout_many: K = %d", K);
+    if (n_pairs > 65535) return set_error(SSC_EUNSUPPORTED, "ssc_rollout_many: %d pairs > 65535 (one grid row each)", n_pairs);
+    const ssc_rollout_many_item &i0 = h_items[0];
+    ManyClass cls0 = MANY_MFMA;
+    bool tanh0 = false, one_base = true;
+    int64_t n_max = 0;
+    std::vector<std::pair<const void *, int>> owned;   // (array, pair) of everything a pair's workgroups write
+    owned.reserve((size_t)n_pairs * 20);
+    for (int p = 0; p < n_pairs; ++p) {
+        const ssc_rollout_many_item &it = h_items[p];
+        char who[48];
+        snprintf(who, sizeof who, "ssc_rollout_many: pair %d", p);
+        const ssc_transition_log *log = it.has_log ? &it.log : nullptr;
+        const ssc_episode_ring *ring = it.has_ring ? &it.ring : nullptr;
+        // the single call's checks
+        if (int rc = rollout_check_sizes(who, &it.params, &it.policy, it.n, K, &it.state)) return rc;
+        SSC_REQUIRE(it.n >= 1, "%s: n = %lld < 1", who, (long long)it.n);
+        SSC_REQUIRE(it.params.kind == SSC_ENV_MOUNTAINCAR || it.params.kind == SSC_ENV_PENDULUM, "%s: unknown env kind %d", who,
+                    it.params.kind);
+        if (int rc = rollout_check_arrays(who, &it.params, &it.policy, it.n, &it.state, log, ring)) return rc;
+        if (it.params.kind == SSC_ENV_MOUNTAINCAR)
+            if (int rc = validate_mc_params(&it.params, who)) return rc;
+        // one instantiation per launch: env kind first (the obs_dim every other check reads)
+        SSC_REQUIRE(it.params.kind == i0.params.kind, "%s: env kind %d differs from pair 0's %d (one kernel instantiation per launch)", who,
+                    it.params.kind, i0.params.kind);
+        const int obs_dim = it.params.kind == SSC_ENV_MOUNTAINCAR ? 2 : 3;
+        const ssc_actor_desc &a = it.policy.actor;
+        if (it.policy.kind != SSC_POLICY_ACTOR)
+            return set_error(SSC_EUNSUPPORTED, "%s: the random policy does not roll out as a population; call ssc_rollout", who);
+        SSC_REQUIRE(a.obs_dim == obs_dim, "%s: actor obs_dim %d != env obs_dim %d", who, a.obs_dim, obs_dim);
+        if (a.act_dim != 1) return set_error(SSC_EUNSUPPORTED, "%s: act_dim %d (only 1)", who, a.act_dim);
+        if (a.precision != SSC_PREC_BF16_MFMA || a.h1 > 64 || a.h2 > 32 || a.ln1_g != nullptr)
+            return set_error(SSC_EUNSUPPORTED, "%s: only bf16-MFMA actors with h1 <= 64, h2 <= 32 and no LayerNorm roll out as a population "
+                                               "(precision %d, %d-%d); call ssc_rollout_rms", who, a.precision, a.h1, a.h2);
+        PolicyArgs pa;
+        RolloutArgs ra;
+        pack_args(it.policy, it.n, K, it.state, log, ring, it.d_stats, it.seed, it.env_id0, h_cursors[p].step0, obs_dim, pa, ra);
+        const ManyClass cls = (obs_dim == 2 && mc_fused_policy(make_mc_const(it.params), a, pa, it.d_rms != nullptr)) ? MANY_FUSED : MANY_MFMA;
+        const bool t2 = a.last_layer_tanh != 0;
+        if (p == 0) { cls0 = cls; tanh0 = t2; }
+        SSC_REQUIRE(cls == cls0, "%s: runs the %s actor policy, pair 0 the %s one (action bounds / epsilon / obs_clip select it; one kernel "
+                                 "instantiation per launch)", who, cls == MANY_FUSED ? "fused" : "generic", cls0 == MANY_FUSED ? "fused" : "generic");
+        SSC_REQUIRE(cls != MANY_FUSED || t2 == tanh0, "%s: last_layer_tanh %d differs from pair 0's %d (one kernel instantiation per launch)",
+                    who, a.last_layer_tanh, i0.policy.actor.last_layer_tanh);
+        SSC_REQUIRE((it.d_rms != nullptr) == (i0.d_rms != nullptr), "%s: d_rms is %s, pair 0's is not (statistics for all pairs or for none)",
+                    who, it.d_rms ? "set" : "NULL");
+        SSC_REQUIRE((it.has_log != 0) == (i0.has_log != 0), "%s: has_log %d differs from pair 0's %d (a log for all pairs or for none)", who,
+                    it.has_log, i0.has_log);
+        one_base = one_base && (!log || ra.one_base);
+        if (it.n > n_max) n_max = it.n;
+        for (const void *q : {(const void *)it.state.s0, (const void *)it.state.s1, (const void *)it.state.steps, (const void *)it.state.ep_ret,
+                              (const void *)it.state.ou_x, (const void *)it.d_stats})
+            if (q != nullptr) owned.emplace_back(q, p);
+        if (log) {
+            for (int c = 0; c < obs_dim; ++c) {
+                owned.emplace_back(log->obs[c], p);
+                owned.emplace_back(log->obs2[c], p);
+            }
+            for (const void *q : {(const void *)log->act, (const void *)log->rew, (const void *)log->done}) owned.emplace_back(q, p);
+        }
+        if (ring)
+            for (const void *q : {(const void *)ring->env_id, (const void *)ring->length, (const void *)ring->ret, (const void *)ring->cursor})
+                owned.emplace_back(q, p);
+    }
+    // two pairs on one array would race without a sign of it
+    std::sort(owned.begin(), owned.end());
+    for (size_t k = 1; k < owned.size(); ++k)
+        SSC_REQUIRE(owned[k].first != owned[k - 1].first || owned[k].second == owned[k - 1].second,
+                    "ssc_rollout_many: pairs %d and %d share a state, log, episode-ring or statistics array", owned[k - 1].second,
+                    owned[k].second);
+    if (K == 0) return SSC_OK;
+    const bool has_log = i0.has_log != 0;
+    hipStream_t s = as_stream(stream);
+    if (i0.params.kind == SSC_ENV_MOUNTAINCAR) {
+        if (i0.d_rms != nullptr)
+            return dispatch_rollout_many<McEnv, const double *>(cls0, tanh0, d_items, d_cursors, n_pairs, K, n_max, has_log, one_base, s);
+        return dispatch_rollout_many<McEnv>(cls0, tanh0, d_items, d_cursors, n_pairs, K, n_max, has_log, one_base, s);
+    }
+    if (i0.d_rms != nullptr)
+        return dispatch_rollout_many<PendEnv, const double *>(cls0, tanh0, d_items, d_cursors, n_pairs, K, n_max, has_log, one_base, s);
+    return dispatch_rollout_many<PendEnv>(cls0, tanh0, d_items, d_cursors, n_pairs, K, n_max, has_log, one_base, s);
 }
 
 // argument checks and packing shared by ssc_mpc_rollout_step and ssc_smartstart_rollout_step

@@ -99,3 +99,48 @@ class ObsRms:
         dst = other.block if isinstance(other, ObsRms) else other
         dst.copy_(self.block)
         return other
+
+
+class ObsRmsGroup:
+    """P :class:`ObsRms` blocks updated by TWO launches for all of them (``ssc_obs_rms_update_many``) instead of two each:
+    every block ends up bit for bit as after ``rms.update_chunk`` one by one (each block's rows are partitioned and summed
+    exactly as its own call does it).  Blocks of different obs_dim, or two entries on one block, update one by one;
+    ``fused`` tells which way the last call went.  The descriptors are rebuilt only when a pointer, a shape, the step range
+    or the stream changes."""
+
+    def __init__(self, blocks):
+        self.blocks = list(blocks)
+        if not self.blocks:
+            raise ValueError("a group needs at least one statistics block")
+        self.device, self.lib = self.blocks[0].device, self.blocks[0].lib
+        self.fused = None
+        self._sig = self._items = None
+
+    def update_chunks(self, chunks, k0=0, K=None):
+        """``blocks[p].update_chunk(chunks[p], k0[p], K[p])`` for every p; ``k0`` / ``K``: one value or one per block."""
+        bs, chunks = self.blocks, list(chunks)
+        k0s = [int(k0)] * len(bs) if isinstance(k0, int) else [int(x) for x in k0]
+        Ks = [K] * len(bs) if K is None or isinstance(K, int) else list(K)
+        Ks = [c.K if k is None else int(k) for c, k in zip(chunks, Ks)]
+        sig = (torch.cuda.current_stream(self.device).cuda_stream, tuple(k0s), tuple(Ks),
+               tuple((b.block.data_ptr(), b._ws.data_ptr(), c.obs.data_ptr(), c.obs.stride(0), c.act.stride(0), c.N)
+                     for b, c in zip(bs, chunks)))
+        if sig != self._sig:
+            from .population import DeviceItems
+            self._sig, self._items = sig, None
+            self.fused = (all(b.obs_dim == bs[0].obs_dim and b.device == self.device for b in bs) and bs[0].obs_dim <= _ffi.SSC_MAX_OBS
+                          and len({b.block.data_ptr() for b in bs}) == len(bs) and len(bs) <= 65535)
+            if self.fused:
+                items = DeviceItems(_ffi.ObsRmsItem, len(bs), self.device)
+                for it, b, c, a, e in zip(items.items, bs, chunks, k0s, Ks):
+                    it.log, it.k0, it.K, it.n = c.as_struct(), a, e, c.N
+                    it.d_rms, it.d_workspace, it.workspace_bytes = b.block.data_ptr(), b._ws.data_ptr(), b._ws.numel()
+                items.upload()
+                self._items = items
+        if not self.fused:
+            for b, c, a, e in zip(bs, chunks, k0s, Ks):
+                b.update_chunk(c, a, e)
+            return
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_obs_rms_update_many(bs[0].obs_dim, self._items.h_ptr, self._items.d_ptr, len(bs),
+                                                        _ffi.stream(self.device)))

@@ -426,3 +426,100 @@ class DeviceReplayBuffer:
         if rows == 0:
             raise ValueError(": (   -   the episode start of this record is no longer in the ring")
         return self._path[:rows].clone()
+
+
+class DeviceReplayPopulation:
+    """P :class:`DeviceReplayBuffer` rings fed by ONE launch per chunk (``ssc_replay_append_many``, grid row p = ring p).
+    The rings are wrapped, not copied; per ring ``count``, ``_next_step0`` and the ``ep_run.zero_()`` rule move exactly as
+    ``append_chunk`` moves them, and every ring array ends up bit for bit as after ``append_chunk`` ring by ring.
+
+    The launch serves rings of one obs_dim that all keep the episode index or all do not and share no array; any other
+    population appends ring by ring.  ``fused`` tells which way the last call went.  The descriptors stay with the object
+    and are rebuilt only when a pointer, a shape, ``last_steps``, a reward scale or the stream changes."""
+
+    def __init__(self, replays):
+        self.replays = list(replays)
+        if not self.replays:
+            raise ValueError("a population needs at least one ring")
+        r0 = self.replays[0]
+        self.device, self.lib = r0.device, r0.lib
+        self._torch, self._ffi = r0._torch, r0._ffi
+        if any(r.device != self.device for r in self.replays):
+            raise ValueError("the rings of a population live on one device")
+        self.fused = None
+        self._sig = self._items = self._own_cursors = None
+
+    def _fusable(self):
+        rs = self.replays
+        arrays = [t.data_ptr() for r in rs for t in (r.s, r.a, r.r, r.t, r.s2, r.ep_steps, r.ep_run) if t is not None]
+        return (all(r.obs_dim == rs[0].obs_dim and r.track_episodes == rs[0].track_episodes for r in rs)
+                and len(set(arrays)) == len(arrays) and len(rs) <= 65535)
+
+    def _prepare(self, chunks, scales, Ks):
+        torch = self._torch
+        sig = (torch.cuda.current_stream(self.device).cuda_stream, tuple(Ks), tuple(scales),
+               tuple((r.s.data_ptr(), r.a.data_ptr(), r.r.data_ptr(), r.t.data_ptr(), r.s2.data_ptr(), r.capacity, r.track_episodes,
+                      c.act.data_ptr(), c.done.data_ptr(), c.obs.data_ptr(), c.obs2.data_ptr(), c.K, c.N, c.act.stride(0),
+                      c.done.stride(0), c.obs.stride(0), c.obs2.stride(0)) for r, c in zip(self.replays, chunks)))
+        if sig == self._sig:
+            return self.fused
+        from .population import DeviceItems
+        self._sig, self._items = sig, None
+        self.fused = self._fusable() and all(c.obs_dim == r.obs_dim for r, c in zip(self.replays, chunks))
+        if not self.fused:
+            return False
+        items = DeviceItems(self._ffi.ReplayAppendItem, len(self.replays), self.device)
+        for it, r, c, K, scale in zip(items.items, self.replays, chunks, Ks, scales):
+            log = c.as_struct()
+            if K < c.K:                       # skip the first c.K - K steps: advance every column pointer (append_chunk)
+                skip = c.K - K
+                for k in range(c.obs_dim):
+                    log.obs[k] = c.obs[k][skip:].data_ptr()
+                    log.obs2[k] = c.obs2[k][skip:].data_ptr()
+                log.act, log.rew, log.done = c.act[skip:].data_ptr(), c.rew[skip:].data_ptr(), c.done[skip:].data_ptr()
+            it.ring, it.log, it.K, it.n, it.reward_scale = r.ring_struct(), log, K, c.N, float(scale)
+        items.upload()
+        self._items = items
+        return True
+
+    def append_chunks(self, chunks, reward_scale=1.0, last_steps=None, cursors=None):
+        """``replay.append_chunk(chunk, reward_scale, last_steps)`` for every (ring, chunk) pair.  ``reward_scale``: one
+        value or one per ring.  ``cursors``: a :class:`population.PairCursors` the caller has staged (``replay_start`` =
+        every ``replay.count``) and uploaded on this stream; None: the object keeps its own."""
+        rs, chunks = self.replays, list(chunks)
+        if len(chunks) != len(rs):
+            raise ValueError("one chunk per ring")
+        scales = [float(reward_scale)] * len(rs) if isinstance(reward_scale, (int, float)) else [float(x) for x in reward_scale]
+        Ks = [c.K if last_steps is None else min(int(last_steps), c.K) for c in chunks]
+        if not self._prepare(chunks, scales, Ks):
+            for r, c, s in zip(rs, chunks, scales):
+                r.append_chunk(c, reward_scale=s, last_steps=last_steps)
+            return
+        for r, c, K in zip(rs, chunks, Ks):
+            if r.track_episodes:
+                if c.N != r.n_envs:
+                    raise ValueError(f"this ring indexes episodes of {r.n_envs} envs, the chunk has {c.N}")
+                # an env's running step count carries over only when this chunk continues where the last append stopped
+                first_step = c.step0 + c.K - K
+                if r._next_step0 is not None and first_step != r._next_step0:
+                    r.ep_run.zero_()
+                r._next_step0 = c.step0 + c.K
+        if cursors is None:
+            if self._own_cursors is None:
+                from .population import PairCursors
+                self._own_cursors = PairCursors(len(rs), self.device)
+            cursors = self._own_cursors.stage(replay_start=[r.count for r in rs])
+            cursors.upload()
+        elif cursors.replay_start() != [r.count for r in rs]:
+            raise ValueError("cursors: stage replay_start = replay.count of every ring (and upload) before the append")
+        with self._torch.cuda.device(self.device):
+            self._ffi.check(self.lib.ssc_replay_append_many(self._items.h_ptr, self._items.d_ptr, cursors.h_ptr, cursors.d_ptr,
+                                                            len(rs), self._ffi.stream(self.device)))
+        for r, c, K in zip(rs, chunks, Ks):
+            r.count += K * c.N
+
+
+def append_chunks(replays, chunks, reward_scale=1.0, last_steps=None):
+    """P chunks into P :class:`DeviceReplayBuffer` rings in one call (:class:`DeviceReplayPopulation`, which a loop keeps
+    for its descriptors; this form builds them anew)."""
+    DeviceReplayPopulation(replays).append_chunks(chunks, reward_scale=reward_scale, last_steps=last_steps)

@@ -281,6 +281,48 @@ class DecaySchedule:
         return int(st[0]), st[1:]
 
 
+class DecayScheduleGroup:
+    """P :class:`DecaySchedule` objects updated by ONE launch (``ssc_decay_schedule_many``, one thread per schedule set):
+    states and outputs end up exactly as after ``schedule.update`` one by one.  Nothing in the descriptors changes from
+    chunk to chunk, so they are built on the first call (and again when a counter, ``finished0`` or the stream changes).
+    Schedules that share a state array update one by one; ``fused`` tells which way the last call went."""
+
+    def __init__(self, schedules):
+        self.schedules = list(schedules)
+        if not self.schedules:
+            raise ValueError("a group needs at least one schedule")
+        s0 = self.schedules[0]
+        self._ffi, self._torch, self.device = s0._ffi, s0._torch, s0.device
+        self.fused = None
+        self._sig = self._items = None
+
+    def update(self, finished, finished0=None):
+        """``schedules[p].update(finished[p], finished0[p])`` for every p."""
+        ffi, torch, ss = self._ffi, self._torch, self.schedules
+        finished = list(finished)
+        finished0 = [0.0] * len(ss) if finished0 is None else [float(x) for x in finished0]
+        sig = (torch.cuda.current_stream(self.device).cuda_stream, tuple(f.data_ptr() for f in finished), tuple(finished0))
+        if sig != self._sig:
+            from .population import DeviceItems
+            self._sig, self._items = sig, None
+            self.fused = (len({s.state.data_ptr() for s in ss}) == len(ss) and all(s.device == self.device for s in ss))
+            if self.fused:
+                items = DeviceItems(ffi.DecayItem, len(ss), self.device)
+                for it, s, f, f0 in zip(items.items, ss, finished, finished0):
+                    it.d_finished, it.finished0, it.per_generation, it.n_sched = f.data_ptr(), f0, s.per_generation, s.n
+                    for i in range(s.n):
+                        it.factor[i], it.floor[i], it.d_out[i] = s._factor[i], s._floor[i], s._out_ptrs[i]
+                    it.d_state = s.state.data_ptr()
+                items.upload()
+                self._items = items
+        if not self.fused:
+            for s, f, f0 in zip(ss, finished, finished0):
+                s.update(f, f0)
+            return
+        with torch.cuda.device(self.device):
+            ffi.check(ffi.lib().ssc_decay_schedule_many(self._items.h_ptr, self._items.d_ptr, len(ss), ffi.stream(self.device)))
+
+
 def epsilon_schedule(agent, per_generation, device=None):
     """DecaySchedule of one agent's OU epsilon, starting from its current host value and writing ``agent.d_epsilon``."""
     n = agent.decaying_ou_action_noise
@@ -591,6 +633,11 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     return summary, losses, replay
 
 
+# The population loop's rollouts, decays, appends and statistics updates: one launch per phase for all pairs (True), or the
+# per-pair calls pair by pair as before those launches existed (False: the yardstick of tools/exp_ddpg_population.py).
+POPULATION_FUSED_CHUNK = True
+
+
 def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
                                  replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
                                  drain_every=None, on_chunk=None, stats_every=None, eval_env=None, eval_every=None,
@@ -602,7 +649,11 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
     agents.  Every pair's parameters, losses, Summary and final epsilon are bit for bit those of its own
     ``rl_train_vec_ddpg`` run with the same arguments.  ``seed``: one replay seed for all pairs or one per pair.
     A population the one launch does not serve (see :class:`agents.DDPGPopulation`: another shape, Pop-Art, mixed
-    normalize_observations, ...) trains agent by agent.  The rollouts and appends are still P launches each.
+    normalize_observations, ...) trains agent by agent.  The rollouts, epsilon decays, replay appends and statistics updates
+    of a chunk are ONE launch each for all pairs too (``vec_env.VecEnvPopulation``, ``DecayScheduleGroup``,
+    ``replay_buffer.DeviceReplayPopulation``, ``obs_rms.ObsRmsGroup``; two launches for the statistics), each falling back to
+    the per-pair calls for a population it does not serve (mixed env kinds, another actor shape or precision, mixed
+    statistics, shared arrays).
 
     Not in this form: ``overlap``, agents with parameter-space noise, ``stats_every`` and ``eval_env``
     (NotImplementedError).  ``on_chunk(i, chunks, envs)`` gets the lists.  Returns [(Summary, losses per chunk, replay)]
@@ -637,12 +688,32 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
         summaries[p].extend_records(lens, rets)
 
     pds = [env.policy_desc(agent.as_policy(device_epsilon=True)) for env, agent in zip(envs, agents)]
+    # the rest of the chunk, one launch per phase for all pairs (a population a launch does not serve: pair by pair inside)
+    from .obs_rms import ObsRmsGroup
+    from .population import PairCursors
+    from .replay_buffer import DeviceReplayPopulation
+    from .vec_env import VecEnvPopulation
+    env_pop, replay_pop, decays = VecEnvPopulation(envs), DeviceReplayPopulation(replays), DecayScheduleGroup(schedules)
+    normed = [p for p, a in enumerate(agents) if getattr(a, "obs_rms", None) is not None]
+    rms_group = ObsRmsGroup([agents[p].obs_rms for p in normed]) if normed else None
+    cursors = PairCursors(P, envs[0].device) if POPULATION_FUSED_CHUNK and all(e.device == envs[0].device for e in envs) else None
+    scales = [a.reward_scale for a in agents]
     for i in range(num_chunks):
-        for p, (env, agent) in enumerate(zip(envs, agents)):
-            out = env.rollout(chunk_steps, out=chunks[p], ring=rings[p], policy_desc=pds[p])
-            schedules[p].update(env.stats[3:4], finished0[p])
-            replays[p].append_chunk(out, reward_scale=agent.reward_scale, last_steps=replay_last_steps)
-            update_obs_rms(agent, out, replay_last_steps)
+        if cursors is None:                       # the per-pair calls, pair by pair
+            for p, (env, agent) in enumerate(zip(envs, agents)):
+                out = env.rollout(chunk_steps, out=chunks[p], ring=rings[p], policy_desc=pds[p])
+                schedules[p].update(env.stats[3:4], finished0[p])
+                replays[p].append_chunk(out, reward_scale=agent.reward_scale, last_steps=replay_last_steps)
+                update_obs_rms(agent, out, replay_last_steps)
+        else:
+            # what changes with the chunk: 16 bytes per pair, known before the rollout -- the one upload of a steady-state chunk
+            cursors.stage(step0=[env.t for env in envs], replay_start=[r.count for r in replays]).upload()
+            outs = env_pop.rollout(chunk_steps, pds, chunks, rings, cursors=cursors)
+            decays.update([env.stats[3:4] for env in envs], finished0)
+            replay_pop.append_chunks(outs, reward_scale=scales, last_steps=replay_last_steps, cursors=cursors)
+            kept = chunk_steps if replay_last_steps is None else min(int(replay_last_steps), chunk_steps)
+            if rms_group is not None and kept > 0:
+                rms_group.update_chunks([outs[p] for p in normed], chunk_steps - kept, chunk_steps)
         for p, l in enumerate(population.train_from(replays, train_iters, copy=True)):
             if l is not None:
                 losses[p].append(l)

@@ -483,6 +483,106 @@ class VecEnv:
         return chunk
 
 
+class VecEnvPopulation:
+    """P :class:`VecEnv` objects -- the env sets of a population of (env, agent) pairs -- rolled out by ONE launch
+    (``ssc_rollout_many``, grid row p = pair p).  The envs are wrapped, not copied: every state array, log, statistics
+    block and episode ring ends up bit for bit as after ``env.rollout`` env by env (the f64 reward sum ``stats[0]`` of an
+    env with more than one workgroup is an atomic sum either way).
+
+    The launch serves actor policies of the shape the population loop's agents use (bf16 MFMA, h1 <= 64, h2 <= 32) with
+    one env kind, one policy class, statistics and a log for all pairs or for none, and no array shared by two pairs;
+    any other population runs ``env.rollout`` pair by pair.  ``fused`` tells which way the last call went.  The launch
+    descriptors stay with the object and are rebuilt only when a pointer, a shape, ``K`` or the stream changes."""
+
+    def __init__(self, envs):
+        self.envs = list(envs)
+        if not self.envs:
+            raise ValueError("a population needs at least one env")
+        self.device = self.envs[0].device
+        if any(e.device != self.device for e in self.envs):
+            raise ValueError("the envs of a population live on one device")
+        self.lib = _ffi.lib()
+        self.fused = None
+        self._sig = self._items = self._own_cursors = self._keep = None
+
+    def __len__(self):
+        return len(self.envs)
+
+    def _prepare(self, K, policy_descs, outs, rings):
+        """Decide the way of this call and bring the launch descriptors up to date -> ``fused``."""
+        sig = (int(K), torch.cuda.current_stream(self.device).cuda_stream,
+               tuple((bytes(e.params), bytes(pd[0]), e.n, e.s0.data_ptr(), e.s1.data_ptr(), e.steps.data_ptr(), e.ep_ret.data_ptr(),
+                      e.ou_x.data_ptr(), e.stats.data_ptr(), e._seed, e.env_id0,
+                      None if (pd[1] or {}).get("_d_obs_rms") is None else pd[1]["_d_obs_rms"].data_ptr(),
+                      None if o is None else (o.act.data_ptr(), o.done.data_ptr(), o.obs.data_ptr(), o.obs2.data_ptr(), o.K, o.N,
+                                              o.act.stride(0), o.done.stride(0), o.obs.stride(0), o.obs2.stride(0)),
+                      None if r is None else (r.cursor.data_ptr(), r.env_id.data_ptr(), r.capacity))
+                     for e, pd, o, r in zip(self.envs, policy_descs, outs, rings)))
+        if sig == self._sig:
+            return self.fused
+        from .population import DeviceItems, served
+        self._sig, self._items = sig, None
+        P = len(self.envs)
+        for e, o in zip(self.envs, outs):
+            if o is not None and (o.K, o.N, o.obs_dim) != (K, e.n, e.obs_dim):
+                raise ValueError("out chunk has the wrong shape")
+        items = DeviceItems(_ffi.RolloutManyItem, P, self.device)
+        for it, e, pd, o, r in zip(items.items, self.envs, policy_descs, outs, rings):
+            it.params, it.policy, it.n, it.state = e.params, pd[0], e.n, e.rollout_state()
+            it.has_log, it.has_ring = int(o is not None), int(r is not None)
+            if o is not None:
+                it.log = o.as_struct()
+            if r is not None:
+                it.ring = r.as_struct()
+            it.d_stats, it.seed, it.env_id0 = e.stats.data_ptr(), e._seed, e.env_id0
+            rms = (pd[1] or {}).get("_d_obs_rms")
+            it.d_rms = None if rms is None else rms.data_ptr()
+        items.upload()
+        # the library's own rules decide: a validation-only call (K = 0 launches nothing, so the device pointers are only
+        # checked for NULL and the cursors may be any array)
+        probe = (_ffi.PairCursor * P)()
+        self.fused = served(self.lib.ssc_rollout_many(items.h_ptr, items.d_ptr, ctypes.addressof(probe), items.d_ptr, P, 0, None))
+        if self.fused:
+            self._items = items
+            self._keep = [pd[1] for pd in policy_descs]      # the weight tensors stay alive with the descriptors
+        return self.fused
+
+    def rollout(self, K, policy_descs, outs=None, rings=None, cursors=None):
+        """``env.rollout(K, out=outs[p], ring=rings[p], log=outs[p] is not None, policy_desc=policy_descs[p])`` for every
+        env -> the list of chunks.  ``policy_descs``: what ``env.policy_desc(policy)`` returns, per env.  ``cursors``: a
+        :class:`population.PairCursors` the caller has staged (``step0`` = every ``env.t``) and uploaded on this stream;
+        None: the object keeps its own."""
+        P = len(self.envs)
+        policy_descs = list(policy_descs)
+        outs = [None] * P if outs is None else list(outs)
+        rings = [None] * P if rings is None else list(rings)
+        if not (len(policy_descs) == len(outs) == len(rings) == P):
+            raise ValueError("one policy descriptor, chunk and ring (or None) per env")
+        for e in self.envs:
+            if e._needs_reset:
+                e.reset()
+        if not self._prepare(K, policy_descs, outs, rings):
+            return [e.rollout(K, out=o, ring=r, log=o is not None, policy_desc=pd)
+                    for e, pd, o, r in zip(self.envs, policy_descs, outs, rings)]
+        for e, o in zip(self.envs, outs):
+            if o is not None:
+                o.step0, o.env_id0 = e.t, e.env_id0
+        if cursors is None:
+            if self._own_cursors is None:
+                from .population import PairCursors
+                self._own_cursors = PairCursors(P, self.device)
+            cursors = self._own_cursors.stage(step0=[e.t for e in self.envs])
+            cursors.upload()
+        elif cursors.step0() != [e.t for e in self.envs]:
+            raise ValueError("cursors: stage step0 = env.t of every env (and upload) before the rollout")
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_rollout_many(self._items.h_ptr, self._items.d_ptr, cursors.h_ptr, cursors.d_ptr, P, int(K),
+                                                 _ffi.stream()))
+        for e in self.envs:
+            e.t += K
+        return outs
+
+
 class SingleEnvView:
     """An N=1 ``VecEnv`` behind the exact scalar ``gym.Env`` protocol of gym 0.10.5:
     ``reset() -> ndarray(obs_dim,)``, ``step(ndarray(act_dim,)) -> (ndarray, float, bool, {})``

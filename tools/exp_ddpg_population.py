@@ -3,6 +3,7 @@
 
     python tools/exp_ddpg_population.py launch --out DIR   # one ssc_ddpg_train_many against P x ssc_ddpg_train; the samplers
     python tools/exp_ddpg_population.py loop --out DIR     # rl_train_vec_ddpg_population against P sequential rl_train_vec_ddpg
+    python tools/exp_ddpg_population.py loop_fused --out DIR   # the population loop on the many-launches against its per-pair form
     python tools/exp_ddpg_population.py probe --agents P   # a few launches of each kind, for a profiler run of its own
 
 launch: P in {1, 8, 64, 256, 512} agents of the shipped shape (64-32, obs_dim 2, tanh layer 2, batch 64), 10 iterations per
@@ -12,7 +13,11 @@ kernel, one after the other.  The samplers (10 batches of 64 per ring) the same 
 of the item fetch; the run-to-run spread of both sides is written beside it.
 loop: P = 64 pairs of 1024 envs, 64-step chunks, 10 iterations per chunk; host clock around 8 chunks between two device
 synchronisations, 3 runs per variant alternating after a warm-up run of each; "rollout_only" is the population loop with no
-iterations (rollouts, epsilon decay, appends), i.e. the part one launch per pair still serialises."""
+iterations (rollouts, epsilon decay, appends), i.e. the part one launch per pair still serialises.
+loop_fused: the same protocol at P in {1, 8, 64}: "fused" is the loop as it is (one rollout, decay and append launch per
+chunk for all pairs), "per_pair" the yardstick -- the same loop with rl_train.POPULATION_FUSED_CHUNK off, i.e. the
+per-pair calls pair by pair as before those launches existed; both train in the one learner launch.  Medians and
+(max - min) / median spreads per variant -> loop_fused.json."""
 import argparse
 import ctypes
 import json
@@ -184,6 +189,48 @@ def loop(out_dir):
     return 0
 
 
+def loop_fused(out_dir):
+    from smartstartcontinuous_amd import rl_train
+    envs, steps, chunks = 1024, 64, 8
+    kw = dict(chunk_steps=steps, replay_capacity=1 << 18, ring_capacity=1 << 16, train_iters=ITERS)
+
+    def run(P, fused):
+        vec, agents = make_pairs(P, envs)
+        rl_train.POPULATION_FUSED_CHUNK = fused
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ssc.rl_train_vec_ddpg_population(vec, agents, chunks, **kw)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / chunks * 1e3
+        finally:
+            rl_train.POPULATION_FUSED_CHUNK = True
+
+    rows = []
+    for P in (1, 8, 64):
+        for fused in (True, False):
+            run(P, fused)
+        times = dict(fused=[], per_pair=[])
+        for _ in range(3):
+            times["fused"].append(run(P, True))
+            times["per_pair"].append(run(P, False))
+        stat = lambda v: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v), spread_ms=max(v) - min(v), runs=v)
+        f, y = stat(times["fused"]), stat(times["per_pair"])
+        row = dict(pairs=P, fused=f, per_pair=y, gain_ms=y["median_ms"] - f["median_ms"], both_spreads_ms=f["spread_ms"] + y["spread_ms"],
+                   per_pair_over_fused=y["median_ms"] / f["median_ms"])
+        row["faster_by_more_than_the_spreads"] = row["gain_ms"] > row["both_spreads_ms"]
+        row["not_slower_by_more_than_the_spreads"] = -row["gain_ms"] <= row["both_spreads_ms"]
+        rows.append(row)
+        print(json.dumps({k: (v["median_ms"] if isinstance(v, dict) else v) for k, v in row.items()}), flush=True)
+    result = dict(shape=dict(envs_per_pair=envs, chunk_steps=steps, iters=ITERS, chunks=chunks, net="64-32"), device=torch.cuda.get_device_name(0),
+                  note="ms per chunk of all pairs, the finishing drain and read-backs of a run included; host clock between two "
+                       "synchronisations; 3 runs per variant alternating after a warm-up run of each",
+                  rows=rows)
+    with open(os.path.join(out_dir, "loop_fused.json"), "w") as f:
+        json.dump(result, f, indent=1)
+    return 0
+
+
 def probe(P):
     """the many-launch at P agents and at one agent, and the single-agent launch, a few times each (told apart in a trace by
     kernel name and grid size)"""
@@ -200,9 +247,10 @@ def probe(P):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["launch", "loop", "probe"])
+    ap.add_argument("what", choices=["launch", "loop", "loop_fused", "probe"])
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ddpg_population"))
     ap.add_argument("--agents", type=int, default=256)
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
-    sys.exit(launch(args.out) if args.what == "launch" else loop(args.out) if args.what == "loop" else probe(args.agents))
+    sys.exit(launch(args.out) if args.what == "launch" else loop(args.out) if args.what == "loop" else
+             loop_fused(args.out) if args.what == "loop_fused" else probe(args.agents))
