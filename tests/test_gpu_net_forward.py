@@ -8,7 +8,8 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.test_gpu_ddpg_stats import CLIP, Device, launch, make_net
+from oracle import ssc_oracle as O
+from tests.test_gpu_ddpg_stats import CLIP, Device, launch, make_net, oracle_kw
 from tests.test_gpu_ddpg_eval import MC, nets, run, stats_block
 
 torch = pytest.importorskip("torch")
@@ -82,16 +83,25 @@ def row_and_generic_agree(case):
 
 
 def test_critic_forward_wide_network(ssc):
-    """400-300 without LayerNorm: (400 + 1) * 256 B of dynamic LDS, beyond the 64 KB a launch gets unasked"""
+    """400-300 without LayerNorm: (400 + 1) * 256 B of dynamic LDS, beyond the 64 KB a launch gets unasked.  Its output
+    against the fp64 oracle on the same weights and the clipped observations, to the tolerance
+    tests/test_gpu_agents.py::test_critic_kde_ucb_kernels holds its 64-32 and 200-100 critics to."""
     from smartstartcontinuous_amd import _ffi
     rng = np.random.default_rng(3)
-    critic = Device(make_net(rng, 2, 400, 1, 300, 1, False, 1.5, 20.0), "critic", 2, 1, True)
+    w = make_net(rng, 2, 400, 1, 300, 1, False, 1.5, 20.0)
+    critic = Device(w, "critic", 2, 1, True)
     obs = sample(rng, 100, 2, None)
     act = torch.as_tensor(rng.uniform(-1, 1, size=(100, 1)).astype(np.float32)).cuda()
     q = torch.full((100,), float("nan"), dtype=torch.float32, device="cuda")
     rc = _ffi.lib().ssc_critic_forward(ctypes.byref(critic.desc), 100, _ffi.ptr(obs), _ffi.ptr(act), _ffi.ptr(q), _stream())
     torch.cuda.synchronize()
     assert rc == _ffi.SSC_OK and torch.isfinite(q).all() and q.std() > 1e-3
+    o = obs.cpu().numpy()
+    assert np.abs(o).max() > CLIP                  # the clip is part of what is compared
+    ref = O.critic_forward(o, act.cpu().numpy(), **oracle_kw(w), last_layer_tanh=True, obs_clip=CLIP)[:, 0]
+    err = float(np.max(np.abs(q.cpu().numpy() - ref)))
+    print("critic 400-300: max |q - ref| = %.2e, |ref|max = %.2f" % (err, np.abs(ref).max()))
+    assert err <= 1e-5 * max(1.0, np.abs(ref).max())
 
 
 STATS_NETS = {"64-32": ((64, 32), False, False), "24-12-ln-rms": ((24, 12), True, True)}
