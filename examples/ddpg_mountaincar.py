@@ -78,19 +78,34 @@ def main():
                 if (episode + 1) % args.stats_every == 0 and len(agent.replay_buffer) >= agent.batch_size:
                     print("  stats:", ", ".join("%s %.6g" % kv for kv in agent.get_stats().items()))
     elif args.population is not None:
-        if args.param_noise is not None or args.stats_every is not None or args.eval_every is not None or args.overlap:
-            ap.error("--population runs the synchronous loop without parameter noise, diagnostics and evaluation")
+        if args.param_noise is not None or args.overlap:
+            ap.error("--population runs the synchronous loop without parameter noise")
         env_id = "MountainCarContinuousActionX%s-v0" % args.power_scalar
-        seeds = [args.seed + p for p in range(args.population)]
+        P = args.population
+        seeds = [args.seed + p for p in range(P)]
         envs = [ssc.VecEnv(env_id, args.envs, seed=s, env_id0=p * args.envs) for p, s in enumerate(seeds)]
         agents = [make_agent(ssc.SingleEnvView(ssc.VecEnv(env_id, 1, seed=s)), s, args.normalize_observations, None, args.popart)
                   for s in seeds]
+        eval_envs = None
+        if args.eval_every is not None:        # envs of their own per pair: another seed, ids behind all training envs'
+            eval_envs = [ssc.VecEnv(env_id, args.eval_envs, seed=s + P, env_id0=P * args.envs + p * args.eval_envs)
+                         for p, s in enumerate(seeds)]
+        monitor = ssc.PopulationMonitor(eval_envs=eval_envs, eval_every=args.eval_every, eval_steps=args.eval_steps,
+                                        stats_every=args.stats_every)
         runs = ssc.rl_train_vec_ddpg_population(envs, agents, num_chunks=args.chunks, chunk_steps=250, replay_capacity=1 << 20,
-                                                train_iters=50, seed=seeds)
-        for s, (summary, losses, replay) in zip(seeds, runs):
+                                                train_iters=50, seed=seeds, monitor=monitor)
+        last = lambda log, k: next((v for v in log[k][::-1] if not np.isnan(v)), float("nan"))   # the last row that was written
+        for s, (summary, losses, replay) in zip(seeds, runs):   # one line per pair
             late = [ret for _steps, ret in summary.episodes[-max(1, len(summary) // 4):]]
-            print("seed %d: %d finished episodes, late-window return %.2f (last quarter of them), last critic/actor loss %.4g / %.4g"
-                  % (s, len(summary), float(np.mean(late)) if late else float("nan"), *losses[-1][-1].tolist()))
+            line = ("seed %d: %d finished episodes, late-window return %.2f (last quarter of them), last critic/actor loss %.4g / %.4g"
+                    % (s, len(summary), float(np.mean(late)) if late else float("nan"), *losses[-1][-1].tolist()))
+            if args.eval_every is not None:
+                line += ", eval/return %.2f eval/Q %.4g over %.0f episodes" % (
+                    last(summary.eval_stats, "eval/return"), last(summary.eval_stats, "eval/Q"), last(summary.eval_stats, "eval/episodes"))
+            if args.stats_every is not None:
+                line += ", reference_Q_mean %.4g reference_action_std %.4g" % (
+                    last(summary.agent_stats, "reference_Q_mean"), last(summary.agent_stats, "reference_action_std"))
+            print(line)
         if args.save_dir:
             os.makedirs(args.save_dir, exist_ok=True)
             for s, (summary, _l, _r) in zip(seeds, runs):

@@ -918,6 +918,73 @@ int ssc_ddpg_eval_rollout(const ssc_env_params *p, const ssc_actor_desc *actor, 
                           uint64_t seed, uint64_t env_id0, uint64_t step0, ssc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Evaluation and diagnostics of a whole population, one launch per phase
+ * -------------------------------------------------------------------------------------
+ * The conventions are ssc_rollout_many's: a host item array that is validated before any HIP call, the caller's device
+ * copy of the same bytes (complete on `stream` before the call) that the kernels read, nothing copied by the library, the
+ * pair's index -- or both indices -- in ssc_last_error().  Workgroups of different pairs share nothing and there are no
+ * atomics: every d_out block, state column and workspace holds, bit for bit, what the pair's own single call leaves.
+ * tests/test_ddpg_monitor_many_host.py holds the structs' sizes and offsets to the ctypes mirrors. */
+
+/* What one ssc_ddpg_eval_rollout call takes, minus step0 (the pair's ssc_pair_cursor; replay_start is ignored), K and
+ * zero_returns (one value per call), the transition log and d_q (the many-form writes neither: the single call stays for
+ * traces). */
+struct ssc_ddpg_eval_many_item {
+    ssc_env_params    params;
+    ssc_actor_desc    actor;
+    ssc_critic_desc   critic;
+    float             act_low, act_high;
+    int64_t           n;               /* >= 1, per pair */
+    ssc_rollout_state state;           /* ou_x is not used */
+    const double     *d_rms;           /* normalize_observations block or NULL, per pair */
+    double           *d_out;           /* [SSC_DDPG_N_EVAL] */
+    void             *d_workspace;
+    size_t            workspace_bytes; /* >= ssc_ddpg_eval_workspace_bytes(n) */
+    uint64_t          seed, env_id0;
+};
+typedef struct ssc_ddpg_eval_many_item ssc_ddpg_eval_many_item;
+
+/* ssc_ddpg_eval_rollout for n_pairs (eval-env set, agent) pairs in one fused launch plus one merge launch.  Grid row p
+ * runs pair p's workgroups (grid x = the largest pair's workgroup count; a smaller pair's surplus workgroups leave at once,
+ * before any barrier); the merge launch has one workgroup per pair.
+ * Uniform over the population: the env kind (SSC_EINVAL naming the first pair that differs from pair 0).  Per pair, read at
+ * run time: the layer sizes of both networks (the kernel is shape-generic: 64-32, 128-64 and 200-100 agents may share a
+ * launch), LayerNorm, last_layer_tanh, obs_clip, d_rms (set or NULL), env constants, action bounds, n, seed, env_id0.
+ * The weights are staged in LDS iff EVERY pair's networks fit beside its activations (and SSC_DDPG_EVAL_GLOBAL_WEIGHTS is
+ * not set); the bits do not depend on it.  The launch's dynamic LDS size is the largest pair's.
+ * Every item passes ssc_ddpg_eval_rollout's checks with its error codes (SSC_EUNSUPPORTED for act_dim != 1 or a tile
+ * beyond LDS).  No two pairs share a state column, a d_out block or a workspace (SSC_EINVAL naming both); weights may be
+ * shared -- they are only read, so one agent evaluated on two env sets is legal.  n_pairs 1..65535.
+ * K == 0: SSC_OK without a launch (the validation-only call the wrappers use). */
+int ssc_ddpg_eval_rollout_many(const ssc_ddpg_eval_many_item *h_items, const ssc_ddpg_eval_many_item *d_items,
+                               const ssc_pair_cursor *h_cursors, const ssc_pair_cursor *d_cursors, int32_t n_pairs, int32_t K,
+                               int32_t zero_returns, ssc_stream_t stream);
+
+/* The arguments of one ssc_ddpg_stats call. */
+struct ssc_ddpg_stats_many_item {
+    ssc_actor_desc  actor;
+    ssc_critic_desc critic;
+    ssc_actor_desc  perturbed;            /* read when has_perturbed */
+    int32_t         has_perturbed;        /* per pair; 0: slots 8-9 are NaN */
+    int64_t         m;                    /* 0..4096, per pair; 0: the pair is skipped */
+    const float    *d_obs, *d_act;
+    const double   *d_rms;                /* or NULL, per pair */
+    const float    *d_param_noise_stddev; /* or NULL, per pair */
+    double         *d_out;                /* [SSC_DDPG_N_STATS] */
+    void           *d_workspace;
+    size_t          workspace_bytes;      /* >= ssc_ddpg_stats_workspace_bytes(m) */
+};
+typedef struct ssc_ddpg_stats_many_item ssc_ddpg_stats_many_item;
+
+/* ssc_ddpg_stats for n_pairs agents in two launches (replaces two per agent): grid row p of the first runs pair p's row
+ * tiles, workgroup p of the second merges them.  Everything is per pair: shapes, LayerNorm, d_rms, the perturbed copy, m.
+ * A pair with m == 0 is skipped -- no workgroup works for it, its d_out is left untouched and nothing else of its item is
+ * read (a pair that has no sample yet); all m == 0: SSC_OK without a launch.  Every other item passes ssc_ddpg_stats's
+ * checks with its error codes.  No two pairs with m > 0 share a d_out block or a workspace (SSC_EINVAL naming both). */
+int ssc_ddpg_stats_many(const ssc_ddpg_stats_many_item *h_items, const ssc_ddpg_stats_many_item *d_items, int32_t n_pairs,
+                        ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Dynamics-model training step
  * ------------------------------------------------------------------------------------- */
 

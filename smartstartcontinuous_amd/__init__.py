@@ -10,8 +10,8 @@ from . import _ffi  # noqa: F401
 from .spaces import Box, EnvSpec  # noqa: F401
 from .vec_env import (ActorPolicy, Continuous_MountainCarEnv_Editted, EpisodeRing, MpcPolicy, RandomPolicy,  # noqa: F401
                       SingleEnvView, TransitionChunk, VecEnv, VecEnvPopulation, make)
-from .rl_train import (Episode, Summary, rlTrain, rl_train_vec, rl_train_vec_ddpg, rl_train_vec_ddpg_population,  # noqa: F401,E402
-                       rl_train_vec_smartstart)
+from .rl_train import (Episode, PopulationMonitor, Summary, rlTrain, rl_train_vec, rl_train_vec_ddpg,  # noqa: F401,E402
+                       rl_train_vec_ddpg_population, rl_train_vec_smartstart)
 from .replay_buffer import DeviceReplayBuffer, DeviceReplayPopulation, ReplayBuffer, append_chunks  # noqa: F401,E402
 from .smartstart import SmartStartContinuous, VecSmartStart  # noqa: F401,E402
 from .agents import DDPGPopulation  # noqa: F401,E402

@@ -179,6 +179,18 @@ class ObsRmsItem(Structure):
                 ("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
+class DdpgEvalManyItem(Structure):
+    _fields_ = [("params", EnvParams), ("actor", ActorDesc), ("critic", CriticDesc), ("act_low", c_float), ("act_high", c_float),
+                ("n", c_int64), ("state", RolloutState), ("d_rms", c_void_p), ("d_out", c_void_p), ("d_workspace", c_void_p),
+                ("workspace_bytes", c_size_t), ("seed", c_uint64), ("env_id0", c_uint64)]
+
+
+class DdpgStatsManyItem(Structure):
+    _fields_ = [("actor", ActorDesc), ("critic", CriticDesc), ("perturbed", ActorDesc), ("has_perturbed", c_int32), ("m", c_int64),
+                ("d_obs", c_void_p), ("d_act", c_void_p), ("d_rms", c_void_p), ("d_param_noise_stddev", c_void_p),
+                ("d_out", c_void_p), ("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
 # C struct -> its ctypes mirror: the struct-layout table (the tests compare sizeof / offsetof as the C compiler sees them)
 STRUCTS = {
     "ssc_env_params": EnvParams, "ssc_actor_desc": ActorDesc, "ssc_ou_desc": OuDesc, "ssc_policy_desc": PolicyDesc,
@@ -188,7 +200,8 @@ STRUCTS = {
     "ssc_ddpg_desc": DdpgDesc, "ssc_replay_view": ReplayView, "ssc_replay_ring": ReplayRing,
     "ssc_mlp_train_desc": MlpTrainDesc, "ssc_ddpg_many_item": DdpgManyItem, "ssc_replay_sample_key": ReplaySampleKey,
     "ssc_pair_cursor": PairCursor, "ssc_rollout_many_item": RolloutManyItem, "ssc_replay_append_item": ReplayAppendItem,
-    "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem,
+    "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem, "ssc_ddpg_eval_many_item": DdpgEvalManyItem,
+    "ssc_ddpg_stats_many_item": DdpgStatsManyItem,
 }
 
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
@@ -272,6 +285,9 @@ _SIGNATURES = {
     "ssc_ddpg_eval_rollout": (c_int, [POINTER(EnvParams), POINTER(ActorDesc), POINTER(CriticDesc), c_float, c_float, c_int64, c_int32,
                                       POINTER(RolloutState), c_void_p, POINTER(TransitionLog), c_void_p, c_int32, c_void_p, c_void_p,
                                       c_size_t, c_uint64, c_uint64, c_uint64, c_void_p]),
+    # both for a whole population, one launch per phase: host items / cursors (validated) + the caller's device copies
+    "ssc_ddpg_eval_rollout_many": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "ssc_ddpg_stats_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "ssc_dataset_scan_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_dataset_scan": (c_int, [POINTER(TransitionLog), c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),

@@ -825,7 +825,10 @@ class DDPGPopulation:
     Index and loss tensors and the pinned-host and device copies of the launch descriptors stay with the population and
     are rebuilt only when a pointer, an iteration count or a ring changes: in steady state a call uploads the P sampling
     keys and nothing else.  The loss tensors a call returns are therefore views of one buffer the NEXT call overwrites
-    (``copy=True`` returns views of a fresh copy instead)."""
+    (``copy=True`` returns views of a fresh copy instead).
+
+    What the agents of a sweep are compared by comes in one launch per phase too: :meth:`evaluate_device` (eval/return,
+    eval/Q) and :meth:`get_stats_device` (the ``get_stats`` diagnostics), for any mix of network shapes."""
 
     B = 64
 
@@ -984,6 +987,174 @@ class DDPGPopulation:
                 out.append(block[off:off + k] if k > 0 else None)
                 off += k
             return out
+
+    # ---- evaluation and diagnostics: what a sweep's agents are compared by, one launch per phase ---------------------
+    # Both calls wrap the per-agent methods' kernels (``ssc_ddpg_eval_rollout_many`` / ``ssc_ddpg_stats_many``: grid row p
+    # runs agent p exactly as its own launch would) and do, object by object, the per-agent methods' host bookkeeping.
+    # Unlike the learner launch they take any mix of network shapes, LayerNorm and normalize_observations.  A population
+    # the launch does not serve -- an agent with normalize_returns (the Pop-Art denormalisation lives in the per-agent
+    # path), mixed env kinds, shared arrays -- runs the per-agent calls; ``eval_fused`` / ``stats_fused`` tell which way
+    # the last call went.  Descriptors are rebuilt only when a pointer, a shape or the stream changes.
+    eval_fused = stats_fused = None
+
+    def _out_block(self, out, cols):
+        P = len(self.agents)
+        if out is None:
+            return torch.empty((P, cols), dtype=torch.float64, device=self.device)
+        if out.dtype != torch.float64 or tuple(out.shape) != (P, cols) or not out.is_contiguous() or out.device != self.agents[0].actor_flat.device:
+            raise ValueError(f"out must be a contiguous float64 [{P}, {cols}] tensor on {self.device}")
+        return out
+
+    def _workspaces(self, name, sizes):
+        """one buffer, a 256-byte aligned slice per pair -> the slices"""
+        offs = [0]
+        for s in sizes:
+            offs.append(offs[-1] + (int(s) + 255) // 256 * 256)
+        ws = getattr(self, name, None)
+        if ws is None or ws.numel() < offs[-1]:
+            ws = torch.empty(max(offs[-1], 256), dtype=torch.uint8, device=self.device)
+            setattr(self, name, ws)
+        return [ws[o:o + int(s)] for o, s in zip(offs, sizes)]
+
+    def evaluate_device(self, eval_envs, nb_eval_steps, out=None, carry_returns=False):
+        """``agent.evaluate_device(eval_env, nb_eval_steps, out=out[p], carry_returns=...)`` for every (agent, eval VecEnv)
+        pair -> the float64 DEVICE tensor [P, SSC_DDPG_N_EVAL], row p in ``EVAL_NAMES`` order, bit for bit what the
+        per-agent call writes; every eval env's state and step counter ``t`` move as there (reset first if it never was).
+        One fused launch plus one merge launch for the whole population; no transition log and no Q buffer (the per-agent
+        call stays for traces).  No host read; enqueued on the current stream."""
+        from .population import DeviceItems, PairCursors, served
+        ag, envs = self.agents, list(eval_envs)
+        K, P = int(nb_eval_steps), len(ag)
+        if K < 1 or K != nb_eval_steps:
+            raise ValueError("nb_eval_steps must be a positive integer")
+        if len(envs) != P:
+            raise ValueError("one eval env per agent")
+        for a, e in zip(ag, envs):
+            if e.obs_dim != a.obs_dim:
+                raise ValueError(f"eval_env observes {e.obs_dim} values, the agent's networks take {a.obs_dim}")
+            if e.s0.device != a.actor_flat.device:
+                raise ValueError(f"eval_env lives on {e.s0.device}, the agent on {a.actor_flat.device}")
+        out = self._out_block(out, _ffi.SSC_DDPG_N_EVAL)
+        for e in envs:
+            if e._needs_reset:
+                e.reset()
+        sig = (torch.cuda.current_stream(self.device).cuda_stream, out.data_ptr(),
+               tuple((bytes(e.params), bytes(a._desc), bytes(a._critic_desc), float(e.action_space.low[0]), float(e.action_space.high[0]),
+                      e.n, e.s0.data_ptr(), e.s1.data_ptr(), e.steps.data_ptr(), e.ep_ret.data_ptr(),
+                      None if a.obs_rms is None else a._rms_block().data_ptr(), e._seed, e.env_id0, a.ret_rms is not None)
+                     for a, e in zip(ag, envs)))
+        if sig != getattr(self, "_eval_sig", None):
+            self._eval_sig, self._eval_items, self.eval_fused = sig, None, False
+            if all(a.ret_rms is None for a in ag):
+                with torch.cuda.device(self.device):
+                    sizes = [int(self.lib.ssc_ddpg_eval_workspace_bytes(e.n)) for e in envs]
+                    ws = self._workspaces("_eval_ws", sizes)
+                    items = DeviceItems(_ffi.DdpgEvalManyItem, P, self.device)
+                    for p, (it, a, e) in enumerate(zip(items.items, ag, envs)):
+                        it.params, it.actor, it.critic = e.params, a._desc, a._critic_desc
+                        it.act_low, it.act_high = float(e.action_space.low[0]), float(e.action_space.high[0])
+                        it.n, it.state = e.n, e.rollout_state(ou=False)
+                        it.d_rms = None if a.obs_rms is None else a._rms_block().data_ptr()
+                        it.d_out, it.d_workspace, it.workspace_bytes = out[p].data_ptr(), ws[p].data_ptr(), sizes[p]
+                        it.seed, it.env_id0 = e._seed, e.env_id0
+                    items.upload()
+                # the library's own rules decide: a validation-only call (K = 0 launches nothing; the cursors may be any array)
+                probe = (_ffi.PairCursor * P)()
+                self.eval_fused = served(self.lib.ssc_ddpg_eval_rollout_many(items.h_ptr, items.d_ptr, ctypes.addressof(probe),
+                                                                             items.d_ptr, P, 0, 1, None))
+                if self.eval_fused:
+                    self._eval_items, self._eval_keep = items, ws
+                    if getattr(self, "_eval_cursors", None) is None:
+                        self._eval_cursors = PairCursors(P, self.device)
+        if not self.eval_fused:
+            for p, (a, e) in enumerate(zip(ag, envs)):
+                a.evaluate_device(e, K, out=out[p], carry_returns=carry_returns)
+            return out
+        cursors = self._eval_cursors.stage(step0=[e.t for e in envs])
+        cursors.upload()
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_ddpg_eval_rollout_many(self._eval_items.h_ptr, self._eval_items.d_ptr, cursors.h_ptr, cursors.d_ptr,
+                                                           P, K, 0 if carry_returns else 1, _ffi.stream()))
+        for e in envs:
+            e.t += K
+        return out
+
+    def evaluate(self, eval_envs, nb_eval_steps, **kw):
+        """:meth:`evaluate_device` as a list of dicts by ``EVAL_NAMES``, one per agent.  Reads the device block (one device ->
+        host copy for the population)."""
+        rows = self.evaluate_device(eval_envs, nb_eval_steps, **kw).cpu().tolist()
+        return [a.eval_dict(r) for a, r in zip(self.agents, rows)]
+
+    def get_stats_device(self, replays=None, out=None):
+        """``agent.get_stats_device(replay, out=out[p])`` for every agent -> the float64 DEVICE tensor
+        [P, SSC_DDPG_N_STATS], row p in ``STATS_NAMES`` order, bit for bit what the per-agent call writes.  An agent without
+        a fixed sample draws and keeps ``batch_size`` records of its replay (``replays[p]``, default its own buffer) exactly
+        as its own call would; one whose replay holds fewer has no sample yet: it is skipped and row p of ``out`` is left as
+        it is (NaN in a block this call allocates).  Two launches for the whole population; no host read."""
+        from .population import DeviceItems
+        ag, P = self.agents, len(self.agents)
+        replays = [None] * P if replays is None else list(replays)
+        if len(replays) != P:
+            raise ValueError("one replay (or None) per agent")
+        out = torch.full((P, _ffi.SSC_DDPG_N_STATS), float("nan"), dtype=torch.float64, device=self.device) if out is None \
+            else self._out_block(out, _ffi.SSC_DDPG_N_STATS)
+        have = []
+        for a, r in zip(ag, replays):
+            if getattr(a, "stats_sample", None) is None:
+                r = a.replay_buffer if r is None else r
+                if len(r) >= a.batch_size:
+                    a._draw_stats_sample(r)
+            have.append(getattr(a, "stats_sample", None) is not None)
+        noisy = [a.param_noise is not None for a in ag]
+        sig = (torch.cuda.current_stream(self.device).cuda_stream, out.data_ptr(),
+               tuple((bytes(a._desc), bytes(a._critic_desc), bytes(a._perturbed_desc) if pn else None,
+                      a.d_param_noise_stddev.data_ptr() if pn else None,
+                      (a.stats_sample[0].data_ptr(), a.stats_sample[1].data_ptr(), a.stats_sample[0].shape[0]) if h else None,
+                      None if a.obs_rms is None else a._rms_block().data_ptr(), a.ret_rms is not None)
+                     for a, pn, h in zip(ag, noisy, have)))
+        if sig != getattr(self, "_stats_sig", None):
+            self._stats_sig, self._stats_items = sig, None
+            self.stats_fused = all(a.ret_rms is None for a in ag) and all(a.device == self.device for a in ag)
+            if self.stats_fused:
+                with torch.cuda.device(self.device):
+                    m = [a.stats_sample[0].shape[0] if h else 0 for a, h in zip(ag, have)]
+                    sizes = [int(self.lib.ssc_ddpg_stats_workspace_bytes(k)) for k in m]
+                    ws = self._workspaces("_stats_ws", sizes)
+                    items = DeviceItems(_ffi.DdpgStatsManyItem, P, self.device)
+                    for p, (it, a) in enumerate(zip(items.items, ag)):
+                        it.actor, it.critic, it.m = a._desc, a._critic_desc, m[p]
+                        if noisy[p]:
+                            it.perturbed, it.has_perturbed = a._perturbed_desc, 1
+                            it.d_param_noise_stddev = a.d_param_noise_stddev.data_ptr()
+                        if have[p]:
+                            it.d_obs, it.d_act = a.stats_sample[0].data_ptr(), a.stats_sample[1].data_ptr()
+                        it.d_rms = None if a.obs_rms is None else a._rms_block().data_ptr()
+                        it.d_out, it.d_workspace, it.workspace_bytes = out[p].data_ptr(), ws[p].data_ptr(), sizes[p]
+                    items.upload()
+                self._stats_items, self._stats_keep = items, ws
+        if not self.stats_fused:
+            for p, (a, r) in enumerate(zip(ag, replays)):
+                if have[p]:
+                    a.get_stats_device(r, out=out[p])
+            return out
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.ssc_ddpg_stats_many(self._stats_items.h_ptr, self._stats_items.d_ptr, P, _ffi.stream()))
+        return out
+
+    def get_stats(self, replays=None):
+        """:meth:`get_stats_device` as a list of dicts, one per agent, each what ``agent.get_stats`` returns (an agent
+        without a sample yet: only what does not come from the block).  Reads the device block (one device -> host copy)."""
+        rows = self.get_stats_device(replays).cpu().tolist()
+        res = []
+        for a, r in zip(self.agents, rows):
+            stats = a.stats_dict(r)
+            if a.ret_rms is not None:                            # setup_stats lists ret_rms first (ddpg_editted.py:223-225)
+                mean, std = a.ret_rms.mean_std()
+                stats = {"ret_rms_mean": float(mean[0]), "ret_rms_std": float(std[0]), **stats}
+            if a.param_noise is not None:
+                stats = {**stats, **a.param_noise.get_stats()}
+            res.append(stats)
+        return res
 
 
 # ---------------------------------------------------------------------------- navigator --

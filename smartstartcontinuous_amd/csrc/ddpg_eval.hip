@@ -17,7 +17,18 @@
 //   * ddpg_eval_merge_kernel: one wave per stream merges the workgroup partials -- every lane its contiguous share in
 //     workgroup order, then a fixed tree over the lanes -- and one thread writes the block.
 // No atomics, no ticket; the grid depends on n alone, so the block is the same bits run to run.
+//
+// A population of (eval-env set, agent) pairs (ssc_ddpg_eval_rollout_many): both kernel bodies are device functions; the
+// *_many kernels run them for the pair of their grid row, with the arguments the single call would have put into the
+// kernarg formed from the pair's item by the SAME host-and-device functions (fill_net, eval_carve, pack_eval).  Workgroups
+// of different pairs share nothing, so every pair's bits are those of its own launch.
+#include <stdio.h>
 #include <stdlib.h>
+
+#include <algorithm>
+#include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "ddpg_rows.h"
 #include "ssc_device.h"
@@ -37,6 +48,7 @@ constexpr size_t kLdsBytes = 160 * 1024;
 struct McEnv {
     using Const = McConst;
     static constexpr int OBS = 2;
+    static SSC_HD Const make_const(const ssc_env_params &p) { return make_mc_const(p); }
     float pos, vel;
     __device__ void load(float a, float b) { pos = a; vel = b; }
     __device__ void observe(float (&o)[OBS]) const { o[0] = pos; o[1] = vel; }
@@ -49,6 +61,7 @@ struct McEnv {
 struct PendEnv {
     using Const = PendConst;
     static constexpr int OBS = 3;
+    static SSC_HD Const make_const(const ssc_env_params &p) { return make_pend_const(p); }
     float th, thdot;
     __device__ void load(float a, float b) { th = a; thdot = b; }
     __device__ void observe(float (&o)[OBS]) const { pend_observe_one(th, thdot, o[0], o[1], o[2]); }
@@ -61,9 +74,18 @@ struct PendEnv {
     __device__ float s1() const { return thdot; }
 };
 
+// LDS carve of one workgroup, in floats: the partial records (f64, at offset 0), rows of 16 floats ([unit][env]), then --
+// wlds -- the weight images
+struct EvalCarve {
+    int32_t off_RED, off_XA, off_XC, off_H1, off_H2, off_PI, off_Q, off_AW, off_CW;
+    int64_t act_floats;                        // the activations alone
+    int64_t weight_floats;                     // both images
+    int64_t floats;                            // what the launch needs: act_floats (+ weight_floats when wlds)
+};
+
 struct EvalArgs {
     StatsNet actor, critic;                    // device (global) pointers
-    int32_t off_RED, off_XA, off_XC, off_H1, off_H2, off_PI, off_Q, off_AW, off_CW;   // LDS float offsets
+    EvalCarve lds;
     int64_t n;
     int32_t K;
     ssc_rollout_state st;
@@ -77,16 +99,57 @@ struct EvalArgs {
 };
 
 // floats of a network's LDS image: W1 | b1 | W2 | b2 | W3 | b3 | (gamma1 | beta1 | gamma2 | beta2)
-int64_t net_floats(int in_dim, int n_extra, int h1, int h2, int out_dim, bool ln) {
+SSC_HD int64_t net_floats(int in_dim, int n_extra, int h1, int h2, int out_dim, bool ln) {
     return (int64_t)in_dim * h1 + h1 + ((int64_t)h1 + n_extra) * h2 + h2 + (int64_t)h2 * out_dim + out_dim + (ln ? 2 * ((int64_t)h1 + h2) : 0);
+}
+
+// ONE function of (obs_dim, layer sizes, LayerNorm, wlds) for the host (launch size, the WLDS decision) and for a workgroup
+// of the population launch, which carves for its own pair: the two cannot disagree.
+SSC_HD EvalCarve eval_carve(int od, int ah1, int ah2, bool aln, int ch1, int ch2, bool cln, bool wlds) {
+    EvalCarve c{};
+    int64_t q = 0;
+    c.off_RED = (int32_t)q; q += (int64_t)kSR * kEPart * 2;
+    c.off_XA = (int32_t)q;  q += (int64_t)od * kSR;
+    c.off_XC = (int32_t)q;  q += (int64_t)od * kSR;
+    c.off_H1 = (int32_t)q;  q += (ah1 > (int64_t)ch1 + 1 ? ah1 : (int64_t)ch1 + 1) * kSR;
+    c.off_H2 = (int32_t)q;  q += (int64_t)(ah2 > ch2 ? ah2 : ch2) * kSR;
+    c.off_PI = (int32_t)q;  q += kSR;
+    c.off_Q = (int32_t)q;   q += kSR;
+    c.act_floats = q;
+    const int64_t wa = net_floats(od, 0, ah1, ah2, 1, aln), wc = net_floats(od, 1, ch1, ch2, 1, cln);
+    c.weight_floats = wa + wc;
+    if (wlds) {
+        c.off_AW = (int32_t)q; q += wa;
+        c.off_CW = (int32_t)q; q += wc;
+    }
+    c.floats = q;
+    return c;
+}
+
+SSC_HD int eval_blocks(int64_t n) { return (int)((n + kSR - 1) / kSR); }
+
+// The kernel arguments of one (eval-env set, agent): no log, no Q buffer (ssc_ddpg_eval_rollout adds its own).  The host
+// packs them into the kernarg of the single launch, a workgroup of the population launch from its pair's item.
+SSC_HD void pack_eval(EvalArgs &a, const ssc_actor_desc &actor, const ssc_critic_desc &critic, float act_low, float act_high,
+                      int64_t n, int32_t K, const ssc_rollout_state &st, const double *rms, int32_t zero_returns, double *part,
+                      uint64_t seed, uint64_t env_id0, uint64_t step0, bool wlds) {
+    fill_net(a.actor, actor.W1, actor.b1, actor.W2, actor.b2, actor.W3, actor.b3, actor.ln1_g, actor.ln1_b, actor.ln2_g, actor.ln2_b,
+             actor.h1, actor.h2, actor.last_layer_tanh, actor.obs_clip);
+    fill_net(a.critic, critic.W1, critic.b1, critic.W2, critic.b2, critic.W3, critic.b3, critic.ln1_g, critic.ln1_b, critic.ln2_g,
+             critic.ln2_b, critic.h1, critic.h2, critic.last_layer_tanh, critic.obs_clip);
+    a.lds = eval_carve(actor.obs_dim, actor.h1, actor.h2, actor.ln1_g != nullptr, critic.h1, critic.h2, critic.ln1_g != nullptr, wlds);
+    a.n = n; a.K = K; a.st = st; a.has_log = 0; a.zero_returns = zero_returns != 0; a.q = nullptr; a.rms = rms;
+    a.act_low = act_low; a.act_high = act_high; a.seed = seed; a.env_id0 = env_id0; a.step0 = step0;
+    a.part = part;
 }
 
 // block-cooperative copy of a network into LDS (layout of net_floats); the caller's next barrier publishes it
 __device__ StatsNet stage_net(const StatsNet &g, float *img, int in_dim, int n_extra, int out_dim, int tid) {
     StatsNet l = g;
     float *p = img;
-    auto put = [&](const float *src, int count) {
-        for (int e = tid; e < count; e += kSThreads) p[e] = src[e];
+    auto put = [&](const float *src, int count) {   // (the source is global memory: no FLAT loads out of a population item)
+        const SSC_GLOBAL float *gsrc = (const SSC_GLOBAL float *)src;
+        for (int e = tid; e < count; e += kSThreads) p[e] = gsrc[e];
         const float *at = p;
         p += count;
         return at;
@@ -114,18 +177,27 @@ __device__ __forceinline__ void welford(Moments &m, double x) {
     m.m2 = fma(d, x - m.mean, m.m2);
 }
 
+// The whole launch of one (eval-env set, agent): workgroup blockIdx.x of ITS grid row.  Shared by ddpg_eval_kernel (the
+// arguments are its kernarg) and ddpg_eval_many_kernel (the arguments are formed from the pair's item); by value, as
+// rollout_body takes its arguments (rollout.hip).
+// Without WLDS the weights are read through address-space-1 pointers: out of the kernarg the compiler proves that itself,
+// out of a population item it cannot, and every weight load of the K-step loop would be a FLAT instruction.
 template <class EnvT, bool WLDS>
-__global__ __launch_bounds__(kSThreads) void ddpg_eval_kernel(typename EnvT::Const ec, EvalArgs a) {
+__device__ __forceinline__ void eval_body(const typename EnvT::Const ec, const EvalArgs a) {
     constexpr int OBS = EnvT::OBS;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
-    StatsNet actor = a.actor, critic = a.critic;
+    using Net = std::conditional_t<WLDS, StatsNet, GlobalNet>;
+    Net actor, critic;
     if constexpr (WLDS) {   // published by the barrier in front of the first forward pass
-        actor = stage_net(a.actor, lds + a.off_AW, OBS, 0, 1, tid);
-        critic = stage_net(a.critic, lds + a.off_CW, OBS, 1, 1, tid);
+        actor = stage_net(a.actor, lds + a.lds.off_AW, OBS, 0, 1, tid);
+        critic = stage_net(a.critic, lds + a.lds.off_CW, OBS, 1, 1, tid);
+    } else {
+        actor = global_net(a.actor);
+        critic = global_net(a.critic);
     }
-    float *xa = lds + a.off_XA, *xc = lds + a.off_XC, *h1s = lds + a.off_H1, *h2s = lds + a.off_H2;
-    float *pi = lds + a.off_PI, *qv = lds + a.off_Q;
+    float *xa = lds + a.lds.off_XA, *xc = lds + a.lds.off_XC, *h1s = lds + a.lds.off_H1, *h2s = lds + a.lds.off_H2;
+    float *pi = lds + a.lds.off_PI, *qv = lds + a.lds.off_Q;
 
     // ---- lanes 0-15: the env of this lane; envs past n shadow env n - 1, write nothing and stay out of the reduction ----
     const int64_t env0 = (int64_t)blockIdx.x * kSR;
@@ -212,7 +284,7 @@ __global__ __launch_bounds__(kSThreads) void ddpg_eval_kernel(typename EnvT::Con
         a.st.ep_ret[i] = ep_ret;
     }
     // ---- the workgroup's envs in env order (Chan) -> its record in the workspace ----
-    double *red = reinterpret_cast<double *>(lds + a.off_RED);   // [16 envs][kEPart]
+    double *red = reinterpret_cast<double *>(lds + a.lds.off_RED);   // [16 envs][kEPart]
     if (owner) {
         double *r = red + tid * kEPart;
         r[0] = mq.n; r[1] = mq.mean; r[2] = mq.m2;
@@ -239,8 +311,31 @@ __global__ __launch_bounds__(kSThreads) void ddpg_eval_kernel(typename EnvT::Con
     }
 }
 
-__global__ __launch_bounds__((kEStreams + 1) * 64) void ddpg_eval_merge_kernel(const double *__restrict__ part, int32_t n_blocks,
-                                                                                double *__restrict__ out) {
+template <class EnvT, bool WLDS>
+__global__ __launch_bounds__(kSThreads) void ddpg_eval_kernel(typename EnvT::Const ec, EvalArgs a) {
+    eval_body<EnvT, WLDS>(ec, a);
+}
+
+// A population in one launch (ssc_ddpg_eval_rollout_many): blockIdx.y is the pair.  Its item and cursor sit at
+// workgroup-uniform addresses (scalar loads); a workgroup beyond its pair's block count leaves as a whole, before any
+// barrier.  WLDS is one value per launch (every pair's weights fit, or none is staged); everything else -- layer sizes,
+// LayerNorm, last_layer_tanh, d_rms, the LDS carve -- is the pair's own, read at run time as in the single launch.
+// Pointers read out of the item are generic to the compiler: the state loads / stores around the step loop are FLAT
+// instructions here; inside the loop nothing but LDS is touched with WLDS, and the weight loads go through global_net
+// without it.
+template <class EnvT, bool WLDS>
+__global__ __launch_bounds__(kSThreads) void ddpg_eval_many_kernel(const ssc_ddpg_eval_many_item *__restrict__ items,
+                                                                   const ssc_pair_cursor *__restrict__ cursors, int32_t K,
+                                                                   int32_t zero_returns) {
+    const ssc_ddpg_eval_many_item &it = items[blockIdx.y];
+    if ((int64_t)blockIdx.x * kSR >= it.n) return;
+    EvalArgs a;
+    pack_eval(a, it.actor, it.critic, it.act_low, it.act_high, it.n, K, it.state, it.d_rms, zero_returns,
+              static_cast<double *>(it.d_workspace), it.seed, it.env_id0, cursors[blockIdx.y].step0, WLDS);
+    eval_body<EnvT, WLDS>(EnvT::make_const(it.params), a);
+}
+
+__device__ __forceinline__ void eval_merge_body(const double *__restrict__ part, int32_t n_blocks, double *__restrict__ out) {
     const int s = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const double nan = __builtin_nan("");
     const int per = (n_blocks + 63) / 64;
@@ -280,19 +375,29 @@ __global__ __launch_bounds__((kEStreams + 1) * 64) void ddpg_eval_merge_kernel(c
     }
 }
 
-int eval_blocks(int64_t n) { return (int)((n + kSR - 1) / kSR); }
+__global__ __launch_bounds__((kEStreams + 1) * 64) void ddpg_eval_merge_kernel(const double *__restrict__ part, int32_t n_blocks,
+                                                                                double *__restrict__ out) {
+    eval_merge_body(part, n_blocks, out);
+}
+
+// workgroup p merges pair p's partials exactly as the pair's own merge launch
+__global__ __launch_bounds__((kEStreams + 1) * 64) void ddpg_eval_merge_many_kernel(const ssc_ddpg_eval_many_item *__restrict__ items) {
+    const ssc_ddpg_eval_many_item &it = items[blockIdx.x];
+    eval_merge_body(static_cast<const double *>(it.d_workspace), eval_blocks(it.n), it.d_out);
+}
 
 constexpr int64_t kEMaxEnvs = (int64_t)1 << 30;   // as ssc_rollout
+
+int raise_lds(const void *fn, size_t lds, const char *what) {
+    if (lds <= 64 * 1024) return SSC_OK;
+    return check_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), what);
+}
 
 template <class EnvT>
 int launch_eval(const typename EnvT::Const &ec, const EvalArgs &a, bool wlds, size_t lds, hipStream_t s) {
     const void *fn = wlds ? reinterpret_cast<const void *>(ddpg_eval_kernel<EnvT, true>)
                           : reinterpret_cast<const void *>(ddpg_eval_kernel<EnvT, false>);
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                           "hipFuncSetAttribute(ddpg_eval_kernel)");
-        if (rc) return rc;
-    }
+    if (int rc = raise_lds(fn, lds, "hipFuncSetAttribute(ddpg_eval_kernel)")) return rc;
     const int nb = eval_blocks(a.n);
     if (wlds)
         hipLaunchKernelGGL((ddpg_eval_kernel<EnvT, true>), dim3(nb), dim3(kSThreads), lds, s, ec, a);
@@ -300,6 +405,72 @@ int launch_eval(const typename EnvT::Const &ec, const EvalArgs &a, bool wlds, si
         hipLaunchKernelGGL((ddpg_eval_kernel<EnvT, false>), dim3(nb), dim3(kSThreads), lds, s, ec, a);
     return SSC_OK;
 }
+
+template <class EnvT>
+int launch_eval_many(const ssc_ddpg_eval_many_item *d_items, const ssc_pair_cursor *d_cursors, int32_t n_pairs, int32_t K,
+                     int32_t zero_returns, int64_t n_max, bool wlds, size_t lds, hipStream_t s) {
+    const void *fn = wlds ? reinterpret_cast<const void *>(ddpg_eval_many_kernel<EnvT, true>)
+                          : reinterpret_cast<const void *>(ddpg_eval_many_kernel<EnvT, false>);
+    if (int rc = raise_lds(fn, lds, "hipFuncSetAttribute(ddpg_eval_many_kernel)")) return rc;
+    const dim3 grid((unsigned)eval_blocks(n_max), (unsigned)n_pairs);
+    if (wlds)
+        hipLaunchKernelGGL((ddpg_eval_many_kernel<EnvT, true>), grid, dim3(kSThreads), lds, s, d_items, d_cursors, K, zero_returns);
+    else
+        hipLaunchKernelGGL((ddpg_eval_many_kernel<EnvT, false>), grid, dim3(kSThreads), lds, s, d_items, d_cursors, K, zero_returns);
+    hipLaunchKernelGGL(ddpg_eval_merge_many_kernel, dim3((unsigned)n_pairs), dim3((kEStreams + 1) * 64), 0, s, d_items);
+    return check_launch("ssc_ddpg_eval_rollout_many");
+}
+
+// The checks of one (eval-env set, agent) -- the single call's, and through `who` an item's of the population call; `log`
+// is the single call's.  *carve: the pair's carve without the weight images.
+int eval_check(const char *who, const ssc_env_params *p, const ssc_actor_desc *actor, const ssc_critic_desc *critic, float act_low,
+               float act_high, int64_t n, int32_t K, int32_t k_min, const ssc_rollout_state *state, const ssc_transition_log *log,
+               const double *d_out, const void *d_workspace, size_t workspace_bytes, EvalCarve *carve) {
+    SSC_REQUIRE(d_out != nullptr, "%s: output block NULL", who);
+    SSC_REQUIRE(n >= 1 && n <= kEMaxEnvs && K >= k_min, "%s: n = %lld (1..2^30), K = %d (>= %d)", who, (long long)n, K, k_min);
+    SSC_REQUIRE(p->kind == SSC_ENV_MOUNTAINCAR || p->kind == SSC_ENV_PENDULUM, "%s: unknown env kind %d", who, p->kind);
+    const int od = p->kind == SSC_ENV_MOUNTAINCAR ? 2 : 3;
+    SSC_REQUIRE(actor->obs_dim == od && critic->obs_dim == od, "%s: actor obs_dim %d / critic obs_dim %d, the env observes %d values", who,
+                actor->obs_dim, critic->obs_dim, od);
+    SSC_REQUIRE(critic->act_dim == actor->act_dim, "%s: the critic's act_dim %d differs from the actor's %d", who, critic->act_dim,
+                actor->act_dim);
+    if (actor->act_dim != 1) return set_error(SSC_EUNSUPPORTED, "%s: act_dim %d (only 1)", who, actor->act_dim);
+    SSC_REQUIRE(actor->h1 >= 1 && actor->h2 >= 1 && critic->h1 >= 1 && critic->h2 >= 1, "%s: bad hidden sizes", who);
+    SSC_REQUIRE(act_low <= act_high, "%s: act_low > act_high", who);
+    SSC_REQUIRE(state->s0 && state->s1 && state->steps && state->ep_ret, "%s: NULL state column", who);
+    StatsNet net;
+    SSC_REQUIRE(fill_net(net, actor->W1, actor->b1, actor->W2, actor->b2, actor->W3, actor->b3, actor->ln1_g, actor->ln1_b,
+                         actor->ln2_g, actor->ln2_b, actor->h1, actor->h2, actor->last_layer_tanh, actor->obs_clip),
+                "%s: actor: NULL device pointer, or LayerNorm pointers that do not come together", who);
+    SSC_REQUIRE(fill_net(net, critic->W1, critic->b1, critic->W2, critic->b2, critic->W3, critic->b3, critic->ln1_g,
+                         critic->ln1_b, critic->ln2_g, critic->ln2_b, critic->h1, critic->h2, critic->last_layer_tanh,
+                         critic->obs_clip),
+                "%s: critic: NULL device pointer, or LayerNorm pointers that do not come together", who);
+    if (log != nullptr) {
+        for (int c = 0; c < od; ++c) SSC_REQUIRE(log->obs[c] && log->obs2[c], "%s: NULL log obs column %d", who, c);
+        SSC_REQUIRE(log->act && log->rew && log->done, "%s: NULL log column", who);
+        SSC_REQUIRE(log->row_stride >= 0 && log->done_row_stride >= 0, "%s: negative row stride", who);
+        SSC_REQUIRE((log->row_stride == 0 || log->row_stride >= n) && (log->done_row_stride == 0 || log->done_row_stride >= n),
+                    "%s: row stride < n", who);
+    }
+    const size_t need = ssc_ddpg_eval_workspace_bytes(n);
+    SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= need, "%s: workspace %zu < %zu bytes (ssc_ddpg_eval_workspace_bytes)", who,
+                workspace_bytes, need);
+    if (p->kind == SSC_ENV_MOUNTAINCAR)
+        if (int rc = validate_mc_params(p, who)) return rc;
+    *carve = eval_carve(od, actor->h1, actor->h2, actor->ln1_g != nullptr, critic->h1, critic->h2, critic->ln1_g != nullptr, false);
+    const size_t lds_act = (size_t)carve->act_floats * sizeof(float);
+    if (lds_act > kLdsBytes)
+        return set_error(SSC_EUNSUPPORTED, "%s: these layer sizes need %zu B of LDS per workgroup (160 KB available)", who, lds_act);
+    return SSC_OK;
+}
+
+// do both weight images fit beside the activations?
+bool weights_fit(const EvalCarve &c) { return (size_t)(c.act_floats + c.weight_floats) * sizeof(float) <= kLdsBytes; }
+
+// SSC_DDPG_EVAL_GLOBAL_WEIGHTS (any value, read per call): A/B switch for the tests and tools -- the weights stay in
+// global memory whatever their size
+bool global_weights_forced() { return getenv("SSC_DDPG_EVAL_GLOBAL_WEIGHTS") != nullptr; }
 
 }  // namespace
 
@@ -323,74 +494,72 @@ int ssc_ddpg_eval_rollout(const ssc_env_params *p, const ssc_actor_desc *actor, 
                           uint64_t seed, uint64_t env_id0, uint64_t step0, ssc_stream_t stream) {
     SSC_REQUIRE(p != nullptr && actor != nullptr && critic != nullptr && state != nullptr,
                 "ssc_ddpg_eval_rollout: NULL params / actor / critic / state");
-    SSC_REQUIRE(d_out != nullptr, "ssc_ddpg_eval_rollout: output block NULL");
-    SSC_REQUIRE(n >= 1 && n <= kEMaxEnvs && K >= 1, "ssc_ddpg_eval_rollout: n = %lld (1..2^30), K = %d (>= 1)", (long long)n, K);
-    SSC_REQUIRE(p->kind == SSC_ENV_MOUNTAINCAR || p->kind == SSC_ENV_PENDULUM, "ssc_ddpg_eval_rollout: unknown env kind %d", p->kind);
-    const int od = p->kind == SSC_ENV_MOUNTAINCAR ? 2 : 3;
-    SSC_REQUIRE(actor->obs_dim == od && critic->obs_dim == od,
-                "ssc_ddpg_eval_rollout: actor obs_dim %d / critic obs_dim %d, the env observes %d values", actor->obs_dim,
-                critic->obs_dim, od);
-    SSC_REQUIRE(critic->act_dim == actor->act_dim, "ssc_ddpg_eval_rollout: the critic's act_dim %d differs from the actor's %d",
-                critic->act_dim, actor->act_dim);
-    if (actor->act_dim != 1) return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_eval_rollout: act_dim %d (only 1)", actor->act_dim);
-    SSC_REQUIRE(actor->h1 >= 1 && actor->h2 >= 1 && critic->h1 >= 1 && critic->h2 >= 1, "ssc_ddpg_eval_rollout: bad hidden sizes");
-    SSC_REQUIRE(act_low <= act_high, "ssc_ddpg_eval_rollout: act_low > act_high");
-    SSC_REQUIRE(state->s0 && state->s1 && state->steps && state->ep_ret, "ssc_ddpg_eval_rollout: NULL state column");
+    EvalCarve carve;
+    if (int rc = eval_check("ssc_ddpg_eval_rollout", p, actor, critic, act_low, act_high, n, K, 1, state, log, d_out, d_workspace,
+                            workspace_bytes, &carve))
+        return rc;
+    const bool wlds = weights_fit(carve) && !global_weights_forced();
     EvalArgs a{};
-    SSC_REQUIRE(fill_net(a.actor, actor->W1, actor->b1, actor->W2, actor->b2, actor->W3, actor->b3, actor->ln1_g, actor->ln1_b,
-                         actor->ln2_g, actor->ln2_b, actor->h1, actor->h2, actor->last_layer_tanh, actor->obs_clip),
-                "ssc_ddpg_eval_rollout: actor: NULL device pointer, or LayerNorm pointers that do not come together");
-    SSC_REQUIRE(fill_net(a.critic, critic->W1, critic->b1, critic->W2, critic->b2, critic->W3, critic->b3, critic->ln1_g,
-                         critic->ln1_b, critic->ln2_g, critic->ln2_b, critic->h1, critic->h2, critic->last_layer_tanh,
-                         critic->obs_clip),
-                "ssc_ddpg_eval_rollout: critic: NULL device pointer, or LayerNorm pointers that do not come together");
-    a.n = n; a.K = K; a.st = *state; a.q = d_q; a.rms = d_rms; a.zero_returns = zero_returns != 0;
-    a.act_low = act_low; a.act_high = act_high; a.seed = seed; a.env_id0 = env_id0; a.step0 = step0;
+    pack_eval(a, *actor, *critic, act_low, act_high, n, K, *state, d_rms, zero_returns, static_cast<double *>(d_workspace), seed,
+              env_id0, step0, wlds);
+    a.q = d_q;
     a.has_log = log != nullptr;
     if (log != nullptr) {
         a.log = *log;
-        for (int c = 0; c < od; ++c)
-            SSC_REQUIRE(log->obs[c] && log->obs2[c], "ssc_ddpg_eval_rollout: NULL log obs column %d", c);
-        SSC_REQUIRE(log->act && log->rew && log->done, "ssc_ddpg_eval_rollout: NULL log column");
-        SSC_REQUIRE(log->row_stride >= 0 && log->done_row_stride >= 0, "ssc_ddpg_eval_rollout: negative row stride");
         if (a.log.row_stride == 0) a.log.row_stride = n;
         if (a.log.done_row_stride == 0) a.log.done_row_stride = n;
-        SSC_REQUIRE(a.log.row_stride >= n && a.log.done_row_stride >= n, "ssc_ddpg_eval_rollout: row stride < n");
     }
-    const size_t need = ssc_ddpg_eval_workspace_bytes(n);
-    SSC_REQUIRE(d_workspace != nullptr && workspace_bytes >= need,
-                "ssc_ddpg_eval_rollout: workspace %zu < %zu bytes (ssc_ddpg_eval_workspace_bytes)", workspace_bytes, need);
-    a.part = static_cast<double *>(d_workspace);
-    if (p->kind == SSC_ENV_MOUNTAINCAR)
-        if (int rc = validate_mc_params(p, "ssc_ddpg_eval_rollout")) return rc;
-    // ---- LDS carve: the partial records (f64, at offset 0), rows of 16 floats ([unit][env]), then the weight images ----
-    int64_t q = 0;
-    auto take = [&](int64_t floats) { const int64_t at = q; q += floats; return (int32_t)at; };
-    a.off_RED = take((int64_t)kSR * kEPart * 2);
-    a.off_XA = take((int64_t)od * kSR); a.off_XC = take((int64_t)od * kSR);
-    a.off_H1 = take((actor->h1 > (int64_t)critic->h1 + 1 ? actor->h1 : (int64_t)critic->h1 + 1) * kSR);
-    a.off_H2 = take((int64_t)(actor->h2 > critic->h2 ? actor->h2 : critic->h2) * kSR);
-    a.off_PI = take(kSR); a.off_Q = take(kSR);
-    const size_t lds_act = (size_t)q * sizeof(float);
-    if (lds_act > kLdsBytes)
-        return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_eval_rollout: these layer sizes need %zu B of LDS per workgroup (160 KB available)",
-                         lds_act);
-    const int64_t wa = net_floats(od, 0, actor->h1, actor->h2, 1, actor->ln1_g != nullptr);
-    const int64_t wc = net_floats(od, 1, critic->h1, critic->h2, 1, critic->ln1_g != nullptr);
-    // SSC_DDPG_EVAL_GLOBAL_WEIGHTS (any value, read per call): A/B switch for the tests and tools -- the weights stay in
-    // global memory whatever their size
-    const bool wlds = lds_act + (size_t)(wa + wc) * sizeof(float) <= kLdsBytes && getenv("SSC_DDPG_EVAL_GLOBAL_WEIGHTS") == nullptr;
-    if (wlds) {
-        a.off_AW = take(wa);
-        a.off_CW = take(wc);
-    }
-    const size_t lds = (size_t)q * sizeof(float);
+    const size_t lds = (size_t)a.lds.floats * sizeof(float);
     hipStream_t s = as_stream(stream);
     int rc = p->kind == SSC_ENV_MOUNTAINCAR ? launch_eval<McEnv>(make_mc_const(*p), a, wlds, lds, s)
                                             : launch_eval<PendEnv>(make_pend_const(*p), a, wlds, lds, s);
     if (rc) return rc;
     hipLaunchKernelGGL(ddpg_eval_merge_kernel, dim3(1), dim3((kEStreams + 1) * 64), 0, s, a.part, eval_blocks(n), d_out);
     return check_launch("ssc_ddpg_eval_rollout");
+}
+
+int ssc_ddpg_eval_rollout_many(const ssc_ddpg_eval_many_item *h_items, const ssc_ddpg_eval_many_item *d_items,
+                               const ssc_pair_cursor *h_cursors, const ssc_pair_cursor *d_cursors, int32_t n_pairs, int32_t K,
+                               int32_t zero_returns, ssc_stream_t stream) {
+    SSC_REQUIRE(n_pairs >= 1, "ssc_ddpg_eval_rollout_many: n_pairs %d < 1", n_pairs);
+    SSC_REQUIRE(h_items != nullptr && d_items != nullptr, "ssc_ddpg_eval_rollout_many: NULL item array");
+    SSC_REQUIRE(h_cursors != nullptr && d_cursors != nullptr, "ssc_ddpg_eval_rollout_many: NULL cursor array");
+    if (n_pairs > 65535) return set_error(SSC_EUNSUPPORTED, "ssc_ddpg_eval_rollout_many: %d pairs > 65535 (one grid row each)", n_pairs);
+    const int kind0 = h_items[0].params.kind;
+    bool wlds = !global_weights_forced();
+    int64_t n_max = 0, act_max = 0, all_max = 0;
+    std::vector<std::pair<const void *, int>> owned;   // (array, pair) of everything a pair's workgroups write
+    owned.reserve((size_t)n_pairs * 6);
+    for (int p = 0; p < n_pairs; ++p) {
+        const ssc_ddpg_eval_many_item &it = h_items[p];
+        char who[56];
+        snprintf(who, sizeof who, "ssc_ddpg_eval_rollout_many: pair %d", p);
+        EvalCarve carve;
+        if (int rc = eval_check(who, &it.params, &it.actor, &it.critic, it.act_low, it.act_high, it.n, K, 0, &it.state, nullptr, it.d_out,
+                                it.d_workspace, it.workspace_bytes, &carve))
+            return rc;
+        SSC_REQUIRE(it.params.kind == kind0, "%s: env kind %d differs from pair 0's %d (one kernel instantiation per launch)", who,
+                    it.params.kind, kind0);
+        wlds = wlds && weights_fit(carve);
+        n_max = std::max(n_max, it.n);
+        act_max = std::max(act_max, carve.act_floats);
+        all_max = std::max(all_max, carve.act_floats + carve.weight_floats);
+        for (const void *q : {(const void *)it.state.s0, (const void *)it.state.s1, (const void *)it.state.steps,
+                              (const void *)it.state.ep_ret, (const void *)it.d_out, (const void *)it.d_workspace})
+            owned.emplace_back(q, p);
+    }
+    // two pairs on one array would race without a sign of it; weights are only read and may be shared
+    std::sort(owned.begin(), owned.end());
+    for (size_t k = 1; k < owned.size(); ++k)
+        SSC_REQUIRE(owned[k].first != owned[k - 1].first || owned[k].second == owned[k - 1].second,
+                    "ssc_ddpg_eval_rollout_many: pairs %d and %d share a state column, an output block or a workspace",
+                    owned[k - 1].second, owned[k].second);
+    if (K == 0) return SSC_OK;
+    // the launch's dynamic LDS: the largest pair's carve (each workgroup carves for its own pair inside it)
+    const size_t lds = (size_t)(wlds ? all_max : act_max) * sizeof(float);
+    hipStream_t s = as_stream(stream);
+    if (kind0 == SSC_ENV_MOUNTAINCAR) return launch_eval_many<McEnv>(d_items, d_cursors, n_pairs, K, zero_returns, n_max, wlds, lds, s);
+    return launch_eval_many<PendEnv>(d_items, d_cursors, n_pairs, K, zero_returns, n_max, wlds, lds, s);
 }
 
 }  // extern "C"

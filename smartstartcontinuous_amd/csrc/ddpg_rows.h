@@ -11,18 +11,32 @@ constexpr int kSR = 16;                        // batch rows per workgroup
 constexpr int kSThreads = 256;
 constexpr int kSParts = kSThreads / kSR;       // threads per batch row
 
-struct StatsNet {
-    const float *W1, *b1, *W2, *b2, *W3, *b3;
-    const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;   // LayerNorm (models_editted.py:45-46, 50-51, 85-86, 91-92); null: none
+#define SSC_GLOBAL __attribute__((address_space(1)))
+
+// PTR: `const float *` (generic: global memory or an LDS image), or `const SSC_GLOBAL float *` for weights that are known
+// to sit in global memory but whose pointers were read out of a population item -- generic to the compiler, which would
+// load through them with FLAT instructions
+template <class PTR>
+struct StatsNetT {
+    PTR W1, b1, W2, b2, W3, b3;
+    PTR ln1_g, ln1_b, ln2_g, ln2_b;               // LayerNorm (models_editted.py:45-46, 50-51, 85-86, 91-92); null: none
     int32_t h1, h2, last_tanh;
     float obs_clip;
 };
+using StatsNet = StatsNetT<const float *>;
+using GlobalNet = StatsNetT<const SSC_GLOBAL float *>;
+
+__device__ __forceinline__ GlobalNet global_net(const StatsNet &g) {
+    using P = const SSC_GLOBAL float *;
+    return GlobalNet{(P)g.W1, (P)g.b1, (P)g.W2, (P)g.b2, (P)g.W3, (P)g.b3, (P)g.ln1_g, (P)g.ln1_b, (P)g.ln2_g, (P)g.ln2_b,
+                     g.h1, g.h2, g.last_tanh, g.obs_clip};
+}
 
 // One network for the workgroup's 16 rows (block-cooperative).  x [in_dim][16]; `extra` [n_extra][16] joins behind the
 // first activation (the critic's action, models_editted.py:89; n_extra = 0 for the actor); out [out_dim][16].
-// EXACT_TANH: the hidden tanh of critic_kernel is tanhf, the actor kernels' is tanh_fast.
-template <bool EXACT_TANH>
-static __device__ void net_rows(const StatsNet &n, const float *x, int in_dim, const float *extra, int n_extra, int out_dim,
+// EXACT_TANH: the hidden tanh of critic_kernel is tanhf, the actor kernels' is tanh_fast.  NET: StatsNet or GlobalNet.
+template <bool EXACT_TANH, class NET>
+static __device__ void net_rows(const NET &n, const float *x, int in_dim, const float *extra, int n_extra, int out_dim,
                                 bool out_tanh, float *h1s, float *h2s, float *out, int tid) {
     const int row = tid & (kSR - 1), part = tid >> 4;
     const bool ln = n.ln1_g != nullptr;
@@ -76,10 +90,11 @@ __device__ __forceinline__ Moments chan_merge(const Moments &x, const Moments &y
     return Moments{n, x.mean + delta * (y.n / n), x.m2 + y.m2 + delta * delta * (x.n * y.n / n)};
 }
 
-// false: a NULL device pointer, or LayerNorm pointers that do not come together
-static inline bool fill_net(StatsNet &n, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
-                            const float *b3, const float *g1, const float *be1, const float *g2, const float *be2, int h1, int h2,
-                            int last_tanh, float clip) {
+// false: a NULL device pointer, or LayerNorm pointers that do not come together.  Host and device: the single launches
+// fill their kernarg with it, a workgroup of the population launches fills the same struct from its pair's item.
+SSC_HD bool fill_net(StatsNet &n, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
+                     const float *b3, const float *g1, const float *be1, const float *g2, const float *be2, int h1, int h2,
+                     int last_tanh, float clip) {
     n = StatsNet{W1, b1, W2, b2, W3, b3, g1, be1, g2, be2, h1, h2, last_tanh, clip};
     const bool ln = g1 != nullptr;
     return W1 && b1 && W2 && b2 && W3 && b3 && ln == (be1 != nullptr) && ln == (g2 != nullptr) && ln == (be2 != nullptr);

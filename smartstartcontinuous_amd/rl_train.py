@@ -638,10 +638,56 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
 POPULATION_FUSED_CHUNK = True
 
 
+class PopulationMonitor:
+    """What :func:`rl_train_vec_ddpg_population` logs beside the training of its P pairs -- the two things a sweep's agents
+    are compared by -- with the meaning the keywords of the same names have in :func:`rl_train_vec_ddpg`, for all pairs at
+    once: ``stats_every=k`` logs the training diagnostics, ``eval_envs`` + ``eval_every=k`` the evaluation block
+    (``eval_steps`` steps of every eval env; default: the eval envs' ``spec.max_episode_steps`` or 1000).  ``eval_envs``: one
+    VecEnv per pair, each an env of its own -- not a training env, none used twice -- with the spaces of its pair's training
+    env."""
+
+    def __init__(self, eval_envs=None, eval_every=None, eval_steps=None, stats_every=None):
+        self.eval_envs = None if eval_envs is None else list(eval_envs)
+        self.eval_every, self.eval_steps, self.stats_every = eval_every, eval_steps, stats_every
+
+    def checked(self, envs):
+        """(eval_envs, eval_every, eval_steps, stats_every) validated against the training envs as the single loop validates
+        its keywords; ValueError otherwise."""
+        stats_every, eval_envs, eval_every, eval_steps = self.stats_every, self.eval_envs, self.eval_every, self.eval_steps
+        if stats_every is not None and (int(stats_every) != stats_every or stats_every < 1):
+            raise ValueError("stats_every must be None or a positive integer")
+        if (eval_envs is None) != (eval_every is None):
+            raise ValueError("eval_envs and eval_every come together")
+        if eval_envs is None:
+            if eval_steps is not None:
+                raise ValueError("eval_steps needs eval_envs and eval_every")
+            return None, None, None, None if stats_every is None else int(stats_every)
+        if len(eval_envs) != len(envs):
+            raise ValueError("eval_envs: one eval env per pair")
+        if any(e is t for e in eval_envs for t in envs):
+            raise ValueError("eval_envs must be envs of their own, not training envs")
+        if len({id(e) for e in eval_envs}) != len(eval_envs):
+            raise ValueError("eval_envs: no eval env may serve two pairs")
+        for p, (ev, env) in enumerate(zip(eval_envs, envs)):
+            for what in ("observation_space", "action_space"):
+                ea, eb = getattr(ev, what), getattr(env, what)
+                if tuple(ea.shape) != tuple(eb.shape) or not (np.array_equal(ea.low, eb.low) and np.array_equal(ea.high, eb.high)):
+                    raise ValueError(f"pair {p}: eval env's {what} differs from the training env's")
+        if eval_steps is None:
+            steps = {getattr(getattr(ev, "spec", None), "max_episode_steps", None) or 1000 for ev in eval_envs}
+            if len(steps) != 1:
+                raise ValueError("the eval envs' episode limits differ: give eval_steps (one value for the population)")
+            eval_steps = steps.pop()
+        for name, v in (("eval_every", eval_every), ("eval_steps", eval_steps)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be a positive integer")
+        return eval_envs, int(eval_every), int(eval_steps), None if stats_every is None else int(stats_every)
+
+
 def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
                                  replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
                                  drain_every=None, on_chunk=None, stats_every=None, eval_env=None, eval_every=None,
-                                 eval_steps=None):
+                                 eval_steps=None, monitor=None):
     """The synchronous :func:`rl_train_vec_ddpg` for P (env, agent) pairs -- seeds x hyper-parameter grids, the reference's
     experimenter.py fan-out -- with ONE learner launch per chunk for the whole population
     (:class:`agents.DDPGPopulation`): per chunk every pair rolls out, decays its epsilon, appends to its own replay ring
@@ -655,19 +701,34 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
     the per-pair calls for a population it does not serve (mixed env kinds, another actor shape or precision, mixed
     statistics, shared arrays).
 
-    Not in this form: ``overlap``, agents with parameter-space noise, ``stats_every`` and ``eval_env``
-    (NotImplementedError).  ``on_chunk(i, chunks, envs)`` gets the lists.  Returns [(Summary, losses per chunk, replay)]
-    per pair."""
+    ``monitor``: a :class:`PopulationMonitor` -- diagnostics and evaluation for all pairs, each ONE call of
+    ``population.get_stats_device`` / ``population.evaluate_device`` (two launches for the whole population) behind the
+    learner launch of every chunk i with (i + 1) % k == 0, into DEVICE logs [ceil(num_chunks / k), P, .] pre-filled with
+    NaN; no host read inside the loop.  A pair whose replay ring holds fewer than ``batch_size`` records and has no sample yet
+    keeps a NaN diagnostics row.  When the loop ends every pair's Summary gets ``agent_stats``, ``agent_stats_chunks``,
+    ``eval_stats`` and ``eval_chunks`` (and ``ret_rms`` for a Pop-Art agent) exactly as :func:`rl_train_vec_ddpg` fills them
+    for ``stats_every=`` / ``eval_env=`` / ``eval_every=`` / ``eval_steps=``, bit for bit; everything else the loop computes
+    is bit-identical to the run without a monitor.
+
+    Not in this form: ``overlap`` and agents with parameter-space noise (NotImplementedError).  The single loop's keywords
+    ``stats_every`` and ``eval_env`` / ``eval_every`` / ``eval_steps`` take one value, not one per pair: they raise
+    NotImplementedError too and point to ``monitor``.  ``on_chunk(i, chunks, envs)`` gets the lists.  Returns
+    [(Summary, losses per chunk, replay)] per pair."""
     from .agents import DDPGPopulation
     envs, agents = list(envs), list(agents)
     if len(envs) != len(agents) or not agents:
         raise ValueError("one env per agent, at least one pair")
-    for what, on in (("overlap=True", overlap), ("stats_every", stats_every is not None),
-                     ("eval_env / eval_every / eval_steps", not (eval_env is None and eval_every is None and eval_steps is None)),
+    for what, on in (("stats_every", stats_every is not None),
+                     ("eval_env / eval_every / eval_steps", not (eval_env is None and eval_every is None and eval_steps is None))):
+        if on:
+            raise NotImplementedError(f"rl_train_vec_ddpg_population: {what} is a keyword of the single loop; the population loop "
+                                      "takes monitor=PopulationMonitor(eval_envs=, eval_every=, eval_steps=, stats_every=)")
+    for what, on in (("overlap=True", overlap),
                      ("an agent with parameter-space noise", any(getattr(a, "param_noise", None) is not None for a in agents))):
         if on:
             raise NotImplementedError(f"rl_train_vec_ddpg_population: {what} is not part of the population loop; "
                                       "run that pair through rl_train_vec_ddpg")
+    eval_envs, eval_every, eval_steps, stats_every = (monitor if monitor is not None else PopulationMonitor()).checked(envs)
     P = len(agents)
     seeds = [int(seed)] * P if isinstance(seed, (int, np.integer)) else [int(s) for s in seed]
     if len(seeds) != P:
@@ -698,6 +759,32 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
     rms_group = ObsRmsGroup([agents[p].obs_rms for p in normed]) if normed else None
     cursors = PairCursors(P, envs[0].device) if POPULATION_FUSED_CHUNK and all(e.device == envs[0].device for e in envs) else None
     scales = [a.reward_scale for a in agents]
+    # the monitor's device logs [rows, P, .]: each call writes ONE block [P, .] the population keeps its descriptors over,
+    # copied into its row on the stream (NaN where a pair has no sample yet)
+    import torch
+    from ._ffi import SSC_DDPG_N_EVAL, SSC_DDPG_N_STATS
+    dev = envs[0].device
+    nan_log = lambda every, cols: (torch.full((-(-num_chunks // every), P, cols), float("nan"), dtype=torch.float64, device=dev),
+                                   torch.full((P, cols), float("nan"), dtype=torch.float64, device=dev))
+    stats_log, stats_block = nan_log(stats_every, SSC_DDPG_N_STATS) if stats_every is not None else (None, None)
+    eval_log, eval_block = nan_log(eval_every, SSC_DDPG_N_EVAL) if eval_envs is not None else (None, None)
+    popart = [p for p, a in enumerate(agents) if getattr(a, "ret_rms", None) is not None] if stats_log is not None else []
+    ret_log = torch.full((stats_log.shape[0], P, 2), float("nan"), dtype=torch.float32, device=dev) if popart else None
+
+    def log_monitor(i):
+        """the diagnostics and the evaluation behind chunk i, enqueued behind its learner launch"""
+        if stats_log is not None and (i + 1) % stats_every == 0:
+            population.get_stats_device(replays, out=stats_block)
+            stats_log[i // stats_every].copy_(stats_block)
+            for p in popart:
+                if getattr(agents[p], "stats_sample", None) is not None:
+                    mean, std = agents[p].ret_rms.mean_std_device()
+                    ret_log[i // stats_every, p, 0:1].copy_(mean)
+                    ret_log[i // stats_every, p, 1:2].copy_(std)
+        if eval_log is not None and (i + 1) % eval_every == 0:
+            population.evaluate_device(eval_envs, eval_steps, out=eval_block)
+            eval_log[i // eval_every].copy_(eval_block)
+
     for i in range(num_chunks):
         if cursors is None:                       # the per-pair calls, pair by pair
             for p, (env, agent) in enumerate(zip(envs, agents)):
@@ -717,16 +804,26 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
         for p, l in enumerate(population.train_from(replays, train_iters, copy=True)):
             if l is not None:
                 losses[p].append(l)
+        log_monitor(i)
         if on_chunk is not None:
             on_chunk(i, chunks, envs)
         for p in range(P):
             if (i + 1) % every[p] == 0:
                 drain(p)
+    stats_host, ret_host, eval_host = (None if log is None else log.cpu().numpy() for log in (stats_log, ret_log, eval_log))
     for p, agent in enumerate(agents):
         drain(p)
         summaries[p].dropped_episode_records = dropped[p]
         _g, (eps,) = schedules[p].read()
         agent.decaying_ou_action_noise.epsilon = eps
+        if stats_host is not None:
+            summaries[p].agent_stats = {name: stats_host[:, p, j].copy() for j, name in enumerate(agent.STATS_NAMES)}
+            summaries[p].agent_stats_chunks = [(r + 1) * stats_every - 1 for r in range(stats_host.shape[0])]
+        if ret_host is not None and p in popart:
+            summaries[p].ret_rms = {"mean": ret_host[:, p, 0].copy(), "std": ret_host[:, p, 1].copy()}
+        if eval_host is not None:
+            summaries[p].eval_stats = {name: eval_host[:, p, j].copy() for j, name in enumerate(agent.EVAL_NAMES)}
+            summaries[p].eval_chunks = [(r + 1) * eval_every - 1 for r in range(eval_host.shape[0])]
     return [(summaries[p], losses[p], replays[p]) for p in range(P)]
 
 
