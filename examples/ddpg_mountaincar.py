@@ -45,8 +45,9 @@ def main():
     ap.add_argument("--save-dir", default=None)
     ap.add_argument("--normalize-observations", action="store_true",
                     help="DDPG normalize_observations: networks see running-statistics-normalised observations")
-    ap.add_argument("--param-noise", type=float, default=None, metavar="STDDEV",
-                    help="adaptive parameter-space noise with this initial (and desired action) stddev, on top of the OU noise")
+    ap.add_argument("--param-noise", default=None, metavar="STDDEV[,STDDEV...]",
+                    help="adaptive parameter-space noise with this initial (and desired action) stddev, on top of the OU noise; "
+                         "with --population a comma list sweeps it: pair p takes entry p modulo the list's length")
     ap.add_argument("--popart", action="store_true",
                     help="DDPG normalize_returns + enable_popart: the critic learns normalised returns, its output layer is "
                          "rescaled with the running return statistics (Pop-Art)")
@@ -59,6 +60,15 @@ def main():
     ap.add_argument("--eval-envs", type=int, default=128, metavar="E", help="vec: evaluation envs")
     ap.add_argument("--eval-steps", type=int, default=None, metavar="S", help="vec: steps per evaluation (default: the time limit)")
     args = ap.parse_args()
+    stddevs = None
+    if args.param_noise is not None:
+        try:
+            stddevs = [float(x) for x in args.param_noise.split(",")]
+        except ValueError:
+            ap.error("--param-noise takes a number or a comma list of numbers")
+        if len(stddevs) > 1 and args.population is None:
+            ap.error("a list of --param-noise values needs --population")
+        args.param_noise = stddevs[0]
     np.random.seed(args.seed)
     if args.mode == "single":
         env = ssc.Continuous_MountainCarEnv_Editted.make_timed_env(args.power_scalar, max_episode_steps=1000,
@@ -78,14 +88,15 @@ def main():
                 if (episode + 1) % args.stats_every == 0 and len(agent.replay_buffer) >= agent.batch_size:
                     print("  stats:", ", ".join("%s %.6g" % kv for kv in agent.get_stats().items()))
     elif args.population is not None:
-        if args.param_noise is not None or args.overlap:
-            ap.error("--population runs the synchronous loop without parameter noise")
+        if args.overlap:
+            ap.error("--population runs the synchronous loop")
         env_id = "MountainCarContinuousActionX%s-v0" % args.power_scalar
         P = args.population
         seeds = [args.seed + p for p in range(P)]
         envs = [ssc.VecEnv(env_id, args.envs, seed=s, env_id0=p * args.envs) for p, s in enumerate(seeds)]
-        agents = [make_agent(ssc.SingleEnvView(ssc.VecEnv(env_id, 1, seed=s)), s, args.normalize_observations, None, args.popart)
-                  for s in seeds]
+        noise = [None if stddevs is None else stddevs[p % len(stddevs)] for p in range(P)]
+        agents = [make_agent(ssc.SingleEnvView(ssc.VecEnv(env_id, 1, seed=s)), s, args.normalize_observations, sd, args.popart)
+                  for s, sd in zip(seeds, noise)]
         eval_envs = None
         if args.eval_every is not None:        # envs of their own per pair: another seed, ids behind all training envs'
             eval_envs = [ssc.VecEnv(env_id, args.eval_envs, seed=s + P, env_id0=P * args.envs + p * args.eval_envs)
@@ -93,9 +104,10 @@ def main():
         monitor = ssc.PopulationMonitor(eval_envs=eval_envs, eval_every=args.eval_every, eval_steps=args.eval_steps,
                                         stats_every=args.stats_every)
         runs = ssc.rl_train_vec_ddpg_population(envs, agents, num_chunks=args.chunks, chunk_steps=250, replay_capacity=1 << 20,
-                                                train_iters=50, seed=seeds, monitor=monitor)
+                                                train_iters=50, seed=seeds, monitor=monitor,
+                                                param_noise_cycle=stddevs is not None)
         last = lambda log, k: next((v for v in log[k][::-1] if not np.isnan(v)), float("nan"))   # the last row that was written
-        for s, (summary, losses, replay) in zip(seeds, runs):   # one line per pair
+        for s, agent, (summary, losses, replay) in zip(seeds, agents, runs):   # one line per pair
             late = [ret for _steps, ret in summary.episodes[-max(1, len(summary) // 4):]]
             line = ("seed %d: %d finished episodes, late-window return %.2f (last quarter of them), last critic/actor loss %.4g / %.4g"
                     % (s, len(summary), float(np.mean(late)) if late else float("nan"), *losses[-1][-1].tolist()))
@@ -105,6 +117,8 @@ def main():
             if args.stats_every is not None:
                 line += ", reference_Q_mean %.4g reference_action_std %.4g" % (
                     last(summary.agent_stats, "reference_Q_mean"), last(summary.agent_stats, "reference_action_std"))
+            if agent.param_noise is not None:
+                line += ", param_noise_stddev %.4g -> %.4g" % (agent.param_noise.initial_stddev, agent.param_noise.current_stddev)
             print(line)
         if args.save_dir:
             os.makedirs(args.save_dir, exist_ok=True)

@@ -847,6 +847,59 @@ int ssc_param_noise_cycle(const ssc_actor_desc *actor, int64_t m, const float *d
                           uint64_t seed, uint64_t generation_adaptive, uint64_t generation_acting, float desired,
                           float coefficient, float *d_stddev, float *d_distance, float *d_dst, ssc_stream_t stream);
 
+/* What one ssc_param_noise_cycle call takes, minus the generations and m (the pair's ssc_param_noise_cursor), with the batch
+ * given as row indices into the replay ring's state column.  Declared tag first like the other *_many items;
+ * tests/test_param_noise_many_host.py holds both structs' sizes and offsets to the ctypes mirrors. */
+struct ssc_param_noise_many_item {
+    ssc_actor_desc actor;            /* the PLAIN actor; pointers inside d_src[0..n) */
+    const float   *d_obs;            /* the ring's state column base, [rows][obs_dim] */
+    const int32_t *d_idx;            /* [m] row indices into d_obs, or NULL: rows 0..m-1 (d_obs holds the batch itself) */
+    const double  *d_rms;            /* or NULL, per pair */
+    int64_t        n;                /* 0: the pair is skipped */
+    const float   *d_src;
+    int64_t        skip0_begin, skip0_end, skip1_begin, skip1_end;
+    uint64_t       seed;
+    float          desired, coefficient;
+    float         *d_stddev, *d_distance, *d_dst;
+};
+typedef struct ssc_param_noise_many_item ssc_param_noise_many_item;
+
+/* What changes with every adaption interval, 24 bytes per pair: the one upload of a steady-state call. */
+struct ssc_param_noise_cursor {
+    uint64_t generation_adaptive, generation_acting;
+    int32_t  m;                      /* 1..4096 batch rows, or 0: perturb only */
+    int32_t  pad;
+};
+typedef struct ssc_param_noise_cursor ssc_param_noise_cursor;
+
+/* ssc_param_noise_cycle for n_pairs agents in ONE launch: workgroup p runs pair p's whole adaption
+ * interval exactly as the pair's own launch would -- workgroups share nothing, there are no atomics -- so d_dst, *d_stddev
+ * and *d_distance hold, bit for bit, what
+ *     ssc_param_noise_cycle(&actor, m, <rows d_idx[0..m) of d_obs>, d_rms, n, d_src, skips, seed, generation_adaptive,
+ *                           generation_acting, desired, coefficient, d_stddev, d_distance, d_dst)
+ * leaves.  Row r of the batch is d_obs[d_idx[r] * obs_dim + c]: the gather out of the replay ring happens inside the kernel
+ * (d_idx == NULL: row r itself).  The caller keeps every d_idx[r] inside the rows of d_obs.
+ * m == 0 (the ring holds no batch yet) is the perturb-only interval: d_dst = d_src + *d_stddev * g(generation_acting) with
+ * the stddev as it stands -- the bits of ssc_param_noise_perturb(n, d_src, d_dst, d_stddev, skips, seed,
+ * generation_acting); *d_stddev and *d_distance are not written, d_obs / d_idx / d_rms not read, generation_adaptive unused.
+ * The conventions are ssc_rollout_many's: host arrays (items and cursors) that are validated before any HIP call, the
+ * caller's device copies of the same bytes, complete on `stream` before the call; the library copies nothing; the pair's
+ * index -- or both indices -- is in ssc_last_error().
+ * Per pair, read at run time: layer sizes (64-32, 128-64 and 200-100 agents may share a launch), LayerNorm, last_layer_tanh,
+ * obs_clip, d_rms (set or NULL), obs_dim, m, seed, desired, coefficient.  Uniform per launch: the plain parameters are
+ * staged in LDS beside the adaptive copy iff EVERY pair with m > 0 fits both copies beside a 128-row tile (the bits do not
+ * depend on it: a pair's tile, and with it every summation order, is the same either way); the dynamic LDS size is the
+ * largest pair's.
+ * Every pair with n > 0 passes ssc_param_noise_cycle's checks with its error codes (m may be 0 as well; SSC_EUNSUPPORTED
+ * with the byte count and the pair when the adaptive copy and a 4-row tile exceed LDS, whatever m is).  Across pairs,
+ * SSC_EINVAL naming both: no two d_dst ranges [d_dst, d_dst + n) overlap, no d_dst range overlaps any pair's d_src range
+ * (its own included), no two pairs share d_stddev or d_distance.  d_src, d_obs, d_idx and d_rms are only read and may be
+ * shared.  n_pairs 1..65535 (more: SSC_EUNSUPPORTED).  A pair with n == 0 is skipped, nothing else of its item is read; all
+ * n == 0: SSC_OK without a launch. */
+int ssc_param_noise_cycle_many(const ssc_param_noise_many_item *h_items, const ssc_param_noise_many_item *d_items,
+                               const ssc_param_noise_cursor *h_cursors, const ssc_param_noise_cursor *d_cursors,
+                               int32_t n_pairs, ssc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Training diagnostics (ddpg_editted.py:219-253 setup_stats, 341-358 get_stats; printed per epoch by
  * training_editted.py:144)

@@ -191,6 +191,17 @@ class DdpgStatsManyItem(Structure):
                 ("d_out", c_void_p), ("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
+class ParamNoiseManyItem(Structure):
+    _fields_ = [("actor", ActorDesc), ("d_obs", c_void_p), ("d_idx", c_void_p), ("d_rms", c_void_p), ("n", c_int64),
+                ("d_src", c_void_p), ("skip0_begin", c_int64), ("skip0_end", c_int64), ("skip1_begin", c_int64),
+                ("skip1_end", c_int64), ("seed", c_uint64), ("desired", c_float), ("coefficient", c_float),
+                ("d_stddev", c_void_p), ("d_distance", c_void_p), ("d_dst", c_void_p)]
+
+
+class ParamNoiseCursor(Structure):
+    _fields_ = [("generation_adaptive", c_uint64), ("generation_acting", c_uint64), ("m", c_int32), ("pad", c_int32)]
+
+
 # C struct -> its ctypes mirror: the struct-layout table (the tests compare sizeof / offsetof as the C compiler sees them)
 STRUCTS = {
     "ssc_env_params": EnvParams, "ssc_actor_desc": ActorDesc, "ssc_ou_desc": OuDesc, "ssc_policy_desc": PolicyDesc,
@@ -201,7 +212,8 @@ STRUCTS = {
     "ssc_mlp_train_desc": MlpTrainDesc, "ssc_ddpg_many_item": DdpgManyItem, "ssc_replay_sample_key": ReplaySampleKey,
     "ssc_pair_cursor": PairCursor, "ssc_rollout_many_item": RolloutManyItem, "ssc_replay_append_item": ReplayAppendItem,
     "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem, "ssc_ddpg_eval_many_item": DdpgEvalManyItem,
-    "ssc_ddpg_stats_many_item": DdpgStatsManyItem,
+    "ssc_ddpg_stats_many_item": DdpgStatsManyItem, "ssc_param_noise_many_item": ParamNoiseManyItem,
+    "ssc_param_noise_cursor": ParamNoiseCursor,
 }
 
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
@@ -276,6 +288,8 @@ _SIGNATURES = {
     "ssc_param_noise_cycle": (c_int, [POINTER(ActorDesc), c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
                                       c_int64, c_int64, c_uint64, c_uint64, c_uint64, c_float, c_float, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    # ... for a whole population in one launch: host items / cursors (validated) + the caller's device copies
+    "ssc_param_noise_cycle_many": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     # training diagnostics (get_stats): one f64 block per call
     "ssc_ddpg_stats_workspace_bytes": (c_size_t, [c_int64]),
     "ssc_ddpg_stats": (c_int, [POINTER(ActorDesc), POINTER(CriticDesc), POINTER(ActorDesc), c_int64, c_void_p, c_void_p, c_void_p,

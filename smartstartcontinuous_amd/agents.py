@@ -811,6 +811,11 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
         return losses
 
 
+# DDPGPopulation.param_noise_cycle: one launch for all noisy agents (True), or its own fallback -- the per-agent
+# adapt_and_perturb(cycle=True) calls (False: the yardstick of tools/exp_ddpg_population_param_noise.py).
+POPULATION_FUSED_PARAM_NOISE = True
+
+
 class DDPGPopulation:
     """P independent :class:`DDPG_Baselines_agent` objects -- seeds x hyper-parameter grids, what the reference fans out
     over processes (experimenter.py) -- trained by ONE learner launch, one workgroup per agent (``ssc_ddpg_train_many``),
@@ -828,7 +833,8 @@ class DDPGPopulation:
     (``copy=True`` returns views of a fresh copy instead).
 
     What the agents of a sweep are compared by comes in one launch per phase too: :meth:`evaluate_device` (eval/return,
-    eval/Q) and :meth:`get_stats_device` (the ``get_stats`` diagnostics), for any mix of network shapes."""
+    eval/Q) and :meth:`get_stats_device` (the ``get_stats`` diagnostics), for any mix of network shapes -- and so does the
+    adaption interval of the agents with parameter-space noise: :meth:`param_noise_cycle`."""
 
     B = 64
 
@@ -1140,6 +1146,121 @@ class DDPGPopulation:
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.ssc_ddpg_stats_many(self._stats_items.h_ptr, self._stats_items.d_ptr, P, _ffi.stream()))
         return out
+
+    # ---- parameter-space noise: the adaption interval of every noisy agent in one launch ---------------------------
+    # ``ssc_param_noise_cycle_many``: workgroup j runs noisy agent j exactly as ``agent.param_noise_cycle`` (or, while its ring
+    # holds no batch, ``agent.perturb_policy``) would; the batch is gathered out of the ring inside the kernel, from indices
+    # that ONE ``ssc_replay_sample_many`` draws for all rings.  Any mix of shapes, LayerNorm and normalize_observations.
+    pn_fused = None
+    _pn_sig = None
+
+    def param_noise_plan(self, replays):
+        """The host half of :meth:`param_noise_cycle`, moving nothing: per agent with parameter noise its index ``p``, the
+        interval (``m`` = batch_size when its ring holds a batch, else 0: perturb only), the generations the interval draws
+        and the key (seed, counter0, size) of the ONE index batch ``replay.sample_indices(1, batch_size)`` would draw."""
+        plan = []
+        for p, (a, r) in enumerate(zip(self.agents, replays)):
+            if a.param_noise is None:
+                continue
+            g = int(a.param_noise_generation)
+            if len(r) >= a.batch_size:
+                plan.append(dict(p=p, m=int(a.batch_size), generation_adaptive=g, generation_acting=g + 1,
+                                 key=(int(r.seed), int(r._batches_drawn), len(r))))
+            else:
+                plan.append(dict(p=p, m=0, generation_adaptive=g, generation_acting=g, key=None))
+        return plan
+
+    def param_noise_commit(self, plan, replays):
+        """What the planned intervals consume, once they are enqueued: two generations and one batch of the ring's index
+        stream where the stddev is adapted, one generation where not; ``perturbed_generation`` is the acting one."""
+        for e in plan:
+            a = self.agents[e["p"]]
+            a.perturbed_generation = e["generation_acting"]
+            a.param_noise_generation = e["generation_acting"] + 1
+            if e["key"] is not None:
+                replays[e["p"]]._batches_drawn += 1
+
+    def param_noise_cycle(self, replays, dsts=None):
+        """``rl_train.adapt_and_perturb(agent, replay, dst, cycle=True)`` for every agent that has ``param_noise`` (the others
+        are not in the launch): the stddev adapted on the obs0 of ONE fresh batch of the agent's ring, then ``dsts[p]``
+        (default ``agent.perturbed_actor_flat``) = actor + noise of the adapted stddev; only the perturbation while the ring
+        holds fewer than ``batch_size`` records.  Generations, ``perturbed_generation`` and every ring's index stream move
+        exactly as there, and every array holds the same bits.  One sampling launch and one cycle launch for the whole
+        population; in steady state a call uploads the sampling keys and the cursors (24 bytes per agent) and nothing
+        else.  A population the launch does not serve -- a ``batch_size`` above 64 or not the same for all noisy agents (the
+        one-wave sampler), agents on different devices, an agent without ``param_noise_cycle``, a refusal by the library's
+        own validation -- runs the per-agent calls; ``pn_fused`` tells which way the last call went.  Stream-ordered, no
+        host read."""
+        from .population import DeviceItems, served
+        from .rl_train import adapt_and_perturb
+        ag, P = self.agents, len(self.agents)
+        replays = list(replays)
+        dsts = [None] * P if dsts is None else list(dsts)
+        if len(replays) != P or len(dsts) != P:
+            raise ValueError("one replay ring (and one dst or None) per agent")
+        plan = self.param_noise_plan(replays)
+        if not plan:
+            return
+        noisy = [e["p"] for e in plan]
+        out = [ag[p].perturbed_actor_flat if dsts[p] is None else dsts[p] for p in noisy]
+        for p, d in zip(noisy, out):
+            if d.dtype != torch.float32 or d.numel() != ag[p].actor_flat.numel() or not d.is_contiguous():
+                raise ValueError("dst must be a contiguous fp32 array of the size of actor_flat")
+        active = tuple(j for j, e in enumerate(plan) if e["m"] > 0)
+        rms = [ag[p]._rms_block() for p in noisy]
+        sig = (POPULATION_FUSED_PARAM_NOISE, torch.cuda.current_stream(self.device).cuda_stream, active,
+               tuple((bytes(a._desc), a.actor_flat.data_ptr(), a.actor_flat.numel(), d.data_ptr(), r.s.data_ptr(), r.s.shape[0],
+                      None if b is None else b.data_ptr(), tuple(a._pn_skip), a.param_noise_seed,
+                      a.param_noise.desired_action_stddev, a.param_noise.adoption_coefficient, a.d_param_noise_stddev.data_ptr(),
+                      a.d_param_noise_distance.data_ptr(), a.batch_size, str(a.actor_flat.device), str(r.s.device))
+                     for a, d, r, b in zip((ag[p] for p in noisy), out, (replays[p] for p in noisy), rms)))
+        if sig != self._pn_sig:
+            self._pn_sig, self._pn = sig, None
+            B = ag[noisy[0]].batch_size
+            self.pn_fused = (POPULATION_FUSED_PARAM_NOISE and B <= 64 and all(ag[p].batch_size == B for p in noisy)
+                             and all(hasattr(ag[p], "param_noise_cycle") for p in noisy)
+                             and all(ag[p].actor_flat.device == ag[noisy[0]].actor_flat.device == replays[p].s.device for p in noisy))
+            if self.pn_fused:
+                n = len(noisy)
+                with torch.cuda.device(self.device):
+                    st = dict(B=B, items=DeviceItems(_ffi.ParamNoiseManyItem, n, self.device),
+                              cursors=DeviceItems(_ffi.ParamNoiseCursor, n, self.device),
+                              keys=DeviceItems(_ffi.ReplaySampleKey, max(len(active), 1), self.device),
+                              idx=torch.zeros((max(len(active), 1), 1, B), dtype=torch.int32, device=self.device))
+                    for j, (it, p, d) in enumerate(zip(st["items"].items, noisy, out)):
+                        a, r = ag[p], replays[p]
+                        it.actor, it.d_obs = a._desc, r.s.data_ptr()
+                        it.d_idx = st["idx"][active.index(j)].data_ptr() if j in active else None
+                        it.d_rms = None if rms[j] is None else rms[j].data_ptr()
+                        it.n, it.d_src = a.actor_flat.numel(), a.actor_flat.data_ptr()
+                        it.skip0_begin, it.skip0_end, it.skip1_begin, it.skip1_end = a._pn_skip
+                        it.seed, it.desired, it.coefficient = a.param_noise_seed, a.param_noise.desired_action_stddev, a.param_noise.adoption_coefficient
+                        it.d_stddev, it.d_distance = a.d_param_noise_stddev.data_ptr(), a.d_param_noise_distance.data_ptr()
+                        it.d_dst = d.data_ptr()
+                    st["items"].upload()
+                self._pn = st
+        if self.pn_fused:
+            st = self._pn
+            st["cursors"].wait()
+            for c, e in zip(st["cursors"].items, plan):
+                c.generation_adaptive, c.generation_acting, c.m = e["generation_adaptive"], e["generation_acting"], e["m"]
+            st["cursors"].upload()
+            with torch.cuda.device(self.device):
+                if active:
+                    st["keys"].wait()
+                    for k, j in zip(st["keys"].items, active):
+                        k.seed, k.counter0, k.size = plan[j]["key"]
+                    st["keys"].upload()
+                    _ffi.check(self.lib.ssc_replay_sample_many(st["keys"].h_ptr, st["keys"].d_ptr, len(active), 1, st["B"],
+                                                               _ffi.ptr(st["idx"]), _ffi.stream(self.device)))
+                # the library's own rules decide: validation precedes every HIP call, so a refusal has launched nothing
+                self.pn_fused = served(self.lib.ssc_param_noise_cycle_many(st["items"].h_ptr, st["items"].d_ptr, st["cursors"].h_ptr,
+                                                                           st["cursors"].d_ptr, len(noisy), _ffi.stream(self.device)))
+            if self.pn_fused:
+                self.param_noise_commit(plan, replays)
+                return
+        for p in noisy:
+            adapt_and_perturb(ag[p], replays[p], dst=dsts[p], cycle=True)
 
     def get_stats(self, replays=None):
         """:meth:`get_stats_device` as a list of dicts, one per agent, each what ``agent.get_stats`` returns (an agent

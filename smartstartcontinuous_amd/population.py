@@ -1,5 +1,6 @@
 """Launch descriptors of the population entry points (``ssc_rollout_many``, ``ssc_replay_append_many``,
-``ssc_decay_schedule_many``, ``ssc_obs_rms_update_many``).
+``ssc_decay_schedule_many``, ``ssc_obs_rms_update_many``, ``ssc_ddpg_eval_rollout_many``, ``ssc_ddpg_stats_many``,
+``ssc_param_noise_cycle_many``).
 
 Each of those calls takes a host array that the library validates and the caller's device copy of the same bytes.
 ``DeviceItems`` is that pair for one ctypes struct; ``PairCursors`` is the small per-chunk array (``ssc_pair_cursor``:

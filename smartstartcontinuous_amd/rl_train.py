@@ -375,7 +375,8 @@ def adapt_and_perturb(agent, replay, dst=None, cycle=True):
 
 def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
                       replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
-                      drain_every=None, on_chunk=None, stats_every=None, eval_env=None, eval_every=None, eval_steps=None):
+                      drain_every=None, on_chunk=None, stats_every=None, eval_env=None, eval_every=None, eval_steps=None,
+                      param_noise_cycle=False):
     """Actor-learner loop entirely in HBM: every chunk is a fused rollout of ``chunk_steps`` steps of all
     ``env.n`` envs under the agent's current actor (+ OU noise), appended to a device replay ring, followed
     by ``train_iters`` DDPG iterations (default ``agent.num_train_iterations``) on batches drawn from it.
@@ -405,6 +406,10 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
     adapted stddev -- both stream-ordered, no host read.  The learner trains ``actor_flat`` only.
     The adaption batch comes from the replay ring's own index stream (``replay.sample_indices``), so with the same seed the
     learner's later batches differ from those of an agent without parameter noise; the run stays deterministic.
+    ``param_noise_cycle=True`` does the adapt and the re-perturb of the synchronous loop in ONE launch
+    (``agent.param_noise_cycle``) instead of the composed sequence; stddev and acting copy carry the composed sequence's
+    bits whenever both agree on which side of the desired distance the measured one lies (``ssc.h``).  It is the
+    single-agent run :func:`rl_train_vec_ddpg_population` is defined against; ``overlap=True`` uses the cycle anyway.
 
     ``overlap=True`` with parameter noise: the rollouts act with one of TWO perturbed copies (chunk i with copy i & 1).
     On the learner stream, behind the iterations of chunk i, ONE launch (``agent.param_noise_cycle``) adapts the stddev on
@@ -622,7 +627,7 @@ def rl_train_vec_ddpg(env, agent, num_chunks, chunk_steps=256, replay_capacity=1
         if l is not None:
             losses.append(l)
         if param_noise:                                          # the next chunk's actor, with the adapted stddev
-            adapt_and_perturb(agent, replay, cycle=False)
+            adapt_and_perturb(agent, replay, cycle=bool(param_noise_cycle))
         log_stats(i)
         log_eval(i)
         if on_chunk is not None:
@@ -687,7 +692,7 @@ class PopulationMonitor:
 def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, replay_capacity=1 << 20, train_iters=None,
                                  replay_last_steps=None, seed=0, ring_capacity=1 << 20, track_episodes=False, overlap=False,
                                  drain_every=None, on_chunk=None, stats_every=None, eval_env=None, eval_every=None,
-                                 eval_steps=None, monitor=None):
+                                 eval_steps=None, monitor=None, param_noise_cycle=False):
     """The synchronous :func:`rl_train_vec_ddpg` for P (env, agent) pairs -- seeds x hyper-parameter grids, the reference's
     experimenter.py fan-out -- with ONE learner launch per chunk for the whole population
     (:class:`agents.DDPGPopulation`): per chunk every pair rolls out, decays its epsilon, appends to its own replay ring
@@ -710,7 +715,16 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
     for ``stats_every=`` / ``eval_env=`` / ``eval_every=`` / ``eval_steps=``, bit for bit; everything else the loop computes
     is bit-identical to the run without a monitor.
 
-    Not in this form: ``overlap`` and agents with parameter-space noise (NotImplementedError).  The single loop's keywords
+    ``param_noise_cycle=True``: agents with parameter-space noise may be part of the population, mixed with plain ones.  The
+    keyword has the meaning it has in :func:`rl_train_vec_ddpg` -- adapt and re-perturb in the one-launch cycle form -- and the
+    population loop has no other form: without it a noisy agent keeps raising NotImplementedError, as the single loop's default
+    (the composed sequence, other bits wherever the two forms disagree on the side of the desired distance) is not what this
+    loop would compute.  A noisy pair rolls out with its perturbed actor, and ONE ``population.param_noise_cycle`` (one sampling launch and one cycle launch for all noisy agents)
+    stands in front of chunk 0 (every ring is empty: perturb only, the single loop's ``perturb_policy()``) and behind the
+    learner launch of every chunk, in front of the monitor -- so the diagnostics see the copy the next chunk acts with.
+    Such a pair equals, bit for bit, its own ``rl_train_vec_ddpg(..., param_noise_cycle=True)`` run.
+
+    Not in this form: ``overlap`` (NotImplementedError).  The single loop's keywords
     ``stats_every`` and ``eval_env`` / ``eval_every`` / ``eval_steps`` take one value, not one per pair: they raise
     NotImplementedError too and point to ``monitor``.  ``on_chunk(i, chunks, envs)`` gets the lists.  Returns
     [(Summary, losses per chunk, replay)] per pair."""
@@ -723,11 +737,13 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
         if on:
             raise NotImplementedError(f"rl_train_vec_ddpg_population: {what} is a keyword of the single loop; the population loop "
                                       "takes monitor=PopulationMonitor(eval_envs=, eval_every=, eval_steps=, stats_every=)")
-    for what, on in (("overlap=True", overlap),
-                     ("an agent with parameter-space noise", any(getattr(a, "param_noise", None) is not None for a in agents))):
-        if on:
-            raise NotImplementedError(f"rl_train_vec_ddpg_population: {what} is not part of the population loop; "
-                                      "run that pair through rl_train_vec_ddpg")
+    if overlap:
+        raise NotImplementedError("rl_train_vec_ddpg_population: overlap=True is not part of the population loop; "
+                                  "run that pair through rl_train_vec_ddpg")
+    if not param_noise_cycle and any(getattr(a, "param_noise", None) is not None for a in agents):
+        raise NotImplementedError("rl_train_vec_ddpg_population: an agent with parameter-space noise runs in the cycle form only: pass "
+                                  "param_noise_cycle=True (each pair then equals its rl_train_vec_ddpg(..., param_noise_cycle=True) run), "
+                                  "or run that pair through rl_train_vec_ddpg")
     eval_envs, eval_every, eval_steps, stats_every = (monitor if monitor is not None else PopulationMonitor()).checked(envs)
     P = len(agents)
     seeds = [int(seed)] * P if isinstance(seed, (int, np.integer)) else [int(s) for s in seed]
@@ -748,7 +764,10 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
         dropped[p] += d
         summaries[p].extend_records(lens, rets)
 
-    pds = [env.policy_desc(agent.as_policy(device_epsilon=True)) for env, agent in zip(envs, agents)]
+    noisy = [getattr(a, "param_noise", None) is not None for a in agents]
+    # a noisy pair acts with its perturbed copy (views into perturbed_actor_flat)
+    pds = [env.policy_desc(agent.as_policy(device_epsilon=True, perturbed=True) if pn else agent.as_policy(device_epsilon=True))
+           for env, agent, pn in zip(envs, agents, noisy)]
     # the rest of the chunk, one launch per phase for all pairs (a population a launch does not serve: pair by pair inside)
     from .obs_rms import ObsRmsGroup
     from .population import PairCursors
@@ -785,6 +804,8 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
             population.evaluate_device(eval_envs, eval_steps, out=eval_block)
             eval_log[i // eval_every].copy_(eval_block)
 
+    if any(noisy):
+        population.param_noise_cycle(replays)     # every ring is empty: the perturbation in front of chunk 0
     for i in range(num_chunks):
         if cursors is None:                       # the per-pair calls, pair by pair
             for p, (env, agent) in enumerate(zip(envs, agents)):
@@ -804,6 +825,8 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
         for p, l in enumerate(population.train_from(replays, train_iters, copy=True)):
             if l is not None:
                 losses[p].append(l)
+        if any(noisy):                            # the next chunk's acting copies, with the adapted stddevs
+            population.param_noise_cycle(replays)
         log_monitor(i)
         if on_chunk is not None:
             on_chunk(i, chunks, envs)
