@@ -13,8 +13,11 @@ pytestmark = pytest.mark.gpu
 
 TOL_ACT_F32 = 1e-5     # fp32 kernel vs fp64 oracle, abs on actions
 TOL_ACT_BF16 = 2e-2    # bf16 MFMA kernel vs fp32/fp64
-TOL_ACT_BF16_EMU = 1.5e-3  # vs the oracle's own bf16 emulation: equal except where a hidden activation sits on a
-                         # bf16 rounding boundary and fp32/fp64 evaluation rounds it to different neighbours
+TOL_ACT_BF16_EMU = 1.5e-3  # vs the oracle's PLAIN bf16 emulation, which rounds W2 where the kernels round W2 * 2 log2(e)
+                         # (the tanh constant folded into layer 2): the two models differ by 0.7e-3 .. 1.4e-3 at the shapes
+                         # below, and that is nearly all of this tolerance.  Against actor_forward_bf16emu(fold=True) the
+                         # standalone kernels stay within 0.24 of the bf16 error itself (tests/test_gpu_actor_matrix.py,
+                         # NOTEBOOK section 20); rounding-boundary flips of single hidden activations are what is left.
 
 
 @pytest.fixture(scope="module")

@@ -36,6 +36,41 @@ def test_actor_matches_torch_stack():
         assert np.max(np.abs(emu - got)) < 2e-2
 
 
+def test_actor_bf16emu_fold_models_the_kernels_tanh_constant():
+    """actor_forward_bf16emu(fold=True): bit for bit the plain emulation without last_layer_tanh (the kernels fold
+    nothing there), a different result with it (W2 * c is rounded to bf16, not W2), and as close to the fp64 forward as the
+    plain emulation is held to in test_actor_matches_torch_stack.  Also through OracleDDPGPolicy(bf16="fold")."""
+    rng = np.random.default_rng(0)
+    for obs_dim, h1, h2 in [(2, 64, 32), (3, 128, 64), (2, 200, 100), (3, 37, 19)]:
+        w = actor_weights(obs_dim, h1, h2, seed=h1, w3_scale=0.5)
+        obs = rng.uniform(-1, 1, size=(257, obs_dim)).astype(np.float32)
+        for clip in (None, 0.5):
+            plain = O.actor_forward_bf16emu(obs, **w, last_layer_tanh=False, obs_clip=clip)
+            assert np.array_equal(O.actor_forward_bf16emu(obs, **w, last_layer_tanh=False, obs_clip=clip, fold=True), plain)
+            assert np.array_equal(O.actor_forward_bf16emu(obs, **w, last_layer_tanh=False, obs_clip=clip, fold=False), plain)
+            old = O.actor_forward_bf16emu(obs, **w, last_layer_tanh=True, obs_clip=clip)
+            assert np.array_equal(O.actor_forward_bf16emu(obs, **w, last_layer_tanh=True, obs_clip=clip, fold=False), old)
+            new = O.actor_forward_bf16emu(obs, **w, last_layer_tanh=True, obs_clip=clip, fold=True)
+            assert not np.array_equal(new, old)
+            assert np.max(np.abs(new - O.actor_forward(obs, **w, last_layer_tanh=True, obs_clip=clip))) < 2e-2
+        pol = O.OracleDDPGPolicy(w, 5, 0, 257, epsilon=0.0, bf16="fold")
+        want = O.actor_forward_bf16emu(obs, **w, last_layer_tanh=True, fold=True)[:, 0]
+        assert np.array_equal(pol(0, 0, obs, None), O.ddpg_action(want, 0.0, 0.0))
+
+
+def test_oracle_policy_device_epsilon_advances_the_noise_state():
+    """OracleDDPGPolicy(device_epsilon=True): a zero or negative epsilon adds no noise to the action, but the OU state
+    advances (the kernels run the noise path whenever epsilon is read from the device); with a host epsilon of 0 it stays."""
+    w = actor_weights(2, 64, 32, seed=1, w3_scale=0.5)
+    obs = np.random.default_rng(3).uniform(-1, 1, size=(9, 2)).astype(np.float32)
+    net = O.ddpg_action(O.actor_forward(obs, **w)[:, 0], 0.0, 0.0)
+    for eps in (0.0, -0.5):
+        host, dev = O.OracleDDPGPolicy(w, 5, 0, 9, epsilon=eps), O.OracleDDPGPolicy(w, 5, 0, 9, epsilon=eps, device_epsilon=True)
+        assert np.array_equal(host(0, 4, obs, None), net) and np.array_equal(dev(0, 4, obs, None), net)
+        assert not host.x.any() and dev.x.all()
+        assert np.array_equal(dev.x, O.ou_step(np.zeros(9), O.ou_gaussian(5, dev.ids, 4), 0.4, 0.6))
+
+
 def test_critic_matches_torch_stack():
     rng = np.random.default_rng(1)
     W1, b1 = rng.normal(size=(2, 64)), rng.normal(size=64)
