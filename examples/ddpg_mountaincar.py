@@ -20,11 +20,11 @@ import smartstartcontinuous_amd as ssc  # noqa: E402
 from smartstartcontinuous_amd.agents import DDPG_Baselines_agent  # noqa: E402
 
 
-def make_agent(env, seed, normalize_observations=False, param_noise=None, popart=False):
+def make_agent(env, seed, normalize_observations=False, param_noise=None, popart=False, hidden=(64, 32)):
     return DDPG_Baselines_agent(env, None, buffer_size=100000, batch_size=64, num_train_iterations=50,
                                 num_steps_before_train=200, ou_epsilon=1.0, ou_min_epsilon=0.01,
                                 ou_epsilon_decay_factor=.99, ou_mu=0.4, ou_sigma=0.6, ou_theta=.15, actor_lr=0.001,
-                                actor_h1=64, actor_h2=32, critic_lr=0.001, critic_h1=64, critic_h2=32,
+                                actor_h1=hidden[0], actor_h2=hidden[1], critic_lr=0.001, critic_h1=hidden[0], critic_h2=hidden[1],
                                 lastLayerTanh=True, normalize_observations=normalize_observations, seed=seed,
                                 param_noise_stddev=param_noise, normalize_returns=popart, enable_popart=popart)
 
@@ -48,6 +48,11 @@ def main():
     ap.add_argument("--param-noise", default=None, metavar="STDDEV[,STDDEV...]",
                     help="adaptive parameter-space noise with this initial (and desired action) stddev, on top of the OU noise; "
                          "with --population a comma list sweeps it: pair p takes entry p modulo the list's length")
+    ap.add_argument("--hidden", default=None, metavar="H1-H2[,H1-H2...]",
+                    help="hidden layer sizes of actor and critic (default 64-32); with --population a comma list sweeps them, "
+                         "e.g. 64-32,128-64,200-100 (the reference's hidden_layer_size_experiment): pair p takes entry p modulo "
+                         "the list's length, the 64-32 agents train in the one-workgroup launch and the wider ones in the grouped "
+                         "multi-workgroup launches")
     ap.add_argument("--popart", action="store_true",
                     help="DDPG normalize_returns + enable_popart: the critic learns normalised returns, its output layer is "
                          "rescaled with the running return statistics (Pop-Art)")
@@ -69,11 +74,21 @@ def main():
         if len(stddevs) > 1 and args.population is None:
             ap.error("a list of --param-noise values needs --population")
         args.param_noise = stddevs[0]
+    hidden = [(64, 32)]
+    if args.hidden is not None:
+        try:
+            hidden = [tuple(int(x) for x in h.split("-")) for h in args.hidden.split(",")]
+        except ValueError:
+            hidden = []
+        if not hidden or any(len(h) != 2 or min(h) < 1 for h in hidden):
+            ap.error("--hidden takes H1-H2 or a comma list of them")
+        if len(hidden) > 1 and args.population is None:
+            ap.error("a list of --hidden values needs --population")
     np.random.seed(args.seed)
     if args.mode == "single":
         env = ssc.Continuous_MountainCarEnv_Editted.make_timed_env(args.power_scalar, max_episode_steps=1000,
                                                                    seed=args.seed)
-        agent = make_agent(env, args.seed, args.normalize_observations, args.param_noise, args.popart)
+        agent = make_agent(env, args.seed, args.normalize_observations, args.param_noise, args.popart, hidden[0])
         if args.stats_every is None:
             summary = ssc.rlTrain(agent, env, print_results=True, print_steps=False, num_episodes=args.episodes,
                                   max_steps=1000)
@@ -95,8 +110,9 @@ def main():
         seeds = [args.seed + p for p in range(P)]
         envs = [ssc.VecEnv(env_id, args.envs, seed=s, env_id0=p * args.envs) for p, s in enumerate(seeds)]
         noise = [None if stddevs is None else stddevs[p % len(stddevs)] for p in range(P)]
-        agents = [make_agent(ssc.SingleEnvView(ssc.VecEnv(env_id, 1, seed=s)), s, args.normalize_observations, sd, args.popart)
-                  for s, sd in zip(seeds, noise)]
+        agents = [make_agent(ssc.SingleEnvView(ssc.VecEnv(env_id, 1, seed=s)), s, args.normalize_observations, sd, args.popart,
+                             hidden[p % len(hidden)])
+                  for p, (s, sd) in enumerate(zip(seeds, noise))]
         eval_envs = None
         if args.eval_every is not None:        # envs of their own per pair: another seed, ids behind all training envs'
             eval_envs = [ssc.VecEnv(env_id, args.eval_envs, seed=s + P, env_id0=P * args.envs + p * args.eval_envs)
@@ -109,8 +125,8 @@ def main():
         last = lambda log, k: next((v for v in log[k][::-1] if not np.isnan(v)), float("nan"))   # the last row that was written
         for s, agent, (summary, losses, replay) in zip(seeds, agents, runs):   # one line per pair
             late = [ret for _steps, ret in summary.episodes[-max(1, len(summary) // 4):]]
-            line = ("seed %d: %d finished episodes, late-window return %.2f (last quarter of them), last critic/actor loss %.4g / %.4g"
-                    % (s, len(summary), float(np.mean(late)) if late else float("nan"), *losses[-1][-1].tolist()))
+            line = ("seed %d (%d-%d): %d finished episodes, late-window return %.2f (last quarter of them), last critic/actor loss %.4g / %.4g"
+                    % (s, agent.h1, agent.h2, len(summary), float(np.mean(late)) if late else float("nan"), *losses[-1][-1].tolist()))
             if args.eval_every is not None:
                 line += ", eval/return %.2f eval/Q %.4g over %.0f episodes" % (
                     last(summary.eval_stats, "eval/return"), last(summary.eval_stats, "eval/Q"), last(summary.eval_stats, "eval/episodes"))
@@ -128,7 +144,7 @@ def main():
     else:
         env = ssc.VecEnv("MountainCarContinuousActionX%s-v0" % args.power_scalar, args.envs, seed=args.seed)
         agent = make_agent(ssc.SingleEnvView(ssc.VecEnv(env.spec.id, 1, seed=args.seed)), args.seed, args.normalize_observations,
-                           args.param_noise, args.popart)
+                           args.param_noise, args.popart, hidden[0])
         eval_kw = {}
         if args.eval_every is not None:        # envs of their own: another seed, ids behind the training envs'
             eval_kw = dict(eval_env=ssc.VecEnv(env.spec.id, args.eval_envs, seed=args.seed + 1, env_id0=args.envs),

@@ -690,6 +690,64 @@ typedef struct ssc_ddpg_many_item ssc_ddpg_many_item;
 int ssc_ddpg_train_many(const ssc_ddpg_many_item *h_items, const ssc_ddpg_many_item *d_items, int32_t n_agents,
                         ssc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A population of ANY mix of shapes on the multi-workgroup learner, in grouped launches
+ * -------------------------------------------------------------------------------------
+ * What ssc_ddpg_train_many is for the shipped shape, for every descriptor ssc_ddpg_train_ws[_rms] runs on the
+ * multi-workgroup kernels: layers wider than 64 (the reference's 128-64 / 200-100 grid), batch sizes 1..4096, LayerNorm,
+ * critic_l2_reg, clip_norm, any obs_dim / last_layer_tanh, statistics on some agents and not on others -- all mixed in one
+ * call.  Grid row p of every launch is an agent: 2 launches per iteration for the call (3 with critic_l2_reg /
+ * clip_norm somewhere) instead of 2 or 3 per agent and iteration, and agent p's result -- the ten arrays, both Adam
+ * counters, the losses -- is bit for bit what ssc_ddpg_train_ws / ssc_ddpg_train_ws_rms gives it alone (the kernels share
+ * the per-agent arithmetic; nothing is summed across agents).  Pop-Art agents train alone (ssc_ddpg_train_ws_popart).
+ *
+ * The item is ssc_ddpg_many_item plus the agent's own workspace, sized by ssc_ddpg_train_workspace_bytes and laid out as
+ * the single-agent call lays it out.  d_batch_idx is [n_iters][batch_size] of THIS agent's batch size.
+ *
+ * The kernels read per-agent tables from a device array, the PLAN; the library allocates nothing, so the caller owns it:
+ *   1. ssc_ddpg_train_many_wide_plan validates the items and fills h_plan (host memory, pinned if the copy is to be
+ *      asynchronous), ssc_ddpg_train_many_wide_plan_bytes(n_agents) bytes; agent p's part depends on item p only;
+ *   2. the caller copies h_plan to d_plan (complete on `stream` before the call);
+ *   3. ssc_ddpg_train_many_wide validates again -- everything on the host copies, before any HIP call; a plan that no
+ *      longer matches the items is SSC_EINVAL -- and launches.
+ * Per-iteration quantities (the index rows, the losses row) are derived from the iteration index, a kernel argument: a
+ * plan stays valid, call after call, until a pointer, a shape or an iteration count changes.
+ *
+ * Refused (SSC_EINVAL unless said otherwise): n_agents < 1 (above 65535: SSC_EUNSUPPORTED), a NULL array, an item that
+ * fails the single-agent checks, an item with n_iters > 0 that ssc_ddpg_train_ws[_rms] would not run on the
+ * multi-workgroup kernels (SSC_EUNSUPPORTED, the agent and its path in ssc_last_error(); ssc_ddpg_learner_path tells
+ * beforehand), a workspace below ssc_ddpg_train_workspace_bytes, a tile above the 160 KB of LDS (SSC_EUNSUPPORTED), two
+ * agents on one parameter / optimiser array or workspace.  All n_iters == 0: SSC_OK without a launch; such an item may
+ * bring NULL arrays and no workspace, and only its shape is checked. */
+struct ssc_ddpg_many_wide_item {
+    ssc_ddpg_desc   ddpg;            /* this agent's arrays and hyper-parameters */
+    ssc_replay_view replay;          /* this agent's ring */
+    const int32_t  *d_batch_idx;     /* [n_iters][ddpg.batch_size] */
+    float          *d_losses;        /* [n_iters][2] or NULL */
+    const double   *d_rms;           /* normalize_observations block or NULL, per agent */
+    int32_t         n_iters;         /* >= 0, per agent; 0: the agent is left exactly as it is */
+    void           *d_workspace;     /* this agent's own, ssc_ddpg_train_workspace_bytes(&ddpg) bytes */
+    size_t          workspace_bytes;
+};
+typedef struct ssc_ddpg_many_wide_item ssc_ddpg_many_wide_item;
+
+size_t ssc_ddpg_train_many_wide_plan_bytes(int32_t n_agents);   /* linear in n_agents; 0 for n_agents < 1 */
+int ssc_ddpg_train_many_wide_plan(const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, void *h_plan, size_t plan_bytes);
+int ssc_ddpg_train_many_wide(const ssc_ddpg_many_wide_item *h_items, const void *h_plan, const void *d_plan, int32_t n_agents,
+                             ssc_stream_t stream);
+
+/* Which learner ssc_ddpg_train (have_workspace = 0) / ssc_ddpg_train_ws[_rms] (have_workspace = 1; have_rms: a statistics
+ * block comes with the call) runs a descriptor on, the SSC_DDPG_INTERPRETER / SSC_DDPG_WIDE switches of the environment
+ * included: one of the values below, or SSC_EINVAL for a NULL or unsized descriptor.  Host only. */
+enum {
+    SSC_DDPG_PATH_FIXED = 0,            /* the shipped 64-32 shape at batch 64, one workgroup */
+    SSC_DDPG_PATH_FIXED_TILED = 1,      /* the shipped networks at batches of several 64-row tiles */
+    SSC_DDPG_PATH_INTERPRETER = 2,      /* other layers <= 64 at batch 64, one workgroup */
+    SSC_DDPG_PATH_WIDE = 3,             /* the multi-workgroup kernels */
+    SSC_DDPG_PATH_NEEDS_WORKSPACE = 4   /* ssc_ddpg_train refuses it: call ssc_ddpg_train_ws */
+};
+int ssc_ddpg_learner_path(const ssc_ddpg_desc *ddpg, int have_workspace, int have_rms);
+
 struct ssc_replay_sample_key {
     uint64_t seed, counter0;
     int64_t size;

@@ -151,6 +151,14 @@ class DdpgManyItem(Structure):
                 ("d_rms", c_void_p), ("n_iters", c_int32)]
 
 
+class DdpgManyWideItem(Structure):
+    _fields_ = DdpgManyItem._fields_ + [("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
+# ssc_ddpg_learner_path's answers
+SSC_DDPG_PATH_FIXED, SSC_DDPG_PATH_FIXED_TILED, SSC_DDPG_PATH_INTERPRETER, SSC_DDPG_PATH_WIDE, SSC_DDPG_PATH_NEEDS_WORKSPACE = range(5)
+
+
 class ReplaySampleKey(Structure):
     _fields_ = [("seed", c_uint64), ("counter0", c_uint64), ("size", c_int64)]
 
@@ -209,7 +217,8 @@ STRUCTS = {
     "ssc_mlp_desc": MlpDesc, "ssc_norm": Norm, "ssc_mpc_problems": MpcProblems, "ssc_mpc_sampling": MpcSampling,
     "ssc_mpc_nav_state": MpcNavState, "ssc_smartstart_step": SmartStartStep, "ssc_critic_desc": CriticDesc,
     "ssc_ddpg_desc": DdpgDesc, "ssc_replay_view": ReplayView, "ssc_replay_ring": ReplayRing,
-    "ssc_mlp_train_desc": MlpTrainDesc, "ssc_ddpg_many_item": DdpgManyItem, "ssc_replay_sample_key": ReplaySampleKey,
+    "ssc_mlp_train_desc": MlpTrainDesc, "ssc_ddpg_many_item": DdpgManyItem,
+    "ssc_ddpg_many_wide_item": DdpgManyWideItem, "ssc_replay_sample_key": ReplaySampleKey,
     "ssc_pair_cursor": PairCursor, "ssc_rollout_many_item": RolloutManyItem, "ssc_replay_append_item": ReplayAppendItem,
     "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem, "ssc_ddpg_eval_many_item": DdpgEvalManyItem,
     "ssc_ddpg_stats_many_item": DdpgStatsManyItem, "ssc_param_noise_many_item": ParamNoiseManyItem,
@@ -276,6 +285,11 @@ _SIGNATURES = {
     # a population of agents in one launch: host items / keys (validated) + the caller's device copy of the same bytes
     "ssc_ddpg_train_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "ssc_replay_sample_many": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    # ... of any mix of shapes on the multi-workgroup kernels: host items + the caller's plan (host copy, device copy)
+    "ssc_ddpg_train_many_wide_plan_bytes": (c_size_t, [c_int32]),
+    "ssc_ddpg_train_many_wide_plan": (c_int, [c_void_p, c_int32, c_void_p, c_size_t]),
+    "ssc_ddpg_train_many_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_ddpg_learner_path": (c_int, [POINTER(DdpgDesc), c_int, c_int]),
     # the rest of a population chunk, one launch each: host items / cursors (validated) + the caller's device copies
     "ssc_rollout_many": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "ssc_replay_append_many": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),

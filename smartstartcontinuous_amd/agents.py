@@ -815,6 +815,12 @@ class DDPG_Baselines_agent(ValueFuncRLAgent, ReplayBufferRLAgent):
 # adapt_and_perturb(cycle=True) calls (False: the yardstick of tools/exp_ddpg_population_param_noise.py).
 POPULATION_FUSED_PARAM_NOISE = True
 
+# DDPGPopulation.train_from / train_on on a population its single launch does not serve: sub-populations in grouped
+# launches (True), or the per-agent calls one after the other (False: the yardstick of tools/exp_ddpg_population_wide.py).
+# Fewer than POPULATION_WIDE_MIN_GROUP agents on the multi-workgroup kernels train alone.
+POPULATION_GROUPED_WIDE = True
+POPULATION_WIDE_MIN_GROUP = 2
+
 
 class DDPGPopulation:
     """P independent :class:`DDPG_Baselines_agent` objects -- seeds x hyper-parameter grids, what the reference fans out
@@ -825,7 +831,17 @@ class DDPGPopulation:
     The launch serves the shipped shape only (64-32 actor and critic, batch 64, one action, obs_dim 2 or 3, no LayerNorm /
     critic_l2_reg / clip_norm / Pop-Art; one obs_dim and lastLayerTanh for all, normalize_observations for all or for
     none, no array shared by two agents) and only while neither ``SSC_DDPG_INTERPRETER`` nor ``SSC_DDPG_WIDE`` is set.
-    Any other population runs the per-agent calls one after the other; ``fused`` tells which way the last call went.
+    ``fused`` tells whether the last call went that way as a whole.
+
+    Any other population is split three ways (``ways``: one of ``"one_workgroup"``, ``"wide"``, ``"alone"`` per agent, for
+    the last call).  The agents ``ssc_ddpg_learner_path`` -- the library's own rule, the two switches included -- sends to
+    the multi-workgroup kernels (wider layers, other batch sizes, LayerNorm, critic_l2_reg, clip_norm, statistics on a
+    shape without a normalising one-workgroup build) train together in the grouped launches of
+    ``ssc_ddpg_train_many_wide``: 2 launches per iteration for all of them (3 with critic_l2_reg / clip_norm) on a plan
+    this object owns.  The agents of the shipped shape go through ``ssc_ddpg_train_many`` as child populations, one per
+    (obs_dim, lastLayerTanh, statistics) key.  Everything else -- Pop-Art, the step interpreter's shapes, the tiled 64-32
+    path, a lone wide agent, agents that share an array -- runs ``agent.train_from`` / ``agent.train_on`` as before, and so
+    does every agent when ``POPULATION_GROUPED_WIDE`` is False.
 
     Index and loss tensors and the pinned-host and device copies of the launch descriptors stay with the population and
     are rebuilt only when a pointer, an iteration count or a ring changes: in steady state a call uploads the P sampling
@@ -847,7 +863,9 @@ class DDPGPopulation:
             raise ValueError("the agents of a population live on one device")
         self.lib = _ffi.lib()
         self.fused = None
+        self.ways = None
         self._sig = None
+        self._groups = None
         self._items_event = self._keys_event = None
 
     def __len__(self):
@@ -893,13 +911,17 @@ class DDPGPopulation:
         tensors [n_iters_p, 2]; None for an agent whose ring holds fewer than ``batch_size`` records (it is left exactly as
         it is).  ``n_iters``: None (each agent's ``num_train_iterations``), one count, or one per agent.  Every ring's index
         stream (``seed``, batches drawn so far) moves exactly as its own ``sample_indices`` would move it."""
+        return self._train_from(replays, n_iters, copy)
+
+    def _train_from(self, replays, n_iters, copy):
+        # (the body of train_from: a split population calls it on its children, which are no calls of the public method)
         replays = list(replays)
         if len(replays) != len(self.agents):
             raise ValueError("one replay ring per agent")
         n = [k if len(r) >= a.batch_size else 0 for k, r, a in zip(self._iters(n_iters), replays, self.agents)]
         views = [(r.s, r.a, r.r, r.t, r.s2) for r in replays]
         if not self._prepare(views, n, None):
-            return [a.train_from(r, k) if k > 0 else None for a, r, k in zip(self.agents, replays, n)]
+            return self._train_split(replays, views, None, n, copy)
         st = self._state
         if st["active"]:
             with torch.cuda.device(self.device):
@@ -917,7 +939,10 @@ class DDPGPopulation:
 
     def train_on(self, views, batch_idx, n_iters, copy=False):
         """The index-explicit form: ``views[p]`` = agent p's (s, a, r, t, s2) device arrays, ``batch_idx[p]`` int32
-        [n_iters[p], 64] (ignored where ``n_iters[p]`` is 0) -> list of loss tensors, None where ``n_iters[p]`` is 0."""
+        [n_iters[p], agent p's batch_size] (ignored where ``n_iters[p]`` is 0) -> list of loss tensors, None where ``n_iters[p]`` is 0."""
+        return self._train_on(views, batch_idx, n_iters, copy)
+
+    def _train_on(self, views, batch_idx, n_iters, copy):
         n = self._iters(n_iters)
         views, batch_idx = [tuple(v) for v in views], list(batch_idx)
         if len(views) != len(self.agents) or len(batch_idx) != len(self.agents):
@@ -926,7 +951,7 @@ class DDPGPopulation:
             if k > 0 and (tuple(idx.shape) != (k, a.batch_size) or idx.dtype != torch.int32 or not idx.is_contiguous()):
                 raise ValueError(f"batch_idx must be contiguous int32 [{k}, {a.batch_size}]")
         if not self._prepare(views, n, batch_idx):
-            return [a.train_on(*v, idx, k) if k > 0 else None for a, v, idx, k in zip(self.agents, views, batch_idx, n)]
+            return self._train_split(None, views, batch_idx, n, copy)
         return self._launch(copy)
 
     # ---- descriptors -----------------------------------------------------------------------------
@@ -935,16 +960,20 @@ class DDPGPopulation:
         ag = self.agents
         ptrs = [t.data_ptr() for a in ag for t in self._arrays(a)]
         rms = [None if a.obs_rms is None else a._rms_block().data_ptr() for a in ag]
-        sig = (self._forced_elsewhere(), tuple(ptrs), tuple(rms), tuple(n),
+        switches = tuple(os.environ.get(k) for k in ("SSC_DDPG_INTERPRETER", "SSC_DDPG_WIDE")) + (POPULATION_GROUPED_WIDE, POPULATION_WIDE_MIN_GROUP)
+        sig = (switches, tuple(ptrs), tuple(rms), tuple(n),
                tuple((v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(), v[4].data_ptr(), v[0].shape[0]) for v in views),
                None if batch_idx is None else tuple(idx.data_ptr() if k > 0 else 0 for idx, k in zip(batch_idx, n)),
-               tuple((a.gamma, a.tau, a.actor_lr, a.critic_lr, a.obs_dim, a.lastLayerTanh, a.batch_size) for a in ag),
+               tuple((a.gamma, a.tau, a.actor_lr, a.critic_lr, a.obs_dim, a.lastLayerTanh, a.batch_size, a.critic_l2_reg, a.clip_norm,
+                      a.popart) for a in ag),
                torch.cuda.current_stream(self.device).cuda_stream)
         if sig == self._sig:
             return self.fused
-        self._sig, self._state = sig, None
+        self._sig, self._state, self._groups = sig, None, None
         self.fused = self._fusable(ptrs)
+        self.ways = ("one_workgroup",) * len(ag)
         if not self.fused:
+            self._split(views, n, batch_idx, ptrs, rms)
             return False
         P, B = len(ag), self.B
         active = [p for p in range(P) if n[p] > 0]
@@ -980,6 +1009,120 @@ class DDPGPopulation:
             self._items_event.record()
         self._state = st
         return True
+
+    # ---- a population the single launch does not serve: three ways ---------------------------------
+    def _split(self, views, n, batch_idx, ptrs, rms):
+        """Route every agent (-> ``ways``) and build what the grouped routes keep between calls (-> ``_groups``)."""
+        ag, P = self.agents, len(self.agents)
+        ways = ["alone"] * P
+        if POPULATION_GROUPED_WIDE and len(set(ptrs)) == len(ptrs):
+            for p, a in enumerate(ag):
+                if a.popart:
+                    continue
+                path = self.lib.ssc_ddpg_learner_path(ctypes.byref(a.ddpg_desc()), 1, int(rms[p] is not None))
+                ways[p] = {_ffi.SSC_DDPG_PATH_WIDE: "wide", _ffi.SSC_DDPG_PATH_FIXED: "one_workgroup"}.get(path, "alone")
+            if ways.count("wide") < POPULATION_WIDE_MIN_GROUP:
+                ways = ["alone" if w == "wide" else w for w in ways]
+        self.ways = tuple(ways)
+        children = {}
+        for p, a in enumerate(ag):
+            if ways[p] == "one_workgroup":
+                children.setdefault((a.obs_dim, bool(a.lastLayerTanh), rms[p] is not None), []).append(p)
+        wide = [p for p in range(P) if ways[p] == "wide"]
+        self._groups = dict(alone=[p for p in range(P) if ways[p] == "alone"],
+                            children=[(ps, DDPGPopulation([ag[p] for p in ps])) for ps in children.values()],
+                            wide=self._wide_state(wide, views, n, batch_idx, rms) if wide else None)
+
+    def _wide_state(self, wide, views, n, batch_idx, rms):
+        """Items, workspaces, index and loss tensors and the plan (pinned host copy, device copy) of the agents on the
+        grouped multi-workgroup launches; kept until the call's signature changes."""
+        ag, W = self.agents, len(wide)
+        st = dict(agents=wide, n=[n[p] for p in wide])
+        with torch.cuda.device(self.device):
+            st["losses"] = torch.empty((sum(st["n"]), 2), dtype=torch.float32, device=self.device)
+            items = st["items"] = (_ffi.DdpgManyWideItem * W)()
+            off, st["rows"], st["idx"] = 0, [], []
+            # our own draw: one launch for all rings where every agent has the same batch size <= 64 (the sampler's one-wave
+            # kernel; rows [slot][n_max][B], agent p reads its first n[p] batches), else one launch per ring
+            active = [p for p in wide if n[p] > 0]
+            sizes = {ag[p].batch_size for p in active}
+            st["keys"] = None
+            if batch_idx is None and len(active) > 1 and len(sizes) == 1 and max(sizes) <= 64:
+                st["active"], st["n_max"], st["B"] = active, max(n[p] for p in active), max(sizes)
+                st["idx_all"] = torch.empty((len(active), st["n_max"], st["B"]), dtype=torch.int32, device=self.device)
+                st["h_keys"] = torch.empty(len(active) * ctypes.sizeof(_ffi.ReplaySampleKey), dtype=torch.uint8).pin_memory()
+                st["d_keys"] = torch.empty(st["h_keys"].numel(), dtype=torch.uint8, device=self.device)
+                st["keys"] = (_ffi.ReplaySampleKey * len(active)).from_address(st["h_keys"].data_ptr())
+            for it, p in zip(items, wide):
+                a, v, k = ag[p], views[p], n[p]
+                it.ddpg = d = a.ddpg_desc()
+                it.replay = _ffi.ReplayView(*(x.data_ptr() for x in v), v[0].shape[0])
+                it.n_iters, it.d_rms = k, rms[p]
+                need = int(self.lib.ssc_ddpg_train_workspace_bytes(ctypes.byref(d)))      # the agent's own, as train_on keeps it
+                ws = getattr(a, "_train_ws", None)
+                if ws is None or ws.numel() < need:
+                    ws = a._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                it.d_workspace, it.workspace_bytes = ws.data_ptr(), ws.numel()
+                st.setdefault("ws", []).append(ws)                                          # (alive as long as the plan names it)
+                st["rows"].append(st["losses"][off:off + k] if k > 0 else None)
+                idx = None
+                if k > 0:
+                    idx = (batch_idx[p] if batch_idx is not None else st["idx_all"][active.index(p)] if st["keys"] is not None
+                           else torch.empty((k, a.batch_size), dtype=torch.int32, device=self.device))
+                    it.d_losses, it.d_batch_idx = st["rows"][-1].data_ptr(), idx.data_ptr()
+                st["idx"].append(idx)
+                off += k
+            nbytes = int(self.lib.ssc_ddpg_train_many_wide_plan_bytes(W))
+            if self._items_event is not None:
+                self._items_event.synchronize()
+            st["h_plan"] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            _ffi.check(self.lib.ssc_ddpg_train_many_wide_plan(ctypes.addressof(items), W, st["h_plan"].data_ptr(), nbytes))
+            st["d_plan"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            st["d_plan"].copy_(st["h_plan"], non_blocking=True)
+            self._items_event = torch.cuda.Event()
+            self._items_event.record()
+        return st
+
+    def _train_split(self, replays, views, batch_idx, n, copy):
+        """The call on a split population; ``replays`` (train_from) or ``batch_idx`` (train_on) is None."""
+        ag, g = self.agents, self._groups
+        out = [None] * len(ag)
+        for p in g["alone"]:
+            if n[p] > 0:
+                out[p] = ag[p].train_from(replays[p], n[p]) if batch_idx is None else ag[p].train_on(*views[p], batch_idx[p], n[p])
+        for ps, child in g["children"]:
+            k = [n[p] for p in ps]
+            got = (child._train_from([replays[p] for p in ps], k, copy) if batch_idx is None
+                   else child._train_on([views[p] for p in ps], [batch_idx[p] for p in ps], k, copy))
+            for p, rows in zip(ps, got):
+                out[p] = rows
+        st = g["wide"]
+        if st is not None and any(st["n"]):
+            with torch.cuda.device(self.device):
+                if batch_idx is None and st["keys"] is not None:
+                    if self._keys_event is not None:
+                        self._keys_event.synchronize()           # the last upload has left the pinned keys
+                    for key, p in zip(st["keys"], st["active"]):
+                        key.seed, key.counter0, key.size = replays[p].take_sample_key(n[p], st["B"])
+                    st["d_keys"].copy_(st["h_keys"], non_blocking=True)
+                    self._keys_event = torch.cuda.Event()
+                    self._keys_event.record()
+                    _ffi.check(self.lib.ssc_replay_sample_many(st["h_keys"].data_ptr(), st["d_keys"].data_ptr(), len(st["active"]),
+                                                               st["n_max"], st["B"], _ffi.ptr(st["idx_all"]), _ffi.stream(self.device)))
+                elif batch_idx is None:     # every ring draws under its own key, as its sample_indices would
+                    for p, k, idx in zip(st["agents"], st["n"], st["idx"]):
+                        if k > 0:
+                            B = ag[p].batch_size
+                            seed, counter0, size = replays[p].take_sample_key(k, B)
+                            _ffi.check(self.lib.ssc_replay_sample(seed, counter0, size, k, B, _ffi.ptr(idx), _ffi.stream(self.device)))
+                _ffi.check(self.lib.ssc_ddpg_train_many_wide(ctypes.addressof(st["items"]), st["h_plan"].data_ptr(), st["d_plan"].data_ptr(),
+                                                             len(st["agents"]), _ffi.stream(self.device)))
+                block = st["losses"].clone() if copy else st["losses"]
+            off = 0
+            for p, k in zip(st["agents"], st["n"]):
+                out[p] = block[off:off + k] if k > 0 else None
+                off += k
+        return out
 
     def _launch(self, copy):
         st = self._state

@@ -99,6 +99,13 @@ void ddpg_wide_finish(const ssc_ddpg_desc *d, int32_t n_iters, hipStream_t strea
 // d_rms (all three): NULL, or the RunningMeanStd block of normalize_observations (actor_device.h)
 int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int32_t *d_batch_idx, int32_t n_iters,
                     float *d_losses, void *d_workspace, size_t workspace_bytes, hipStream_t stream, const double *d_rms);
+// A population on the same kernels, grid row = agent (ssc_ddpg_train_many_wide; the items already through ddpg_check).
+// The plan -- [n_agents rows | four lists of row numbers] -- is caller memory: ddpg_wide_plan fills a host buffer of
+// ddpg_wide_plan_bytes(n_agents) bytes (pure host code; refuses a short workspace and a tile above the LDS),
+// ddpg_train_wide_many launches over the host copy's geometry and the device copy's address.
+size_t ddpg_wide_plan_bytes(int32_t n_agents);
+int ddpg_wide_plan(const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, void *h_plan);
+int ddpg_train_wide_many(const void *h_plan, const void *d_plan, int32_t n_agents, hipStream_t stream);
 // Pop-Art (normalize_returns + enable_popart): every shape runs the multi-workgroup kernels, four launches per iteration;
 // d_ret_rms: the one-column RunningMeanStd block of the returns, read and written
 size_t ddpg_popart_workspace_bytes(const ssc_ddpg_desc *d);

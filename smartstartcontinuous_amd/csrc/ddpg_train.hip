@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -828,6 +829,88 @@ extern "C" int ssc_ddpg_train_many(const ssc_ddpg_many_item *h_items, const ssc_
 static bool ddpg_desc_sized(const ssc_ddpg_desc *d) {
     return d != nullptr && d->batch_size >= 1 && d->batch_size <= 4096 && d->obs_dim >= 1 && d->act_dim >= 1 && d->actor_h1 >= 1 &&
            d->actor_h2 >= 1 && d->critic_h1 >= 1 && d->critic_h2 >= 1;
+}
+
+// ddpg_train_any's rule, the two environment switches included
+static DdpgPath ddpg_path_now(const ssc_ddpg_desc *d, bool have_ws, bool have_rms) {
+    const char *force_i = getenv("SSC_DDPG_INTERPRETER"), *force_w = getenv("SSC_DDPG_WIDE");
+    return ddpg_learner_path(d, have_ws, have_rms, force_i && force_i[0] == '1', force_w && force_w[0] == '1');
+}
+
+static_assert(SSC_DDPG_PATH_FIXED == (int)DDPG_FIXED && SSC_DDPG_PATH_FIXED_TILED == (int)DDPG_FIXED_TILED &&
+                  SSC_DDPG_PATH_INTERPRETER == (int)DDPG_INTERPRETER && SSC_DDPG_PATH_WIDE == (int)DDPG_WIDE &&
+                  SSC_DDPG_PATH_NEEDS_WORKSPACE == (int)DDPG_NEEDS_WORKSPACE,
+              "include/ssc.h names the paths of ddpg_layout.h");
+
+extern "C" int ssc_ddpg_learner_path(const ssc_ddpg_desc *d, int have_workspace, int have_rms) {
+    SSC_REQUIRE(ddpg_desc_sized(d), "ssc_ddpg_learner_path: NULL descriptor or sizes out of range");
+    return (int)ddpg_path_now(d, have_workspace != 0, have_rms != 0);
+}
+
+// A population on the multi-workgroup kernels, grid row = agent (ddpg_train_wide.hip).  The walk both entry points share:
+// every refusal that needs no plan.  *any: some agent has iterations to run.
+static int many_wide_check(const char *fn, const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, bool *any) {
+    static const char *const kPath[] = {"the one-workgroup 64-32 kernel", "the tiled 64-32 kernel", "the step interpreter",
+                                        "the multi-workgroup kernels", "no learner without a workspace"};
+    SSC_REQUIRE(n_agents >= 1, "%s: n_agents %d < 1", fn, n_agents);
+    if (n_agents > 65535) return set_error(SSC_EUNSUPPORTED, "%s: n_agents %d > 65535 (one grid row per agent)", fn, n_agents);
+    SSC_REQUIRE(h_items != nullptr, "%s: NULL item array", fn);
+    *any = false;
+    std::vector<std::pair<const void *, int>> owned;   // (array, agent) of every parameter / optimiser array and workspace
+    owned.reserve((size_t)n_agents * 10);
+    for (int p = 0; p < n_agents; ++p) {
+        const ssc_ddpg_many_wide_item &it = h_items[p];
+        const ssc_ddpg_desc *d = &it.ddpg;
+        char who[56];
+        snprintf(who, sizeof who, "%s: agent %d", fn, p);
+        const int rc = ddpg_check(who, d, &it.replay, it.d_batch_idx, it.n_iters);
+        if (rc != DDPG_GO && rc != SSC_OK) return rc;
+        if (it.n_iters > 0) {
+            const DdpgPath path = ddpg_path_now(d, true, it.d_rms != nullptr);
+            if (path != DDPG_WIDE)
+                return set_error(SSC_EUNSUPPORTED, "%s: ssc_ddpg_train_ws runs this agent on %s, not on the multi-workgroup kernels "
+                                                   "(ssc_ddpg_learner_path); train it with ssc_ddpg_train_many or alone", who, kPath[path]);
+            *any = true;
+        }
+        for (const void *a : {(const void *)d->actor, (const void *)d->critic, (const void *)d->target_actor,
+                              (const void *)d->target_critic, (const void *)d->adam_m_actor, (const void *)d->adam_v_actor,
+                              (const void *)d->adam_m_critic, (const void *)d->adam_v_critic, (const void *)d->adam_t,
+                              (const void *)it.d_workspace})
+            if (a != nullptr) owned.emplace_back(a, p);   // (NULL: an agent with n_iters == 0 may bring none)
+    }
+    std::sort(owned.begin(), owned.end());
+    for (size_t k = 1; k < owned.size(); ++k)
+        SSC_REQUIRE(owned[k].first != owned[k - 1].first, "%s: agents %d and %d share a parameter / optimiser array or a workspace", fn,
+                    owned[k - 1].second, owned[k].second);
+    return SSC_OK;
+}
+
+extern "C" size_t ssc_ddpg_train_many_wide_plan_bytes(int32_t n_agents) { return ddpg_wide_plan_bytes(n_agents); }
+
+extern "C" int ssc_ddpg_train_many_wide_plan(const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, void *h_plan, size_t plan_bytes) {
+    const char *fn = "ssc_ddpg_train_many_wide_plan";
+    bool any = false;
+    if (int rc = many_wide_check(fn, h_items, n_agents, &any)) return rc;
+    SSC_REQUIRE(h_plan != nullptr, "%s: NULL plan", fn);
+    SSC_REQUIRE(plan_bytes >= ddpg_wide_plan_bytes(n_agents), "%s: plan %zu < %zu bytes (ssc_ddpg_train_many_wide_plan_bytes)", fn,
+                plan_bytes, ddpg_wide_plan_bytes(n_agents));
+    return ddpg_wide_plan(h_items, n_agents, h_plan);
+}
+
+extern "C" int ssc_ddpg_train_many_wide(const ssc_ddpg_many_wide_item *h_items, const void *h_plan, const void *d_plan, int32_t n_agents,
+                                        ssc_stream_t stream) {
+    const char *fn = "ssc_ddpg_train_many_wide";
+    bool any = false;
+    if (int rc = many_wide_check(fn, h_items, n_agents, &any)) return rc;
+    SSC_REQUIRE(h_plan != nullptr && d_plan != nullptr, "%s: NULL plan", fn);
+    // the plan these items give, against the one the caller uploaded: a stale plan would send the kernels to old pointers
+    std::vector<uint64_t> fresh((ddpg_wide_plan_bytes(n_agents) + 7) / 8);
+    if (int rc = ddpg_wide_plan(h_items, n_agents, fresh.data())) return rc;
+    SSC_REQUIRE(memcmp(fresh.data(), h_plan, ddpg_wide_plan_bytes(n_agents)) == 0,
+                "%s: the plan does not match the items (a pointer, a shape or an iteration count changed since "
+                "ssc_ddpg_train_many_wide_plan)", fn);
+    if (!any) return SSC_OK;
+    return ddpg_train_wide_many(h_plan, d_plan, n_agents, as_stream(stream));
 }
 
 extern "C" size_t ssc_ddpg_train_workspace_bytes(const ssc_ddpg_desc *d) {

@@ -22,11 +22,19 @@
 // counters are read-only during the launch sequence (iteration index added on the fly) and advanced by one
 // one-thread launch at the end.
 //
+// A population of agents of any mix of shapes runs the same two (three) launches per iteration with a grid row per agent
+// (ssc_ddpg_train_many_wide below): the kernels' bodies are __device__ functions shared by the single-agent and the grouped
+// __global__ kernels, and the grouped ones read from a device array, the plan, what the single-agent ones get as arguments.
+//
 // Pop-Art (normalize_returns + enable_popart, ddpg_editted.py:201-217, 291-301) is four launches per iteration on the same
 // pieces: the grad kernel built as a target pass (target networks only; writes y and per-workgroup sums), a one-workgroup
 // renormalise kernel (statistics update, rescaling of both critics' output layers), the grad kernel built without the
 // target levels (normalised TD error), and the unchanged apply pass -- ddpg_train_wide_popart below.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
 #include <type_traits>
+#include <vector>
 
 #include "actor_device.h"
 #include "ddpg_device.h"
@@ -89,7 +97,9 @@ struct WideTables {
 };
 static_assert(sizeof(WideTables) % 4 == 0 && sizeof(WideTables) <= 2 * kWThreads * 4, "two dwords per thread copy the tables");
 
-struct WideArgs {
+// Everything of a gradient launch except the tables: what the kernel keeps in scalar registers.  The single-agent kernel
+// has it in its kernel-argument segment, the grouped one reads it from its agent's row of the plan.
+struct WideHead {
     ssc_replay_view rp;
     const int32_t *batch_idx;    // [batch] of this iteration
     int32_t batch, obs_dim, act_dim;
@@ -100,9 +110,15 @@ struct WideArgs {
     float *lpart;   // [n_blocks][2]
     int32_t n_params;
     int32_t off_tab;             // LDS float offset of the copy of `tab`
+};
+struct WideArgs : WideHead {
     WideTables tab;
 };
+constexpr int kTabWords = (int)(sizeof(WideTables) / 4);
+static_assert(sizeof(WideHead) % alignof(WideTables) == 0 && sizeof(WideArgs) == sizeof(WideHead) + sizeof(WideTables),
+              "the tables follow the head without a gap");
 
+// (any address that is the same in every lane: the tables in LDS, and a row of the plan in the grouped kernel)
 template <class T> __device__ __forceinline__ T lds_uniform(const T *p) {
     static_assert(sizeof(T) % 4 == 0, "dword-sized tables");
     union { T t; uint32_t w[sizeof(T) / 4]; } u;
@@ -366,7 +382,7 @@ __device__ __forceinline__ void ret_mean_std(double sum, double sumsq, double cn
 
 // td_level of the target pass, thread r < 16 = the workgroup's row r: target_Q with the OLD statistics (:132-133 through
 // denormalize, :292-296), and the 16 rows' sums in f64 by an xor butterfly (the same order every time)
-__device__ __forceinline__ void pop_target_rows(const WideArgs &a, const PopTarget &pt, float *rt, int r, int row0, bool valid) {
+__device__ __forceinline__ void pop_target_rows(const WideHead &a, const PopTarget &pt, float *rt, int r, int row0, bool valid) {
 #pragma clang fp contract(off)
     float mu, sg;
     ret_mean_std(pt.ret_rms[0], pt.ret_rms[1], pt.ret_rms[2], mu, sg);
@@ -388,7 +404,7 @@ __device__ __forceinline__ void pop_target_rows(const WideArgs &a, const PopTarg
 
 // td_level of the gradient pass: critic loss mean((q - (y - mu_new) / sigma_new)^2) (:181 with normalize, :140-149),
 // actor loss -mean(q_pi sigma_new + mu_new) (:131, :170), hence dL/dq_pi = -sigma_new / B
-__device__ __forceinline__ void pop_grad_rows(const WideArgs &a, const PopGrad &pg, float *rt, int r, int row0, bool valid, float *lpart) {
+__device__ __forceinline__ void pop_grad_rows(const WideHead &a, const PopGrad &pg, float *rt, int r, int row0, bool valid, float *lpart) {
 #pragma clang fp contract(off)
     const float mu = pg.scal[2], sg = pg.scal[3];
     const float y = pg.y[min(row0 + r, a.batch - 1)];
@@ -409,28 +425,15 @@ __device__ __forceinline__ void pop_grad_rows(const WideArgs &a, const PopGrad &
     }
 }
 
+// The gradient pass of one workgroup once the tables stand in LDS at a.off_tab (the caller's copy and barrier): shared by
+// the single-agent kernel and the grouped one, so that an agent's arithmetic does not depend on which launch runs it.
 // Rms (normalize_observations): the RunningMeanStd block; obs0 / obs1 enter the networks as clip((x - mean) / std).
 // The pack may end in a PopTarget or a PopGrad (above).
 template <class... Rms>
-__global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a, Rms... rms) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-#ifdef SSC_WIDE_DIAG
-    const uint64_t t_entry = __builtin_amdgcn_s_memtime();
-#endif
+__device__ __forceinline__ void wide_grad_body(const WideHead &a, float *lds, uint64_t t_entry, Rms... rms) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: job dispatch runs on the scalar unit
     const int row0 = blockIdx.x * kWR;
-    // ---- the tables: one dword per thread from the kernel-argument segment into LDS ----
-#if defined(__HIP_DEVICE_COMPILE__)
-    {
-        typedef const __attribute__((address_space(4))) char *karg_bytes;
-        typedef const __attribute__((address_space(4))) uint32_t *karg_words;
-        const karg_words src = (karg_words)((karg_bytes)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(WideArgs, tab));
-#pragma unroll
-        for (int e = tid; e < (int)(sizeof(WideTables) / 4); e += kWThreads) reinterpret_cast<uint32_t *>(lds + a.off_tab)[e] = src[e];
-    }
-#endif
-    __syncthreads();
     const WideTables *T = reinterpret_cast<const WideTables *>(lds + a.off_tab);
     // ---- everything the launch needs from memory is requested up front, in one round trip where it can be:
     //   * the batch indices (the rows need a second, dependent one);
@@ -616,6 +619,27 @@ __global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a, R
 #endif
 }
 
+template <class... Rms>
+__global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_kernel(WideArgs a, Rms... rms) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    uint64_t t_entry = 0;
+#ifdef SSC_WIDE_DIAG
+    t_entry = __builtin_amdgcn_s_memtime();
+#endif
+    // ---- the tables: one dword per thread from the kernel-argument segment into LDS ----
+#if defined(__HIP_DEVICE_COMPILE__)
+    {
+        typedef const __attribute__((address_space(4))) char *karg_bytes;
+        typedef const __attribute__((address_space(4))) uint32_t *karg_words;
+        const karg_words src = (karg_words)((karg_bytes)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(WideHead));
+#pragma unroll
+        for (int e = threadIdx.x; e < kTabWords; e += kWThreads) reinterpret_cast<uint32_t *>(lds + a.off_tab)[e] = src[e];
+    }
+#endif
+    __syncthreads();
+    wide_grad_body(a, lds, t_entry, rms...);
+}
+
 struct ApplyArgs {
     ssc_ddpg_desc d;
     const float *gpart, *lpart;
@@ -665,8 +689,7 @@ __device__ __forceinline__ float block256_sum(float x, float *red) {
 
 // critic_l2_reg / clip_norm only: gsum = sum of the partials (+ critic_l2_reg * W on the critic's dense kernels: the
 // gradient of scale * l2_loss(W), ddpg_editted.py:183-191), and the block's share of sum W^2 for the reported loss
-__global__ __launch_bounds__(256) void ddpg_wide_prepare_kernel(ApplyArgs a) {
-    __shared__ float red[4];
+__device__ __forceinline__ void wide_prepare_body(const ApplyArgs &a, float *red) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     const int n = a.nA + a.nC;
     float sq = 0.0f;
@@ -686,15 +709,20 @@ __global__ __launch_bounds__(256) void ddpg_wide_prepare_kernel(ApplyArgs a) {
     if (threadIdx.x == 0) a.regpart[blockIdx.x] = sq;
 }
 
-template <bool PREPARED>
-__global__ __launch_bounds__(256) void ddpg_wide_apply_kernel(ApplyArgs a) {
-    __shared__ AdamCfg cfg[2];
+__global__ __launch_bounds__(256) void ddpg_wide_prepare_kernel(ApplyArgs a) {
     __shared__ float red[4];
+    wide_prepare_body(a, red);
+}
+
+// The apply pass of one 256-thread block on iteration `it` of the call (losses: the [2] of that iteration or nullptr);
+// shared by the single-agent kernel and the grouped one.
+template <bool PREPARED>
+__device__ __forceinline__ void wide_apply_body(const ApplyArgs &a, int it, float *losses, AdamCfg *cfg, float *red) {
     if (threadIdx.x < 2) {
         // MpiAdam's bias-corrected step size in f64 (1 - 0.999^t loses 5 digits in fp32); t = counter before this
         // call + iterations done + 1 (the counters themselves move once, after the last iteration)
         const int net = threadIdx.x;
-        const int t = a.d.adam_t[net] + a.it + 1;
+        const int t = a.d.adam_t[net] + it + 1;
         const double b1 = ipow((double)a.d.beta1, t), b2 = ipow((double)a.d.beta2, t);
         cfg[net] = adam_cfg(net == 0 ? (double)a.d.actor_lr : (double)a.d.critic_lr, b1, b2, a.d);
     }
@@ -736,17 +764,25 @@ __global__ __launch_bounds__(256) void ddpg_wide_apply_kernel(ApplyArgs a) {
         tg = (1.0f - a.d.tau) * tg + a.d.tau * th;
         mm[q] = m; vv[q] = v; theta[q] = th; target[q] = tg;
     }
-    if (blockIdx.x == 0 && threadIdx.x < 2 && a.losses != nullptr) {
+    if (blockIdx.x == 0 && threadIdx.x < 2 && losses != nullptr) {
         float s = 0.0f;
         for (int b = 0; b < a.n_blocks; ++b) s += a.lpart[b * 2 + threadIdx.x];
         s /= (float)a.d.batch_size;
         if (PREPARED && threadIdx.x == 0) {
             float w2 = 0.0f;
-            for (unsigned b = 0; b < gridDim.x; ++b) w2 += a.regpart[b];
+            const int apply_blocks = (n + 255) / 256;     // (the single-agent launch's grid; a grouped one may be wider)
+            for (int b = 0; b < apply_blocks; ++b) w2 += a.regpart[b];
             s += 0.5f * a.d.critic_l2_reg * w2;
         }
-        a.losses[threadIdx.x] = s;
+        losses[threadIdx.x] = s;
     }
+}
+
+template <bool PREPARED>
+__global__ __launch_bounds__(256) void ddpg_wide_apply_kernel(ApplyArgs a) {
+    __shared__ AdamCfg cfg[2];
+    __shared__ float red[4];
+    wide_apply_body<PREPARED>(a, a.it, a.losses, cfg, red);
 }
 
 __global__ void ddpg_wide_finish_kernel(int32_t *adam_t, int32_t n_iters) {
@@ -784,20 +820,16 @@ WidePartials ddpg_wide_partials(const ssc_ddpg_desc *d, void *d_workspace, int n
                         reinterpret_cast<float *>(static_cast<char *>(d_workspace) + wide_gpart_bytes(d, n_blocks))};
 }
 
-void ddpg_wide_apply(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks, int it, float *d_losses_it, hipStream_t stream) {
+// The apply pass's arguments over `n_blocks` partials in `d_workspace`, iteration and losses row left open (the one place
+// that lays out [gsum | regpart] and the variable table; `ap` comes in zeroed).
+static void wide_apply_args(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks, ApplyArgs &ap) {
     const DdpgNets ac = ddpg_nets(d);
     const DdpgNet &A = ac.A, &C = ac.C;
     const int ln = A.ln;
     const int nA = A.total(), nC = C.total();
     const WidePartials wp = ddpg_wide_partials(d, d_workspace, n_blocks);
-    ApplyArgs ap{};
     ap.d = *d; ap.gpart = wp.gpart; ap.lpart = wp.lpart; ap.n_blocks = n_blocks; ap.nA = nA; ap.nC = nC;
-    ap.it = it; ap.losses = d_losses_it;
-    const unsigned apply_blocks = (unsigned)((nA + nC + 255) / 256);
-    if (!wide_prepared(d)) {
-        hipLaunchKernelGGL(ddpg_wide_apply_kernel<false>, dim3(apply_blocks), dim3(256), 0, stream, ap);
-        return;
-    }
+    if (!wide_prepared(d)) return;
     char *tail = static_cast<char *>(d_workspace) + wide_gpart_bytes(d, n_blocks) + wide_lpart_bytes(n_blocks);
     ap.gsum = reinterpret_cast<float *>(tail);
     ap.regpart = reinterpret_cast<float *>(tail + (((size_t)(nA + nC) * sizeof(float) + 255) & ~(size_t)255));
@@ -817,6 +849,18 @@ void ddpg_wide_apply(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks, in
     }
     ap.n_var = nv;
     ap.var_lo[nv] = nA + nC;
+}
+
+void ddpg_wide_apply(const ssc_ddpg_desc *d, void *d_workspace, int n_blocks, int it, float *d_losses_it, hipStream_t stream) {
+    ApplyArgs ap;
+    memset(&ap, 0, sizeof ap);
+    wide_apply_args(d, d_workspace, n_blocks, ap);
+    ap.it = it; ap.losses = d_losses_it;
+    const unsigned apply_blocks = (unsigned)((ap.nA + ap.nC + 255) / 256);
+    if (!wide_prepared(d)) {
+        hipLaunchKernelGGL(ddpg_wide_apply_kernel<false>, dim3(apply_blocks), dim3(256), 0, stream, ap);
+        return;
+    }
     hipLaunchKernelGGL(ddpg_wide_prepare_kernel, dim3(apply_blocks), dim3(256), 0, stream, ap);
     hipLaunchKernelGGL(ddpg_wide_apply_kernel<true>, dim3(apply_blocks), dim3(256), 0, stream, ap);
 }
@@ -840,7 +884,7 @@ static int wide_build(const ssc_ddpg_desc *d, const ssc_replay_view *rp, int mod
     // with LayerNorm the contractions of the hidden layers leave the pre-normalisation sums and the LayerNorm op applies
     // the activation (ln_level)
     const int epi1 = ln ? EPI_NONE : EPI_RELU, epi2 = ln ? EPI_NONE : act2;
-    g = WideArgs{};
+    memset(&g, 0, sizeof g);     // (padding too: a plan row is compared byte by byte)
     g.rp = *rp; g.batch = d->batch_size; g.obs_dim = od; g.act_dim = ad; g.gamma = d->gamma; g.obs_clip = d->obs_clip;
     // ---- LDS carve: rows of 16 floats ([unit][row]) ------------------------------------------------------------------
     int p = 0;
@@ -1026,6 +1070,174 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
     }
     ddpg_wide_finish(d, n_iters, stream);
     return check_launch("ssc_ddpg_train (wide)");
+}
+
+// ---- a population in grouped launches (ssc_ddpg_train_many_wide): grid row blockIdx.y is an agent ----------------------
+// What the single-agent kernels get in their kernel-argument segment, agent p's workgroups read from row p of a device
+// array, the plan (caller-owned; filled on the host by ddpg_wide_plan_row).  Behind the P rows the plan holds four lists
+// of row numbers, one per launch group: the gradient launch is instantiated per statistics / no statistics, the apply
+// launch per prepared / plain, and grid row y of a launch serves agent list[y].  A grid is as wide as its widest agent;
+// a narrower agent's surplus workgroups, and every workgroup of an agent whose iterations are done, leave before their
+// first barrier.  Dynamic LDS is the launch's maximum; each agent keeps its own carve inside it.
+struct WideRowTail {
+    const double *d_rms;       // normalize_observations block or nullptr
+    float *d_losses;           // [n_iters][2] or nullptr
+    int32_t n_iters, n_blocks, apply_blocks, lds_bytes;
+};
+struct WidePlanRow {
+    WideArgs g;                // batch_idx: iteration 0's rows
+    ApplyArgs ap;              // it / losses unused: they follow from the launch's iteration
+    WideRowTail t;
+};
+static_assert(sizeof(WidePlanRow) % 8 == 0 && sizeof(WideHead) % 4 == 0 && sizeof(WideRowTail) % 4 == 0, "dword-sized, pointer-aligned rows");
+enum : int { LIST_GRAD_PLAIN = 0, LIST_GRAD_RMS, LIST_APPLY_PLAIN, LIST_APPLY_PREPARED, N_LISTS };
+
+template <bool RMS>
+__global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_many_kernel(const WidePlanRow *__restrict__ plan, const int32_t *__restrict__ list,
+                                                                         int32_t it) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const WidePlanRow *row = plan + list[blockIdx.y];
+    // one round trip: the head and the tail (every lane the same address; kept in scalar registers) and this thread's
+    // share of the tables -- the one vector load per thread of the single-agent kernel, from global memory
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&row->g.tab);
+    static_assert(kTabWords <= 2 * kWThreads, "two dwords per thread copy the tables");
+    const uint32_t w0 = src[min(tid, kTabWords - 1)], w1 = src[min(tid + kWThreads, kTabWords - 1)];
+    const WideRowTail t = lds_uniform(&row->t);
+    WideHead a = lds_uniform(static_cast<const WideHead *>(&row->g));
+    if ((int)blockIdx.x >= t.n_blocks || it >= t.n_iters) return;     // the whole workgroup, before the first barrier
+    a.batch_idx += (int64_t)it * a.batch;
+    uint32_t *dst = reinterpret_cast<uint32_t *>(lds + a.off_tab);
+    if (tid < kTabWords) dst[tid] = w0;
+    if (tid + kWThreads < kTabWords) dst[tid + kWThreads] = w1;
+    __syncthreads();
+    if constexpr (RMS) wide_grad_body(a, lds, 0, t.d_rms);
+    else wide_grad_body(a, lds, 0);
+}
+
+__global__ __launch_bounds__(256) void ddpg_wide_prepare_many_kernel(const WidePlanRow *__restrict__ plan, const int32_t *__restrict__ list,
+                                                                      int32_t it) {
+    __shared__ float red[4];
+    const WidePlanRow *row = plan + list[blockIdx.y];
+    if ((int)blockIdx.x >= row->t.apply_blocks || it >= row->t.n_iters) return;
+    wide_prepare_body(row->ap, red);
+}
+
+template <bool PREPARED>
+__global__ __launch_bounds__(256) void ddpg_wide_apply_many_kernel(const WidePlanRow *__restrict__ plan, const int32_t *__restrict__ list,
+                                                                    int32_t it) {
+    __shared__ AdamCfg cfg[2];
+    __shared__ float red[4];
+    const WidePlanRow *row = plan + list[blockIdx.y];
+    if ((int)blockIdx.x >= row->t.apply_blocks || it >= row->t.n_iters) return;
+    float *losses = row->t.d_losses;
+    wide_apply_body<PREPARED>(row->ap, it, losses != nullptr ? losses + 2 * it : nullptr, cfg, red);
+}
+
+// one thread per agent; an agent without iterations may have no arrays at all
+__global__ __launch_bounds__(256) void ddpg_wide_finish_many_kernel(const WidePlanRow *__restrict__ plan, int32_t n_agents) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_agents) return;
+    const int32_t n = plan[p].t.n_iters;
+    if (n <= 0) return;
+    int32_t *adam_t = plan[p].ap.d.adam_t;
+    adam_t[0] += n;
+    adam_t[1] += n;
+}
+
+size_t ddpg_wide_plan_bytes(int32_t n_agents) {
+    return n_agents < 1 ? 0 : (size_t)n_agents * (sizeof(WidePlanRow) + N_LISTS * sizeof(int32_t));
+}
+
+static int32_t *plan_list(void *plan, int32_t n_agents, int which) {
+    return reinterpret_cast<int32_t *>(static_cast<char *>(plan) + (size_t)n_agents * sizeof(WidePlanRow)) + (size_t)which * n_agents;
+}
+
+// Row `agent` of a plan from its item alone (already through the single-agent checks); an item without iterations leaves
+// a zeroed row that no list names.
+static int wide_plan_row(const ssc_ddpg_many_wide_item *item, int agent, WidePlanRow *row) {
+    memset(row, 0, sizeof *row);
+    if (item->n_iters <= 0) return SSC_OK;
+    const ssc_ddpg_desc *d = &item->ddpg;
+    char who[56];
+    snprintf(who, sizeof who, "ssc_ddpg_train_many_wide: agent %d", agent);
+    if (int rc = wide_batch_check(who, d)) return rc;
+    const size_t need = ddpg_wide_workspace_bytes(d);
+    SSC_REQUIRE(item->d_workspace != nullptr && item->workspace_bytes >= need,
+                "%s: workspace %zu < %zu bytes (ssc_ddpg_train_workspace_bytes)", who, item->workspace_bytes, need);
+    size_t lds = 0;
+    if (int rc = wide_build(d, &item->replay, WIDE_FULL, item->d_workspace, row->g, lds)) return rc;
+    row->g.batch_idx = item->d_batch_idx;
+    const int nb = wide_blocks(d);
+    wide_apply_args(d, item->d_workspace, nb, row->ap);
+    row->t.d_rms = item->d_rms; row->t.d_losses = item->d_losses;
+    row->t.n_iters = item->n_iters; row->t.n_blocks = nb;
+    row->t.apply_blocks = (row->ap.nA + row->ap.nC + 255) / 256;
+    row->t.lds_bytes = (int32_t)lds;
+    return SSC_OK;
+}
+
+int ddpg_wide_plan(const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, void *h_plan) {
+    WidePlanRow *rows = static_cast<WidePlanRow *>(h_plan);
+    int32_t count[N_LISTS] = {0, 0, 0, 0};
+    for (int which = 0; which < N_LISTS; ++which)
+        for (int p = 0; p < n_agents; ++p) plan_list(h_plan, n_agents, which)[p] = 0;     // (unused slots name a valid row)
+    for (int p = 0; p < n_agents; ++p) {
+        if (int rc = wide_plan_row(&h_items[p], p, &rows[p])) return rc;
+        if (h_items[p].n_iters <= 0) continue;
+        const int gl = h_items[p].d_rms != nullptr ? LIST_GRAD_RMS : LIST_GRAD_PLAIN;
+        const int al = wide_prepared(&h_items[p].ddpg) ? LIST_APPLY_PREPARED : LIST_APPLY_PLAIN;
+        plan_list(h_plan, n_agents, gl)[count[gl]++] = p;
+        plan_list(h_plan, n_agents, al)[count[al]++] = p;
+    }
+    return SSC_OK;
+}
+
+template <bool RMS> static int wide_many_lds_attr(size_t lds) {
+    if (lds <= 64 * 1024) return SSC_OK;
+    return check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_wide_grad_many_kernel<RMS>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                     "hipFuncSetAttribute(ddpg_wide_grad_many_kernel)");
+}
+
+// The launch sequence over a validated plan (h_plan: the host copy, read here for the geometry; d_plan: the device copy
+// the kernels read).  Iteration `it` of every agent that still has one runs in the same launches.
+int ddpg_train_wide_many(const void *h_plan, const void *d_plan, int32_t n_agents, hipStream_t stream) {
+    const WidePlanRow *rows = static_cast<const WidePlanRow *>(h_plan), *d_rows = static_cast<const WidePlanRow *>(d_plan);
+    struct Group { int count = 0, iters = 0, width = 0; size_t lds = 0; } grp[N_LISTS];
+    for (int p = 0; p < n_agents; ++p) {
+        const WideRowTail &t = rows[p].t;
+        if (t.n_iters <= 0) continue;
+        const bool prepared = wide_prepared(&rows[p].ap.d);
+        Group &gg = grp[t.d_rms != nullptr ? LIST_GRAD_RMS : LIST_GRAD_PLAIN], &ga = grp[prepared ? LIST_APPLY_PREPARED : LIST_APPLY_PLAIN];
+        ++gg.count; gg.iters = std::max(gg.iters, t.n_iters); gg.width = std::max(gg.width, t.n_blocks);
+        gg.lds = std::max(gg.lds, (size_t)t.lds_bytes);
+        ++ga.count; ga.iters = std::max(ga.iters, t.n_iters); ga.width = std::max(ga.width, t.apply_blocks);
+    }
+    const int iters = std::max(grp[LIST_GRAD_PLAIN].iters, grp[LIST_GRAD_RMS].iters);
+    if (iters == 0) return SSC_OK;
+    if (int rc = wide_many_lds_attr<false>(grp[LIST_GRAD_PLAIN].lds)) return rc;
+    if (int rc = wide_many_lds_attr<true>(grp[LIST_GRAD_RMS].lds)) return rc;
+    auto list = [&](int which) { return plan_list(const_cast<void *>(d_plan), n_agents, which); };
+    for (int it = 0; it < iters; ++it) {
+        const Group &gp = grp[LIST_GRAD_PLAIN], &gr = grp[LIST_GRAD_RMS], &ap = grp[LIST_APPLY_PLAIN], &aq = grp[LIST_APPLY_PREPARED];
+        if (it < gp.iters)
+            hipLaunchKernelGGL(ddpg_wide_grad_many_kernel<false>, dim3(gp.width, gp.count), dim3(kWThreads), gp.lds, stream, d_rows,
+                               list(LIST_GRAD_PLAIN), it);
+        if (it < gr.iters)
+            hipLaunchKernelGGL(ddpg_wide_grad_many_kernel<true>, dim3(gr.width, gr.count), dim3(kWThreads), gr.lds, stream, d_rows,
+                               list(LIST_GRAD_RMS), it);
+        if (it < aq.iters) {
+            hipLaunchKernelGGL(ddpg_wide_prepare_many_kernel, dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows, list(LIST_APPLY_PREPARED), it);
+            hipLaunchKernelGGL(ddpg_wide_apply_many_kernel<true>, dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows,
+                               list(LIST_APPLY_PREPARED), it);
+        }
+        if (it < ap.iters)
+            hipLaunchKernelGGL(ddpg_wide_apply_many_kernel<false>, dim3(ap.width, ap.count), dim3(256), 0, stream, d_rows,
+                               list(LIST_APPLY_PLAIN), it);
+    }
+    hipLaunchKernelGGL(ddpg_wide_finish_many_kernel, dim3(blocks_for(n_agents)), dim3(256), 0, stream, d_rows, n_agents);
+    return check_launch("ssc_ddpg_train_many_wide");
 }
 
 // ---- Pop-Art: four launches per iteration (target pass, renormalise, gradient pass, apply) -----------------------------

@@ -699,8 +699,11 @@ def rl_train_vec_ddpg_population(envs, agents, num_chunks, chunk_steps=256, repl
     and updates its observation statistics exactly as the single loop does, then ``population.train_from`` trains all
     agents.  Every pair's parameters, losses, Summary and final epsilon are bit for bit those of its own
     ``rl_train_vec_ddpg`` run with the same arguments.  ``seed``: one replay seed for all pairs or one per pair.
-    A population the one launch does not serve (see :class:`agents.DDPGPopulation`: another shape, Pop-Art, mixed
-    normalize_observations, ...) trains agent by agent.  The rollouts, epsilon decays, replay appends and statistics updates
+    A population the one launch does not serve is split by ``train_from`` itself (see :class:`agents.DDPGPopulation`): the
+    agents on the multi-workgroup kernels -- wider layers, other batch sizes, LayerNorm, critic_l2_reg, clip_norm -- train
+    together in grouped launches, those of the shipped shape in one-workgroup launches per (obs_dim, lastLayerTanh,
+    statistics) key, and only the rest (Pop-Art, a lone wide agent, ...) agent by agent; this loop needs, and has, no code
+    of its own for that.  The rollouts, epsilon decays, replay appends and statistics updates
     of a chunk are ONE launch each for all pairs too (``vec_env.VecEnvPopulation``, ``DecayScheduleGroup``,
     ``replay_buffer.DeviceReplayPopulation``, ``obs_rms.ObsRmsGroup``; two launches for the statistics), each falling back to
     the per-pair calls for a population it does not serve (mixed env kinds, another actor shape or precision, mixed
