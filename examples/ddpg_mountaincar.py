@@ -55,7 +55,8 @@ def main():
                          "multi-workgroup launches")
     ap.add_argument("--popart", action="store_true",
                     help="DDPG normalize_returns + enable_popart: the critic learns normalised returns, its output layer is "
-                         "rescaled with the running return statistics (Pop-Art)")
+                         "rescaled with the running return statistics (Pop-Art); with --population the Pop-Art agents, whatever "
+                         "their --hidden sizes, train together in grouped launches (ssc_ddpg_train_many_popart)")
     ap.add_argument("--stats-every", type=int, default=None, metavar="K",
                     help="the reference's training diagnostics (get_stats): vec: logged on the device every K chunks and printed "
                          "after the run; single: printed every K episodes")

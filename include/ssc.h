@@ -699,7 +699,8 @@ int ssc_ddpg_train_many(const ssc_ddpg_many_item *h_items, const ssc_ddpg_many_i
  * call.  Grid row p of every launch is an agent: 2 launches per iteration for the call (3 with critic_l2_reg /
  * clip_norm somewhere) instead of 2 or 3 per agent and iteration, and agent p's result -- the ten arrays, both Adam
  * counters, the losses -- is bit for bit what ssc_ddpg_train_ws / ssc_ddpg_train_ws_rms gives it alone (the kernels share
- * the per-agent arithmetic; nothing is summed across agents).  Pop-Art agents train alone (ssc_ddpg_train_ws_popart).
+ * the per-agent arithmetic; nothing is summed across agents).  Pop-Art agents have grouped launches of their own:
+ * ssc_ddpg_train_many_popart below.
  *
  * The item is ssc_ddpg_many_item plus the agent's own workspace, sized by ssc_ddpg_train_workspace_bytes and laid out as
  * the single-agent call lays it out.  d_batch_idx is [n_iters][batch_size] of THIS agent's batch size.
@@ -735,6 +736,49 @@ size_t ssc_ddpg_train_many_wide_plan_bytes(int32_t n_agents);   /* linear in n_a
 int ssc_ddpg_train_many_wide_plan(const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, void *h_plan, size_t plan_bytes);
 int ssc_ddpg_train_many_wide(const ssc_ddpg_many_wide_item *h_items, const void *h_plan, const void *d_plan, int32_t n_agents,
                              ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Pop-Art agents of any mix of shapes in grouped launches
+ * -------------------------------------------------------------------------------------
+ * What ssc_ddpg_train_many_wide is for ssc_ddpg_train_ws[_rms], for ssc_ddpg_train_ws_popart: every descriptor that call
+ * runs (any layer sizes, the shipped 64-32 x 64 included; batch 1..4096; LayerNorm, critic_l2_reg, clip_norm, statistics
+ * on some agents and not on others), all mixed in one call.  Grid row p of every launch is an agent: per iteration a
+ * target pass, ONE renormalise launch (a workgroup per agent), a gradient pass and the apply pass -- 4 launches for the
+ * call, 5 with critic_l2_reg / clip_norm somewhere; one more target and one more gradient launch where agents with and
+ * without observation statistics are mixed, one more apply launch where agents with and without critic_l2_reg /
+ * clip_norm are -- instead of 4 or 5 per agent and iteration.  Agent p's result -- the ten arrays, both Adam counters,
+ * the losses, its ret_rms block and its workspace -- is bit for bit what ssc_ddpg_train_ws_popart gives it alone; no
+ * atomics, fixed summation order.
+ *
+ * The item is ssc_ddpg_many_wide_item plus d_ret_rms.  The workspace is the agent's own, at least
+ * ssc_ddpg_train_popart_workspace_bytes(&ddpg) bytes, laid out as the single-agent call lays it out: after the call it
+ * holds that agent's last y, partials and (mu_old, sigma_old, mu_new, sigma_new).  The plan protocol is that of
+ * ssc_ddpg_train_many_wide (plan on the host, the caller copies it, validate again and launch); the plan's format is its
+ * own, ssc_ddpg_train_many_popart_plan_bytes(n_agents) bytes.
+ *
+ * Refused (SSC_EINVAL unless said otherwise), on the host before any HIP call and with the agent's index in
+ * ssc_last_error(): n_agents < 1 (above 65535: SSC_EUNSUPPORTED), a NULL array, an item that fails the single-agent
+ * checks, d_ret_rms == NULL on an item with iterations (a plain agent belongs in ssc_ddpg_train_many_wide), a workspace
+ * below ssc_ddpg_train_popart_workspace_bytes, a tile above the 160 KB of LDS (SSC_EUNSUPPORTED), two agents on one
+ * parameter / optimiser array, one workspace or one ret_rms block, a plan that no longer matches the items.  All
+ * n_iters == 0: SSC_OK without a launch; such an item may bring NULL arrays and only its shape is checked. */
+struct ssc_ddpg_many_popart_item {
+    ssc_ddpg_desc   ddpg;            /* this agent's arrays and hyper-parameters */
+    ssc_replay_view replay;          /* this agent's ring */
+    const int32_t  *d_batch_idx;     /* [n_iters][ddpg.batch_size] */
+    float          *d_losses;        /* [n_iters][2] or NULL */
+    const double   *d_rms;           /* normalize_observations block or NULL, per agent */
+    int32_t         n_iters;         /* >= 0, per agent; 0: the agent is left exactly as it is */
+    void           *d_workspace;     /* this agent's own, ssc_ddpg_train_popart_workspace_bytes(&ddpg) bytes */
+    size_t          workspace_bytes;
+    double         *d_ret_rms;       /* this agent's own [sum | sumsq | count], read and written */
+};
+typedef struct ssc_ddpg_many_popart_item ssc_ddpg_many_popart_item;
+
+size_t ssc_ddpg_train_many_popart_plan_bytes(int32_t n_agents);   /* linear in n_agents; 0 for n_agents < 1 */
+int ssc_ddpg_train_many_popart_plan(const ssc_ddpg_many_popart_item *h_items, int32_t n_agents, void *h_plan, size_t plan_bytes);
+int ssc_ddpg_train_many_popart(const ssc_ddpg_many_popart_item *h_items, const void *h_plan, const void *d_plan, int32_t n_agents,
+                               ssc_stream_t stream);
 
 /* Which learner ssc_ddpg_train (have_workspace = 0) / ssc_ddpg_train_ws[_rms] (have_workspace = 1; have_rms: a statistics
  * block comes with the call) runs a descriptor on, the SSC_DDPG_INTERPRETER / SSC_DDPG_WIDE switches of the environment

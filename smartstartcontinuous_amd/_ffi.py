@@ -155,6 +155,10 @@ class DdpgManyWideItem(Structure):
     _fields_ = DdpgManyItem._fields_ + [("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
+class DdpgManyPopartItem(Structure):
+    _fields_ = DdpgManyWideItem._fields_ + [("d_ret_rms", c_void_p)]
+
+
 # ssc_ddpg_learner_path's answers
 SSC_DDPG_PATH_FIXED, SSC_DDPG_PATH_FIXED_TILED, SSC_DDPG_PATH_INTERPRETER, SSC_DDPG_PATH_WIDE, SSC_DDPG_PATH_NEEDS_WORKSPACE = range(5)
 
@@ -218,7 +222,8 @@ STRUCTS = {
     "ssc_mpc_nav_state": MpcNavState, "ssc_smartstart_step": SmartStartStep, "ssc_critic_desc": CriticDesc,
     "ssc_ddpg_desc": DdpgDesc, "ssc_replay_view": ReplayView, "ssc_replay_ring": ReplayRing,
     "ssc_mlp_train_desc": MlpTrainDesc, "ssc_ddpg_many_item": DdpgManyItem,
-    "ssc_ddpg_many_wide_item": DdpgManyWideItem, "ssc_replay_sample_key": ReplaySampleKey,
+    "ssc_ddpg_many_wide_item": DdpgManyWideItem, "ssc_ddpg_many_popart_item": DdpgManyPopartItem,
+    "ssc_replay_sample_key": ReplaySampleKey,
     "ssc_pair_cursor": PairCursor, "ssc_rollout_many_item": RolloutManyItem, "ssc_replay_append_item": ReplayAppendItem,
     "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem, "ssc_ddpg_eval_many_item": DdpgEvalManyItem,
     "ssc_ddpg_stats_many_item": DdpgStatsManyItem, "ssc_param_noise_many_item": ParamNoiseManyItem,
@@ -289,6 +294,10 @@ _SIGNATURES = {
     "ssc_ddpg_train_many_wide_plan_bytes": (c_size_t, [c_int32]),
     "ssc_ddpg_train_many_wide_plan": (c_int, [c_void_p, c_int32, c_void_p, c_size_t]),
     "ssc_ddpg_train_many_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    # ... and of Pop-Art agents (the item carries the agent's ret_rms block; a plan format of its own)
+    "ssc_ddpg_train_many_popart_plan_bytes": (c_size_t, [c_int32]),
+    "ssc_ddpg_train_many_popart_plan": (c_int, [c_void_p, c_int32, c_void_p, c_size_t]),
+    "ssc_ddpg_train_many_popart": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "ssc_ddpg_learner_path": (c_int, [POINTER(DdpgDesc), c_int, c_int]),
     # the rest of a population chunk, one launch each: host items / cursors (validated) + the caller's device copies
     "ssc_rollout_many": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),

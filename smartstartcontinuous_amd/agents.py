@@ -817,9 +817,12 @@ POPULATION_FUSED_PARAM_NOISE = True
 
 # DDPGPopulation.train_from / train_on on a population its single launch does not serve: sub-populations in grouped
 # launches (True), or the per-agent calls one after the other (False: the yardstick of tools/exp_ddpg_population_wide.py).
-# Fewer than POPULATION_WIDE_MIN_GROUP agents on the multi-workgroup kernels train alone.
+# Fewer than POPULATION_WIDE_MIN_GROUP agents on the multi-workgroup kernels train alone, and so do fewer than
+# POPULATION_POPART_MIN_GROUP Pop-Art agents (the smallest group size at which the grouped launches were measured to win:
+# tools/exp_ddpg_population_popart.py, profiles/ddpg_population/popart.json).
 POPULATION_GROUPED_WIDE = True
 POPULATION_WIDE_MIN_GROUP = 2
+POPULATION_POPART_MIN_GROUP = 2
 
 
 class DDPGPopulation:
@@ -833,15 +836,18 @@ class DDPGPopulation:
     none, no array shared by two agents) and only while neither ``SSC_DDPG_INTERPRETER`` nor ``SSC_DDPG_WIDE`` is set.
     ``fused`` tells whether the last call went that way as a whole.
 
-    Any other population is split three ways (``ways``: one of ``"one_workgroup"``, ``"wide"``, ``"alone"`` per agent, for
-    the last call).  The agents ``ssc_ddpg_learner_path`` -- the library's own rule, the two switches included -- sends to
-    the multi-workgroup kernels (wider layers, other batch sizes, LayerNorm, critic_l2_reg, clip_norm, statistics on a
+    Any other population is split four ways (``ways``: one of ``"one_workgroup"``, ``"wide"``, ``"wide_popart"``,
+    ``"alone"`` per agent, for the last call).  The agents ``ssc_ddpg_learner_path`` -- the library's own rule, the two
+    switches included -- sends to the multi-workgroup kernels (wider layers, other batch sizes, LayerNorm, critic_l2_reg, clip_norm, statistics on a
     shape without a normalising one-workgroup build) train together in the grouped launches of
     ``ssc_ddpg_train_many_wide``: 2 launches per iteration for all of them (3 with critic_l2_reg / clip_norm) on a plan
     this object owns.  The agents of the shipped shape go through ``ssc_ddpg_train_many`` as child populations, one per
-    (obs_dim, lastLayerTanh, statistics) key.  Everything else -- Pop-Art, the step interpreter's shapes, the tiled 64-32
-    path, a lone wide agent, agents that share an array -- runs ``agent.train_from`` / ``agent.train_on`` as before, and so
-    does every agent when ``POPULATION_GROUPED_WIDE`` is False.
+    (obs_dim, lastLayerTanh, statistics) key.  The Pop-Art agents (``normalize_returns`` with ``enable_popart``), of any
+    shape, train together in the grouped launches of ``ssc_ddpg_train_many_popart``: 4 launches per iteration for all of
+    them (5 with critic_l2_reg / clip_norm), each agent on its own ``ret_rms`` block and workspace.  Everything else -- the
+    step interpreter's shapes, the tiled 64-32 path, a lone wide agent, fewer Pop-Art agents than
+    ``POPULATION_POPART_MIN_GROUP``, agents that share an array -- runs ``agent.train_from`` / ``agent.train_on`` as before,
+    and so does every agent when ``POPULATION_GROUPED_WIDE`` is False.
 
     Index and loss tensors and the pinned-host and device copies of the launch descriptors stay with the population and
     are rebuilt only when a pointer, an iteration count or a ring changes: in steady state a call uploads the P sampling
@@ -960,8 +966,8 @@ class DDPGPopulation:
         ag = self.agents
         ptrs = [t.data_ptr() for a in ag for t in self._arrays(a)]
         rms = [None if a.obs_rms is None else a._rms_block().data_ptr() for a in ag]
-        switches = tuple(os.environ.get(k) for k in ("SSC_DDPG_INTERPRETER", "SSC_DDPG_WIDE")) + (POPULATION_GROUPED_WIDE, POPULATION_WIDE_MIN_GROUP)
-        sig = (switches, tuple(ptrs), tuple(rms), tuple(n),
+        switches = tuple(os.environ.get(k) for k in ("SSC_DDPG_INTERPRETER", "SSC_DDPG_WIDE")) + (POPULATION_GROUPED_WIDE, POPULATION_WIDE_MIN_GROUP, POPULATION_POPART_MIN_GROUP)
+        sig = (switches, tuple(ptrs), tuple(rms), tuple(None if a.ret_rms is None else a.ret_rms.block.data_ptr() for a in ag), tuple(n),
                tuple((v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(), v[4].data_ptr(), v[0].shape[0]) for v in views),
                None if batch_idx is None else tuple(idx.data_ptr() if k > 0 else 0 for idx, k in zip(batch_idx, n)),
                tuple((a.gamma, a.tau, a.actor_lr, a.critic_lr, a.obs_dim, a.lastLayerTanh, a.batch_size, a.critic_l2_reg, a.clip_norm,
@@ -1018,29 +1024,39 @@ class DDPGPopulation:
         if POPULATION_GROUPED_WIDE and len(set(ptrs)) == len(ptrs):
             for p, a in enumerate(ag):
                 if a.popart:
+                    ways[p] = "wide_popart"
                     continue
                 path = self.lib.ssc_ddpg_learner_path(ctypes.byref(a.ddpg_desc()), 1, int(rms[p] is not None))
                 ways[p] = {_ffi.SSC_DDPG_PATH_WIDE: "wide", _ffi.SSC_DDPG_PATH_FIXED: "one_workgroup"}.get(path, "alone")
             if ways.count("wide") < POPULATION_WIDE_MIN_GROUP:
                 ways = ["alone" if w == "wide" else w for w in ways]
+            if ways.count("wide_popart") < POPULATION_POPART_MIN_GROUP:
+                ways = ["alone" if w == "wide_popart" else w for w in ways]
         self.ways = tuple(ways)
         children = {}
         for p, a in enumerate(ag):
             if ways[p] == "one_workgroup":
                 children.setdefault((a.obs_dim, bool(a.lastLayerTanh), rms[p] is not None), []).append(p)
-        wide = [p for p in range(P) if ways[p] == "wide"]
+        wide, pop = ([p for p in range(P) if ways[p] == w] for w in ("wide", "wide_popart"))
         self._groups = dict(alone=[p for p in range(P) if ways[p] == "alone"],
                             children=[(ps, DDPGPopulation([ag[p] for p in ps])) for ps in children.values()],
-                            wide=self._wide_state(wide, views, n, batch_idx, rms) if wide else None)
+                            wide=self._wide_state(wide, views, n, batch_idx, rms) if wide else None,
+                            wide_popart=self._wide_state(pop, views, n, batch_idx, rms, popart=True) if pop else None)
 
-    def _wide_state(self, wide, views, n, batch_idx, rms):
+    def _wide_state(self, wide, views, n, batch_idx, rms, popart=False):
         """Items, workspaces, index and loss tensors and the plan (pinned host copy, device copy) of the agents on the
-        grouped multi-workgroup launches; kept until the call's signature changes."""
-        ag, W = self.agents, len(wide)
-        st = dict(agents=wide, n=[n[p] for p in wide])
+        grouped multi-workgroup launches -- the plain ones or, ``popart``, the Pop-Art ones; kept until the call's
+        signature changes."""
+        ag, W, lib = self.agents, len(wide), self.lib
+        item_t, ws_bytes, plan_bytes, plan, train = (
+            (_ffi.DdpgManyPopartItem, lib.ssc_ddpg_train_popart_workspace_bytes, lib.ssc_ddpg_train_many_popart_plan_bytes,
+             lib.ssc_ddpg_train_many_popart_plan, lib.ssc_ddpg_train_many_popart) if popart else
+            (_ffi.DdpgManyWideItem, lib.ssc_ddpg_train_workspace_bytes, lib.ssc_ddpg_train_many_wide_plan_bytes,
+             lib.ssc_ddpg_train_many_wide_plan, lib.ssc_ddpg_train_many_wide))
+        st = dict(agents=wide, n=[n[p] for p in wide], train=train)
         with torch.cuda.device(self.device):
             st["losses"] = torch.empty((sum(st["n"]), 2), dtype=torch.float32, device=self.device)
-            items = st["items"] = (_ffi.DdpgManyWideItem * W)()
+            items = st["items"] = (item_t * W)()
             off, st["rows"], st["idx"] = 0, [], []
             # our own draw: one launch for all rings where every agent has the same batch size <= 64 (the sampler's one-wave
             # kernel; rows [slot][n_max][B], agent p reads its first n[p] batches), else one launch per ring
@@ -1058,7 +1074,9 @@ class DDPGPopulation:
                 it.ddpg = d = a.ddpg_desc()
                 it.replay = _ffi.ReplayView(*(x.data_ptr() for x in v), v[0].shape[0])
                 it.n_iters, it.d_rms = k, rms[p]
-                need = int(self.lib.ssc_ddpg_train_workspace_bytes(ctypes.byref(d)))      # the agent's own, as train_on keeps it
+                if popart:
+                    it.d_ret_rms = a.ret_rms.block.data_ptr()
+                need = int(ws_bytes(ctypes.byref(d)))      # the agent's own, as train_on keeps it
                 ws = getattr(a, "_train_ws", None)
                 if ws is None or ws.numel() < need:
                     ws = a._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -1072,11 +1090,11 @@ class DDPGPopulation:
                     it.d_losses, it.d_batch_idx = st["rows"][-1].data_ptr(), idx.data_ptr()
                 st["idx"].append(idx)
                 off += k
-            nbytes = int(self.lib.ssc_ddpg_train_many_wide_plan_bytes(W))
+            nbytes = int(plan_bytes(W))
             if self._items_event is not None:
                 self._items_event.synchronize()
             st["h_plan"] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-            _ffi.check(self.lib.ssc_ddpg_train_many_wide_plan(ctypes.addressof(items), W, st["h_plan"].data_ptr(), nbytes))
+            _ffi.check(plan(ctypes.addressof(items), W, st["h_plan"].data_ptr(), nbytes))
             st["d_plan"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             st["d_plan"].copy_(st["h_plan"], non_blocking=True)
             self._items_event = torch.cuda.Event()
@@ -1096,33 +1114,38 @@ class DDPGPopulation:
                    else child._train_on([views[p] for p in ps], [batch_idx[p] for p in ps], k, copy))
             for p, rows in zip(ps, got):
                 out[p] = rows
-        st = g["wide"]
-        if st is not None and any(st["n"]):
-            with torch.cuda.device(self.device):
-                if batch_idx is None and st["keys"] is not None:
-                    if self._keys_event is not None:
-                        self._keys_event.synchronize()           # the last upload has left the pinned keys
-                    for key, p in zip(st["keys"], st["active"]):
-                        key.seed, key.counter0, key.size = replays[p].take_sample_key(n[p], st["B"])
-                    st["d_keys"].copy_(st["h_keys"], non_blocking=True)
-                    self._keys_event = torch.cuda.Event()
-                    self._keys_event.record()
-                    _ffi.check(self.lib.ssc_replay_sample_many(st["h_keys"].data_ptr(), st["d_keys"].data_ptr(), len(st["active"]),
-                                                               st["n_max"], st["B"], _ffi.ptr(st["idx_all"]), _ffi.stream(self.device)))
-                elif batch_idx is None:     # every ring draws under its own key, as its sample_indices would
-                    for p, k, idx in zip(st["agents"], st["n"], st["idx"]):
-                        if k > 0:
-                            B = ag[p].batch_size
-                            seed, counter0, size = replays[p].take_sample_key(k, B)
-                            _ffi.check(self.lib.ssc_replay_sample(seed, counter0, size, k, B, _ffi.ptr(idx), _ffi.stream(self.device)))
-                _ffi.check(self.lib.ssc_ddpg_train_many_wide(ctypes.addressof(st["items"]), st["h_plan"].data_ptr(), st["d_plan"].data_ptr(),
-                                                             len(st["agents"]), _ffi.stream(self.device)))
-                block = st["losses"].clone() if copy else st["losses"]
-            off = 0
-            for p, k in zip(st["agents"], st["n"]):
-                out[p] = block[off:off + k] if k > 0 else None
-                off += k
+        for st in (g["wide"], g["wide_popart"]):
+            if st is not None and any(st["n"]):
+                self._train_grouped(st, replays, batch_idx, n, copy, out)
         return out
+
+    def _train_grouped(self, st, replays, batch_idx, n, copy, out):
+        """one grouped call (plain or Pop-Art) on its kept state; fills the agents' slots of ``out``"""
+        ag = self.agents
+        with torch.cuda.device(self.device):
+            if batch_idx is None and st["keys"] is not None:
+                if self._keys_event is not None:
+                    self._keys_event.synchronize()           # the last upload has left the pinned keys
+                for key, p in zip(st["keys"], st["active"]):
+                    key.seed, key.counter0, key.size = replays[p].take_sample_key(n[p], st["B"])
+                st["d_keys"].copy_(st["h_keys"], non_blocking=True)
+                self._keys_event = torch.cuda.Event()
+                self._keys_event.record()
+                _ffi.check(self.lib.ssc_replay_sample_many(st["h_keys"].data_ptr(), st["d_keys"].data_ptr(), len(st["active"]),
+                                                           st["n_max"], st["B"], _ffi.ptr(st["idx_all"]), _ffi.stream(self.device)))
+            elif batch_idx is None:     # every ring draws under its own key, as its sample_indices would
+                for p, k, idx in zip(st["agents"], st["n"], st["idx"]):
+                    if k > 0:
+                        B = ag[p].batch_size
+                        seed, counter0, size = replays[p].take_sample_key(k, B)
+                        _ffi.check(self.lib.ssc_replay_sample(seed, counter0, size, k, B, _ffi.ptr(idx), _ffi.stream(self.device)))
+            _ffi.check(st["train"](ctypes.addressof(st["items"]), st["h_plan"].data_ptr(), st["d_plan"].data_ptr(), len(st["agents"]),
+                                   _ffi.stream(self.device)))
+            block = st["losses"].clone() if copy else st["losses"]
+        off = 0
+        for p, k in zip(st["agents"], st["n"]):
+            out[p] = block[off:off + k] if k > 0 else None
+            off += k
 
     def _launch(self, copy):
         st = self._state

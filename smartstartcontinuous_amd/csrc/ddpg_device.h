@@ -106,6 +106,11 @@ int ddpg_train_wide(const ssc_ddpg_desc *d, const ssc_replay_view *rp, const int
 size_t ddpg_wide_plan_bytes(int32_t n_agents);
 int ddpg_wide_plan(const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, void *h_plan);
 int ddpg_train_wide_many(const void *h_plan, const void *d_plan, int32_t n_agents, hipStream_t stream);
+// ... and the Pop-Art agents' grouped launches (ssc_ddpg_train_many_popart): the same protocol on a plan format of its own,
+// [n_agents rows | five lists]
+size_t ddpg_pop_plan_bytes(int32_t n_agents);
+int ddpg_pop_plan(const ssc_ddpg_many_popart_item *h_items, int32_t n_agents, void *h_plan);
+int ddpg_train_pop_many(const void *h_plan, const void *d_plan, int32_t n_agents, hipStream_t stream);
 // Pop-Art (normalize_returns + enable_popart): every shape runs the multi-workgroup kernels, four launches per iteration;
 // d_ret_rms: the one-column RunningMeanStd block of the returns, read and written
 size_t ddpg_popart_workspace_bytes(const ssc_ddpg_desc *d);

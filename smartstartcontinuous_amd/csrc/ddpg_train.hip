@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -849,7 +850,9 @@ extern "C" int ssc_ddpg_learner_path(const ssc_ddpg_desc *d, int have_workspace,
 
 // A population on the multi-workgroup kernels, grid row = agent (ddpg_train_wide.hip).  The walk both entry points share:
 // every refusal that needs no plan.  *any: some agent has iterations to run.
-static int many_wide_check(const char *fn, const ssc_ddpg_many_wide_item *h_items, int32_t n_agents, bool *any) {
+// Item: ssc_ddpg_many_wide_item, or ssc_ddpg_many_popart_item (any path's shape; a ret_rms block of its own).
+template <class Item> static int many_wide_check(const char *fn, const Item *h_items, int32_t n_agents, bool *any) {
+    constexpr bool kPop = std::is_same_v<Item, ssc_ddpg_many_popart_item>;
     static const char *const kPath[] = {"the one-workgroup 64-32 kernel", "the tiled 64-32 kernel", "the step interpreter",
                                         "the multi-workgroup kernels", "no learner without a workspace"};
     SSC_REQUIRE(n_agents >= 1, "%s: n_agents %d < 1", fn, n_agents);
@@ -857,19 +860,23 @@ static int many_wide_check(const char *fn, const ssc_ddpg_many_wide_item *h_item
     SSC_REQUIRE(h_items != nullptr, "%s: NULL item array", fn);
     *any = false;
     std::vector<std::pair<const void *, int>> owned;   // (array, agent) of every parameter / optimiser array and workspace
-    owned.reserve((size_t)n_agents * 10);
+    owned.reserve((size_t)n_agents * 11);
     for (int p = 0; p < n_agents; ++p) {
-        const ssc_ddpg_many_wide_item &it = h_items[p];
+        const Item &it = h_items[p];
         const ssc_ddpg_desc *d = &it.ddpg;
-        char who[56];
+        char who[64];
         snprintf(who, sizeof who, "%s: agent %d", fn, p);
         const int rc = ddpg_check(who, d, &it.replay, it.d_batch_idx, it.n_iters);
         if (rc != DDPG_GO && rc != SSC_OK) return rc;
         if (it.n_iters > 0) {
-            const DdpgPath path = ddpg_path_now(d, true, it.d_rms != nullptr);
-            if (path != DDPG_WIDE)
-                return set_error(SSC_EUNSUPPORTED, "%s: ssc_ddpg_train_ws runs this agent on %s, not on the multi-workgroup kernels "
-                                                   "(ssc_ddpg_learner_path); train it with ssc_ddpg_train_many or alone", who, kPath[path]);
+            if constexpr (kPop) {
+                SSC_REQUIRE(it.d_ret_rms != nullptr, "%s: d_ret_rms is NULL (an agent without Pop-Art trains in ssc_ddpg_train_many_wide)", who);
+            } else {
+                const DdpgPath path = ddpg_path_now(d, true, it.d_rms != nullptr);
+                if (path != DDPG_WIDE)
+                    return set_error(SSC_EUNSUPPORTED, "%s: ssc_ddpg_train_ws runs this agent on %s, not on the multi-workgroup kernels "
+                                                       "(ssc_ddpg_learner_path); train it with ssc_ddpg_train_many or alone", who, kPath[path]);
+            }
             *any = true;
         }
         for (const void *a : {(const void *)d->actor, (const void *)d->critic, (const void *)d->target_actor,
@@ -877,11 +884,13 @@ static int many_wide_check(const char *fn, const ssc_ddpg_many_wide_item *h_item
                               (const void *)d->adam_m_critic, (const void *)d->adam_v_critic, (const void *)d->adam_t,
                               (const void *)it.d_workspace})
             if (a != nullptr) owned.emplace_back(a, p);   // (NULL: an agent with n_iters == 0 may bring none)
+        if constexpr (kPop)
+            if (it.d_ret_rms != nullptr) owned.emplace_back((const void *)it.d_ret_rms, p);
     }
     std::sort(owned.begin(), owned.end());
     for (size_t k = 1; k < owned.size(); ++k)
-        SSC_REQUIRE(owned[k].first != owned[k - 1].first, "%s: agents %d and %d share a parameter / optimiser array or a workspace", fn,
-                    owned[k - 1].second, owned[k].second);
+        SSC_REQUIRE(owned[k].first != owned[k - 1].first, "%s: agents %d and %d share a parameter / optimiser array%s", fn,
+                    owned[k - 1].second, owned[k].second, kPop ? ", a workspace or a ret_rms block" : " or a workspace");
     return SSC_OK;
 }
 
@@ -911,6 +920,34 @@ extern "C" int ssc_ddpg_train_many_wide(const ssc_ddpg_many_wide_item *h_items, 
                 "ssc_ddpg_train_many_wide_plan)", fn);
     if (!any) return SSC_OK;
     return ddpg_train_wide_many(h_plan, d_plan, n_agents, as_stream(stream));
+}
+
+// Pop-Art agents in grouped launches: the same protocol on a plan format of its own (ddpg_train_wide.hip)
+extern "C" size_t ssc_ddpg_train_many_popart_plan_bytes(int32_t n_agents) { return ddpg_pop_plan_bytes(n_agents); }
+
+extern "C" int ssc_ddpg_train_many_popart_plan(const ssc_ddpg_many_popart_item *h_items, int32_t n_agents, void *h_plan, size_t plan_bytes) {
+    const char *fn = "ssc_ddpg_train_many_popart_plan";
+    bool any = false;
+    if (int rc = many_wide_check(fn, h_items, n_agents, &any)) return rc;
+    SSC_REQUIRE(h_plan != nullptr, "%s: NULL plan", fn);
+    SSC_REQUIRE(plan_bytes >= ddpg_pop_plan_bytes(n_agents), "%s: plan %zu < %zu bytes (ssc_ddpg_train_many_popart_plan_bytes)", fn,
+                plan_bytes, ddpg_pop_plan_bytes(n_agents));
+    return ddpg_pop_plan(h_items, n_agents, h_plan);
+}
+
+extern "C" int ssc_ddpg_train_many_popart(const ssc_ddpg_many_popart_item *h_items, const void *h_plan, const void *d_plan,
+                                          int32_t n_agents, ssc_stream_t stream) {
+    const char *fn = "ssc_ddpg_train_many_popart";
+    bool any = false;
+    if (int rc = many_wide_check(fn, h_items, n_agents, &any)) return rc;
+    SSC_REQUIRE(h_plan != nullptr && d_plan != nullptr, "%s: NULL plan", fn);
+    std::vector<uint64_t> fresh((ddpg_pop_plan_bytes(n_agents) + 7) / 8);
+    if (int rc = ddpg_pop_plan(h_items, n_agents, fresh.data())) return rc;
+    SSC_REQUIRE(memcmp(fresh.data(), h_plan, ddpg_pop_plan_bytes(n_agents)) == 0,
+                "%s: the plan does not match the items (a pointer, a shape or an iteration count changed since "
+                "ssc_ddpg_train_many_popart_plan)", fn);
+    if (!any) return SSC_OK;
+    return ddpg_train_pop_many(h_plan, d_plan, n_agents, as_stream(stream));
 }
 
 extern "C" size_t ssc_ddpg_train_workspace_bytes(const ssc_ddpg_desc *d) {

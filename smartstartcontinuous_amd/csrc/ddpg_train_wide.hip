@@ -29,7 +29,8 @@
 // Pop-Art (normalize_returns + enable_popart, ddpg_editted.py:201-217, 291-301) is four launches per iteration on the same
 // pieces: the grad kernel built as a target pass (target networks only; writes y and per-workgroup sums), a one-workgroup
 // renormalise kernel (statistics update, rescaling of both critics' output layers), the grad kernel built without the
-// target levels (normalised TD error), and the unchanged apply pass -- ddpg_train_wide_popart below.
+// target levels (normalised TD error), and the unchanged apply pass -- ddpg_train_wide_popart below.  A population of Pop-Art
+// agents runs the same four launches with a grid row per agent (ssc_ddpg_train_many_popart, at the end of the file).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -1092,50 +1093,58 @@ struct WidePlanRow {
 static_assert(sizeof(WidePlanRow) % 8 == 0 && sizeof(WideHead) % 4 == 0 && sizeof(WideRowTail) % 4 == 0, "dword-sized, pointer-aligned rows");
 enum : int { LIST_GRAD_PLAIN = 0, LIST_GRAD_RMS, LIST_APPLY_PLAIN, LIST_APPLY_PREPARED, N_LISTS };
 
-template <bool RMS>
-__global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_many_kernel(const WidePlanRow *__restrict__ plan, const int32_t *__restrict__ list,
-                                                                         int32_t it) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+// The start of a grouped gradient workgroup: one round trip for the head and the tail (every lane the same address; kept
+// in scalar registers) and this thread's share of the tables -- the one vector load per thread of the single-agent
+// kernel, from global memory.  false: the whole workgroup leaves, before the first barrier.
+__device__ __forceinline__ bool wide_many_enter(const WideArgs *g, const WideRowTail &t, int32_t it, float *lds, WideHead &a) {
     const int tid = threadIdx.x;
-    const WidePlanRow *row = plan + list[blockIdx.y];
-    // one round trip: the head and the tail (every lane the same address; kept in scalar registers) and this thread's
-    // share of the tables -- the one vector load per thread of the single-agent kernel, from global memory
-    const uint32_t *src = reinterpret_cast<const uint32_t *>(&row->g.tab);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&g->tab);
     static_assert(kTabWords <= 2 * kWThreads, "two dwords per thread copy the tables");
     const uint32_t w0 = src[min(tid, kTabWords - 1)], w1 = src[min(tid + kWThreads, kTabWords - 1)];
-    const WideRowTail t = lds_uniform(&row->t);
-    WideHead a = lds_uniform(static_cast<const WideHead *>(&row->g));
-    if ((int)blockIdx.x >= t.n_blocks || it >= t.n_iters) return;     // the whole workgroup, before the first barrier
+    a = lds_uniform(static_cast<const WideHead *>(g));
+    if ((int)blockIdx.x >= t.n_blocks || it >= t.n_iters) return false;
     a.batch_idx += (int64_t)it * a.batch;
     uint32_t *dst = reinterpret_cast<uint32_t *>(lds + a.off_tab);
     if (tid < kTabWords) dst[tid] = w0;
     if (tid + kWThreads < kTabWords) dst[tid + kWThreads] = w1;
     __syncthreads();
+    return true;
+}
+
+template <bool RMS>
+__global__ __launch_bounds__(kWThreads) void ddpg_wide_grad_many_kernel(const WidePlanRow *__restrict__ plan, const int32_t *__restrict__ list,
+                                                                         int32_t it) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const WidePlanRow *row = plan + list[blockIdx.y];
+    const WideRowTail t = lds_uniform(&row->t);
+    WideHead a;
+    if (!wide_many_enter(&row->g, t, it, lds, a)) return;
     if constexpr (RMS) wide_grad_body(a, lds, 0, t.d_rms);
     else wide_grad_body(a, lds, 0);
 }
 
-__global__ __launch_bounds__(256) void ddpg_wide_prepare_many_kernel(const WidePlanRow *__restrict__ plan, const int32_t *__restrict__ list,
-                                                                      int32_t it) {
+// (Row: WidePlanRow, or the Pop-Art row that extends it)
+template <class Row>
+__global__ __launch_bounds__(256) void ddpg_wide_prepare_many_kernel(const Row *__restrict__ plan, const int32_t *__restrict__ list, int32_t it) {
     __shared__ float red[4];
-    const WidePlanRow *row = plan + list[blockIdx.y];
+    const Row *row = plan + list[blockIdx.y];
     if ((int)blockIdx.x >= row->t.apply_blocks || it >= row->t.n_iters) return;
     wide_prepare_body(row->ap, red);
 }
 
-template <bool PREPARED>
-__global__ __launch_bounds__(256) void ddpg_wide_apply_many_kernel(const WidePlanRow *__restrict__ plan, const int32_t *__restrict__ list,
-                                                                    int32_t it) {
+template <bool PREPARED, class Row>
+__global__ __launch_bounds__(256) void ddpg_wide_apply_many_kernel(const Row *__restrict__ plan, const int32_t *__restrict__ list, int32_t it) {
     __shared__ AdamCfg cfg[2];
     __shared__ float red[4];
-    const WidePlanRow *row = plan + list[blockIdx.y];
+    const Row *row = plan + list[blockIdx.y];
     if ((int)blockIdx.x >= row->t.apply_blocks || it >= row->t.n_iters) return;
     float *losses = row->t.d_losses;
     wide_apply_body<PREPARED>(row->ap, it, losses != nullptr ? losses + 2 * it : nullptr, cfg, red);
 }
 
 // one thread per agent; an agent without iterations may have no arrays at all
-__global__ __launch_bounds__(256) void ddpg_wide_finish_many_kernel(const WidePlanRow *__restrict__ plan, int32_t n_agents) {
+template <class Row>
+__global__ __launch_bounds__(256) void ddpg_wide_finish_many_kernel(const Row *__restrict__ plan, int32_t n_agents) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n_agents) return;
     const int32_t n = plan[p].t.n_iters;
@@ -1149,8 +1158,8 @@ size_t ddpg_wide_plan_bytes(int32_t n_agents) {
     return n_agents < 1 ? 0 : (size_t)n_agents * (sizeof(WidePlanRow) + N_LISTS * sizeof(int32_t));
 }
 
-static int32_t *plan_list(void *plan, int32_t n_agents, int which) {
-    return reinterpret_cast<int32_t *>(static_cast<char *>(plan) + (size_t)n_agents * sizeof(WidePlanRow)) + (size_t)which * n_agents;
+static int32_t *plan_list(void *plan, int32_t n_agents, int which, size_t row_bytes = sizeof(WidePlanRow)) {
+    return reinterpret_cast<int32_t *>(static_cast<char *>(plan) + (size_t)n_agents * row_bytes) + (size_t)which * n_agents;
 }
 
 // Row `agent` of a plan from its item alone (already through the single-agent checks); an item without iterations leaves
@@ -1228,15 +1237,16 @@ int ddpg_train_wide_many(const void *h_plan, const void *d_plan, int32_t n_agent
             hipLaunchKernelGGL(ddpg_wide_grad_many_kernel<true>, dim3(gr.width, gr.count), dim3(kWThreads), gr.lds, stream, d_rows,
                                list(LIST_GRAD_RMS), it);
         if (it < aq.iters) {
-            hipLaunchKernelGGL(ddpg_wide_prepare_many_kernel, dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows, list(LIST_APPLY_PREPARED), it);
-            hipLaunchKernelGGL(ddpg_wide_apply_many_kernel<true>, dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows,
+            hipLaunchKernelGGL(ddpg_wide_prepare_many_kernel<WidePlanRow>, dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows,
+                               list(LIST_APPLY_PREPARED), it);
+            hipLaunchKernelGGL((ddpg_wide_apply_many_kernel<true, WidePlanRow>), dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows,
                                list(LIST_APPLY_PREPARED), it);
         }
         if (it < ap.iters)
-            hipLaunchKernelGGL(ddpg_wide_apply_many_kernel<false>, dim3(ap.width, ap.count), dim3(256), 0, stream, d_rows,
+            hipLaunchKernelGGL((ddpg_wide_apply_many_kernel<false, WidePlanRow>), dim3(ap.width, ap.count), dim3(256), 0, stream, d_rows,
                                list(LIST_APPLY_PLAIN), it);
     }
-    hipLaunchKernelGGL(ddpg_wide_finish_many_kernel, dim3(blocks_for(n_agents)), dim3(256), 0, stream, d_rows, n_agents);
+    hipLaunchKernelGGL(ddpg_wide_finish_many_kernel<WidePlanRow>, dim3(blocks_for(n_agents)), dim3(256), 0, stream, d_rows, n_agents);
     return check_launch("ssc_ddpg_train_many_wide");
 }
 
@@ -1250,11 +1260,10 @@ struct RenormArgs {
 };
 
 // ret_rms.update(target_Q) (:297), then the rescaling of both output layers that keeps sigma q + mu where it was
-// (setup_popart, :201-217).  One workgroup; thread 0 merges the partials in workgroup order.
-__global__ __launch_bounds__(256) void ddpg_popart_renorm_kernel(RenormArgs a) {
+// (setup_popart, :201-217).  One workgroup of 256 threads; thread 0 merges the partials in workgroup order.  sp: [2 * 256]
+// doubles, sc: [4] floats of LDS.  Shared by the single-agent kernel and the grouped one.
+__device__ __forceinline__ void popart_renorm_body(const RenormArgs &a, double *sp, float *sc) {
 #pragma clang fp contract(off)
-    __shared__ double sp[2 * 256];
-    __shared__ float sc[4];
     const int tid = threadIdx.x;
     for (int i = tid; i < 2 * a.n_part; i += 256) sp[i] = a.part[i];
     __syncthreads();
@@ -1286,6 +1295,12 @@ __global__ __launch_bounds__(256) void ddpg_popart_renorm_kernel(RenormArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void ddpg_popart_renorm_kernel(RenormArgs a) {
+    __shared__ double sp[2 * 256];
+    __shared__ float sc[4];
+    popart_renorm_body(a, sp, sc);
+}
+
 // [the plain step's workspace | y [batch] | partials [blocks][2] f64 | the four scalars]: the one layout both the size
 // query and the launcher use
 struct PopLayout { float *y; double *part; float *scal; size_t bytes; };
@@ -1295,11 +1310,21 @@ static PopLayout popart_layout(const ssc_ddpg_desc *d, void *d_workspace) {
     const size_t o_y = up(ddpg_wide_workspace_bytes(d));
     const size_t o_part = o_y + up((size_t)d->batch_size * sizeof(float));
     const size_t o_scal = o_part + up((size_t)wide_blocks(d) * 2 * sizeof(double));
+    if (base == nullptr) return PopLayout{nullptr, nullptr, nullptr, o_scal + 256};     // (the size query; a refused item)
     return PopLayout{reinterpret_cast<float *>(base + o_y), reinterpret_cast<double *>(base + o_part),
                      reinterpret_cast<float *>(base + o_scal), o_scal + 256};
 }
 
 size_t ddpg_popart_workspace_bytes(const ssc_ddpg_desc *d) { return popart_layout(d, nullptr).bytes; }
+
+// (field by field into a zeroed `rn`: a plan row is compared byte by byte, padding included)
+static void popart_renorm_args(const ssc_ddpg_desc *d, const PopLayout &L, double *d_ret_rms, RenormArgs &rn) {
+    const DdpgNet C = ddpg_nets(d).C;
+    rn.ret_rms = d_ret_rms; rn.part = L.part; rn.scal = L.scal;
+    rn.cW3 = d->critic + C.oW3(); rn.cb3 = d->critic + C.ob3();
+    rn.tW3 = d->target_critic + C.oW3(); rn.tb3 = d->target_critic + C.ob3();
+    rn.n_part = wide_blocks(d); rn.batch = d->batch_size; rn.h2 = C.h2;
+}
 
 template <class... Rms>
 static int wide_popart_iters(const ssc_ddpg_desc *d, WideArgs &gt, WideArgs &gg, size_t lds, const RenormArgs &rn, const PopLayout &L,
@@ -1332,14 +1357,163 @@ int ddpg_train_wide_popart(const ssc_ddpg_desc *d, const ssc_replay_view *rp, co
     size_t lds = 0;
     if (int rc = wide_build(d, rp, WIDE_POP_TARGET, d_workspace, gt, lds)) return rc;
     if (int rc = wide_build(d, rp, WIDE_POP_GRAD, d_workspace, gg, lds)) return rc;
-    const DdpgNet C = ddpg_nets(d).C;
     RenormArgs rn{};
-    rn.ret_rms = d_ret_rms; rn.part = L.part; rn.scal = L.scal;
-    rn.cW3 = d->critic + C.oW3(); rn.cb3 = d->critic + C.ob3();
-    rn.tW3 = d->target_critic + C.oW3(); rn.tb3 = d->target_critic + C.ob3();
-    rn.n_part = wide_blocks(d); rn.batch = d->batch_size; rn.h2 = C.h2;
+    popart_renorm_args(d, L, d_ret_rms, rn);
     if (d_rms != nullptr) return wide_popart_iters(d, gt, gg, lds, rn, L, d_batch_idx, n_iters, d_losses, d_workspace, stream, d_rms);
     return wide_popart_iters(d, gt, gg, lds, rn, L, d_batch_idx, n_iters, d_losses, d_workspace, stream);
+}
+
+// ---- Pop-Art agents in grouped launches (ssc_ddpg_train_many_popart): grid row blockIdx.y is an agent -------------------
+// The plan of the plain grouped launches with a longer row: the WidePlanRow part holds the TARGET pass's tables (g), the
+// apply arguments and the tail, so that the prepare / apply / finish kernels run on it as they are; behind it the
+// gradient pass's tables and what the single-agent launches get as RenormArgs / PopTarget / PopGrad.  Five lists: the four
+// of the plain plan (the target and the gradient pass share the statistics / no-statistics lists) and every agent with
+// iterations, for the renormalise launch.
+struct PopPlanRow : WidePlanRow {
+    WideArgs gg;               // WIDE_POP_GRAD (g: WIDE_POP_TARGET); batch_idx: iteration 0's rows
+    RenormArgs rn;
+    PopTarget pt;
+    PopGrad pg;
+};
+static_assert(sizeof(PopPlanRow) % 8 == 0 && sizeof(RenormArgs) % 4 == 0 && sizeof(PopTarget) % 4 == 0 && sizeof(PopGrad) % 4 == 0,
+              "dword-sized, pointer-aligned rows");
+enum : int { LIST_POP_ALL = N_LISTS, N_POP_LISTS };
+
+template <bool RMS, bool GRAD>
+__global__ __launch_bounds__(kWThreads) void ddpg_wide_pop_many_kernel(const PopPlanRow *__restrict__ plan, const int32_t *__restrict__ list,
+                                                                        int32_t it) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const PopPlanRow *row = plan + list[blockIdx.y];
+    const WideRowTail t = lds_uniform(&row->t);
+    WideHead a;
+    if (!wide_many_enter(GRAD ? &row->gg : &row->g, t, it, lds, a)) return;
+    if constexpr (GRAD) {
+        const PopGrad pg = lds_uniform(&row->pg);
+        if constexpr (RMS) wide_grad_body(a, lds, 0, t.d_rms, pg);
+        else wide_grad_body(a, lds, 0, pg);
+    } else {
+        const PopTarget pt = lds_uniform(&row->pt);
+        if constexpr (RMS) wide_grad_body(a, lds, 0, t.d_rms, pt);
+        else wide_grad_body(a, lds, 0, pt);
+    }
+}
+
+// Grid (1, count).  An agent whose iterations are done must leave here: the renormalisation is no fixed point (it would
+// add the last batch's sums to ret_rms once more and rescale both output layers by sigma_old / sigma_new again).
+__global__ __launch_bounds__(256) void ddpg_popart_renorm_many_kernel(const PopPlanRow *__restrict__ plan, const int32_t *__restrict__ list,
+                                                                       int32_t it) {
+    __shared__ double sp[2 * 256];
+    __shared__ float sc[4];
+    const PopPlanRow *row = plan + list[blockIdx.y];
+    if (it >= row->t.n_iters) return;
+    const RenormArgs a = row->rn;
+    popart_renorm_body(a, sp, sc);
+}
+
+size_t ddpg_pop_plan_bytes(int32_t n_agents) {
+    return n_agents < 1 ? 0 : (size_t)n_agents * (sizeof(PopPlanRow) + N_POP_LISTS * sizeof(int32_t));
+}
+
+static int pop_plan_row(const ssc_ddpg_many_popart_item *item, int agent, PopPlanRow *row) {
+    memset(row, 0, sizeof *row);
+    if (item->n_iters <= 0) return SSC_OK;
+    const ssc_ddpg_desc *d = &item->ddpg;
+    char who[64];
+    snprintf(who, sizeof who, "ssc_ddpg_train_many_popart: agent %d", agent);
+    if (int rc = wide_batch_check(who, d)) return rc;
+    const PopLayout L = popart_layout(d, item->d_workspace);
+    SSC_REQUIRE(item->d_workspace != nullptr && item->workspace_bytes >= L.bytes,
+                "%s: workspace %zu < %zu bytes (ssc_ddpg_train_popart_workspace_bytes)", who, item->workspace_bytes, L.bytes);
+    size_t lds = 0;
+    if (wide_build(d, &item->replay, WIDE_POP_TARGET, item->d_workspace, row->g, lds) ||
+        wide_build(d, &item->replay, WIDE_POP_GRAD, item->d_workspace, row->gg, lds))
+        return set_error(SSC_EUNSUPPORTED, "%s: these layer sizes need %zu B of LDS per workgroup (160 KB available)", who, lds);
+    row->g.batch_idx = row->gg.batch_idx = item->d_batch_idx;
+    const int nb = wide_blocks(d);
+    wide_apply_args(d, item->d_workspace, nb, row->ap);
+    row->t.d_rms = item->d_rms; row->t.d_losses = item->d_losses;
+    row->t.n_iters = item->n_iters; row->t.n_blocks = nb;
+    row->t.apply_blocks = (row->ap.nA + row->ap.nC + 255) / 256;
+    row->t.lds_bytes = (int32_t)lds;
+    popart_renorm_args(d, L, item->d_ret_rms, row->rn);
+    row->pt = PopTarget{item->d_ret_rms, L.y, L.part};
+    row->pg = PopGrad{L.y, L.scal};
+    return SSC_OK;
+}
+
+int ddpg_pop_plan(const ssc_ddpg_many_popart_item *h_items, int32_t n_agents, void *h_plan) {
+    PopPlanRow *rows = static_cast<PopPlanRow *>(h_plan);
+    int32_t count[N_POP_LISTS] = {};
+    auto list = [&](int which) { return plan_list(h_plan, n_agents, which, sizeof(PopPlanRow)); };
+    for (int which = 0; which < N_POP_LISTS; ++which)
+        for (int p = 0; p < n_agents; ++p) list(which)[p] = 0;     // (unused slots name a valid row)
+    for (int p = 0; p < n_agents; ++p) {
+        if (int rc = pop_plan_row(&h_items[p], p, &rows[p])) return rc;
+        if (h_items[p].n_iters <= 0) continue;
+        const int gl = h_items[p].d_rms != nullptr ? LIST_GRAD_RMS : LIST_GRAD_PLAIN;
+        const int al = wide_prepared(&h_items[p].ddpg) ? LIST_APPLY_PREPARED : LIST_APPLY_PLAIN;
+        for (int which : {gl, al, (int)LIST_POP_ALL}) list(which)[count[which]++] = p;
+    }
+    return SSC_OK;
+}
+
+template <bool RMS, bool GRAD> static int pop_many_lds_attr(size_t lds) {
+    if (lds <= 64 * 1024) return SSC_OK;
+    return check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(ddpg_wide_pop_many_kernel<RMS, GRAD>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                     "hipFuncSetAttribute(ddpg_wide_pop_many_kernel)");
+}
+
+// The launch sequence over a validated plan: per iteration the target pass (one launch per statistics / no statistics),
+// the renormalise launch, the gradient pass (likewise), then prepare + apply or apply -- 4 launches where the agents are
+// alike, 5 with critic_l2_reg / clip_norm.
+int ddpg_train_pop_many(const void *h_plan, const void *d_plan, int32_t n_agents, hipStream_t stream) {
+    const PopPlanRow *rows = static_cast<const PopPlanRow *>(h_plan), *d_rows = static_cast<const PopPlanRow *>(d_plan);
+    struct Group { int count = 0, iters = 0, width = 0; size_t lds = 0; } grp[N_POP_LISTS];
+    for (int p = 0; p < n_agents; ++p) {
+        const WideRowTail &t = rows[p].t;
+        if (t.n_iters <= 0) continue;
+        const bool prepared = wide_prepared(&rows[p].ap.d);
+        Group &gg = grp[t.d_rms != nullptr ? LIST_GRAD_RMS : LIST_GRAD_PLAIN], &ga = grp[prepared ? LIST_APPLY_PREPARED : LIST_APPLY_PLAIN];
+        ++gg.count; gg.iters = std::max(gg.iters, t.n_iters); gg.width = std::max(gg.width, t.n_blocks);
+        gg.lds = std::max(gg.lds, (size_t)t.lds_bytes);
+        ++ga.count; ga.iters = std::max(ga.iters, t.n_iters); ga.width = std::max(ga.width, t.apply_blocks);
+        ++grp[LIST_POP_ALL].count; grp[LIST_POP_ALL].iters = std::max(grp[LIST_POP_ALL].iters, t.n_iters);
+    }
+    const int iters = grp[LIST_POP_ALL].iters;
+    if (iters == 0) return SSC_OK;
+    if (int rc = pop_many_lds_attr<false, false>(grp[LIST_GRAD_PLAIN].lds)) return rc;
+    if (int rc = pop_many_lds_attr<false, true>(grp[LIST_GRAD_PLAIN].lds)) return rc;
+    if (int rc = pop_many_lds_attr<true, false>(grp[LIST_GRAD_RMS].lds)) return rc;
+    if (int rc = pop_many_lds_attr<true, true>(grp[LIST_GRAD_RMS].lds)) return rc;
+    auto list = [&](int which) { return plan_list(const_cast<void *>(d_plan), n_agents, which, sizeof(PopPlanRow)); };
+    for (int it = 0; it < iters; ++it) {
+        const Group &gp = grp[LIST_GRAD_PLAIN], &gr = grp[LIST_GRAD_RMS], &ap = grp[LIST_APPLY_PLAIN], &aq = grp[LIST_APPLY_PREPARED];
+        if (it < gp.iters)
+            hipLaunchKernelGGL((ddpg_wide_pop_many_kernel<false, false>), dim3(gp.width, gp.count), dim3(kWThreads), gp.lds, stream, d_rows,
+                               list(LIST_GRAD_PLAIN), it);
+        if (it < gr.iters)
+            hipLaunchKernelGGL((ddpg_wide_pop_many_kernel<true, false>), dim3(gr.width, gr.count), dim3(kWThreads), gr.lds, stream, d_rows,
+                               list(LIST_GRAD_RMS), it);
+        hipLaunchKernelGGL(ddpg_popart_renorm_many_kernel, dim3(1, grp[LIST_POP_ALL].count), dim3(256), 0, stream, d_rows, list(LIST_POP_ALL), it);
+        if (it < gp.iters)
+            hipLaunchKernelGGL((ddpg_wide_pop_many_kernel<false, true>), dim3(gp.width, gp.count), dim3(kWThreads), gp.lds, stream, d_rows,
+                               list(LIST_GRAD_PLAIN), it);
+        if (it < gr.iters)
+            hipLaunchKernelGGL((ddpg_wide_pop_many_kernel<true, true>), dim3(gr.width, gr.count), dim3(kWThreads), gr.lds, stream, d_rows,
+                               list(LIST_GRAD_RMS), it);
+        if (it < aq.iters) {
+            hipLaunchKernelGGL(ddpg_wide_prepare_many_kernel<PopPlanRow>, dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows,
+                               list(LIST_APPLY_PREPARED), it);
+            hipLaunchKernelGGL((ddpg_wide_apply_many_kernel<true, PopPlanRow>), dim3(aq.width, aq.count), dim3(256), 0, stream, d_rows,
+                               list(LIST_APPLY_PREPARED), it);
+        }
+        if (it < ap.iters)
+            hipLaunchKernelGGL((ddpg_wide_apply_many_kernel<false, PopPlanRow>), dim3(ap.width, ap.count), dim3(256), 0, stream, d_rows,
+                               list(LIST_APPLY_PLAIN), it);
+    }
+    hipLaunchKernelGGL(ddpg_wide_finish_many_kernel<PopPlanRow>, dim3(blocks_for(n_agents)), dim3(256), 0, stream, d_rows, n_agents);
+    return check_launch("ssc_ddpg_train_many_popart");
 }
 
 }  // namespace ssc
