@@ -449,6 +449,8 @@ def _net_fwd(ar, p, x, Ex, llt, act=None, Eact=None):
     n2, En2, l2 = _ln_fwd(ar, z2, Ez2, p, "ln2")
     a2, Ea2, pre2 = _hidden2(ar, n2, En2, llt)
     out, Eout = _dense(ar, a2, Ea2, p["W3"], p["b3"])
+    if Eout is not None and "E_W3" in p:        # an output layer that is itself a float32 result (tests/popart_grad_cases.py)
+        Eout = Eout + np.abs(a2) @ p["E_W3"] + p["E_b3"]
     c = dict(x=x, Ex=Ex, n1=n1, a1=a1, Ea1=Ea1, n2=n2, a2=a2, Ea2=Ea2, l1=l1, l2=l2, relu_pre=[n1] + ([pre2] if pre2 is not None else []))
     if act is None:
         out, Eout = _tanh_fwd(ar, out, Eout)
@@ -466,6 +468,8 @@ def _net_bwd(ar, p, c, dout, Edout, llt, want_weights, mut, rows, brows, actor):
     if want_weights:
         g["W3"], g["b3"], A["W3"], A["b3"] = _wgrad(ar, c["a2"], c["Ea2"], dout, Edout, rows, brows)
     da2, Eda2 = _back(ar, dout, Edout, p["W3"])
+    if Eda2 is not None and "E_W3" in p:
+        Eda2 = Eda2 + np.abs(dout) @ p["E_W3"].T
     dn2, Edn2 = _hidden2_bwd(da2, Eda2, c, llt)
     if mut == "drop_last_unit_h2":
         dn2 = dn2.copy(); dn2[:, -1] = 0
@@ -515,6 +519,50 @@ def row_margin(d, rows=None):
     _, _, c1 = _net_fwd(ar, critic, x, Ex, d["llt"], act, np.zeros(act.shape))
     _, _, c2 = _net_fwd(ar, critic, x, Ex, d["llt"], pi, Epi)
     return np.min(np.concatenate([np.abs(p) for p in ac["relu_pre"] + c1["relu_pre"] + c2["relu_pre"]], axis=1), axis=1)
+
+
+def _l2_terms(ar, critic, gc, Ac, loss_c, A_lc, l2, mut):
+    """critic_l2_reg on the critic's gradients gc / sizes Ac (in place) -> (critic loss, its size)"""
+    T, absd = ar.t, ar.sizes
+    if l2:
+        for k in ("W1", "W2", "W3") + (("b1", "b2", "b3") if mut == "l2_on_biases" else ()):
+            if k[0] == "W":
+                w = critic[k].reshape(-1)
+                loss_c = loss_c + T(0.5) * T(l2) * ar.colsum((w * w)[:, None])[0]
+            gc[k] = gc[k] + T(l2) * critic[k].reshape(gc[k].shape)
+            if absd and k[0] == "W":
+                Ac[k] = Ac[k] + l2 * np.abs(critic[k]) + np.abs(gc[k])
+                if "E_" + k in critic:
+                    Ac[k] = Ac[k] + l2 * critic["E_" + k].reshape(Ac[k].shape)
+                A_lc += 0.5 * l2 * float(np.sum(critic[k] ** 2))
+    return loss_c, A_lc
+
+
+def _shape_and_clip(ar, actor, critic, ga, gc, Aa, Ac, clip, mut):
+    """the gradients in their parameters' shapes, the per-variable norms BEFORE clip_norm, clip_norm applied:
+    (ga, gc, Aa, Ac, norms, n_bound)"""
+    T, absd = ar.t, ar.sizes
+    ga = {k: ga[k].reshape(actor[k].shape) for k in keys_of(actor)}
+    gc = {k: gc[k].reshape(critic[k].shape) for k in keys_of(critic)}
+    if absd:
+        Aa = {k: Aa[k].reshape(actor[k].shape) for k in keys_of(actor)}
+        Ac = {k: Ac[k].reshape(critic[k].shape) for k in keys_of(critic)}
+    norms = {n: {k: float(np.sqrt(np.sum(np.square(v.astype(np.float64))))) for k, v in g.items()} for n, g in (("actor", ga), ("critic", gc))}
+    n_bound = 0
+    if clip is not None:
+        for g, A in ((ga, Aa), (gc, Ac)):
+            if mut == "clip_global_norm":
+                gn = T(np.sqrt(sum(float(np.sum(np.square(v.astype(np.float64)))) for v in g.values())))
+            for k in g:
+                v = g[k].reshape(-1)
+                nrm = gn if mut == "clip_global_norm" else np.sqrt(ar.colsum((v * v)[:, None])[0])
+                if nrm > T(clip):
+                    sc = T(clip) / nrm
+                    n_bound += 1
+                    if absd:
+                        A[k] = sc * A[k] + np.abs(sc * g[k]) * (float(np.sum(np.abs(g[k]) * A[k])) / float(nrm) ** 2 + 3.0)
+                    g[k] = g[k] * sc
+    return ga, gc, Aa, Ac, norms, n_bound
 
 
 def step(d, f32=False, mut=None, idx=None, sizes=True):
@@ -569,15 +617,7 @@ def step(d, f32=False, mut=None, idx=None, sizes=True):
     Edq = 2.0 * (Qa + Ya + np.abs(e)) / B + np.abs(dq) if absd else None
     gc, Ac, _, _ = _net_bwd(ar, critic, cc, dq, Edq, llt, True, mut, rows, brows, False)
     A_lc = float(np.mean((Qa + Ya) ** 2)) if absd else None
-    if l2:
-        for k in ("W1", "W2", "W3") + (("b1", "b2", "b3") if mut == "l2_on_biases" else ()):
-            if k[0] == "W":
-                w = critic[k].reshape(-1)
-                loss_c = loss_c + T(0.5) * T(l2) * ar.colsum((w * w)[:, None])[0]
-            gc[k] = gc[k] + T(l2) * critic[k].reshape(gc[k].shape)
-            if absd and k[0] == "W":
-                Ac[k] = Ac[k] + l2 * np.abs(critic[k]) + np.abs(gc[k])
-                A_lc += 0.5 * l2 * float(np.sum(critic[k] ** 2))
+    loss_c, A_lc = _l2_terms(ar, critic, gc, Ac, loss_c, A_lc, l2, mut)
     # actor
     pi, Epi, ac = _net_fwd(ar, actor, s, Es, llt)
     qpi, Qpia, cc2 = _net_fwd(ar, critic, s, Es, llt, pi, Epi)
@@ -586,26 +626,7 @@ def step(d, f32=False, mut=None, idx=None, sizes=True):
     _, _, dact, Edact = _net_bwd(ar, critic, cc if mut == "actor_grad_at_s_a" else cc2, seed, np.abs(seed) if absd else None, llt,
                                  False, mut, rows, brows, False)
     ga, Aa, _, _ = _net_bwd(ar, actor, ac, dact, Edact, llt, True, mut, rows, brows, True)
-    ga = {k: ga[k].reshape(actor[k].shape) for k in keys_of(actor)}
-    gc = {k: gc[k].reshape(critic[k].shape) for k in keys_of(critic)}
-    if absd:
-        Aa = {k: Aa[k].reshape(actor[k].shape) for k in keys_of(actor)}
-        Ac = {k: Ac[k].reshape(critic[k].shape) for k in keys_of(critic)}
-    norms = {n: {k: float(np.sqrt(np.sum(np.square(v.astype(np.float64))))) for k, v in g.items()} for n, g in (("actor", ga), ("critic", gc))}
-    n_bound = 0
-    if clip is not None:
-        for g, A in ((ga, Aa), (gc, Ac)):
-            if mut == "clip_global_norm":
-                gn = T(np.sqrt(sum(float(np.sum(np.square(v.astype(np.float64)))) for v in g.values())))
-            for k in g:
-                v = g[k].reshape(-1)
-                nrm = gn if mut == "clip_global_norm" else np.sqrt(ar.colsum((v * v)[:, None])[0])
-                if nrm > T(clip):
-                    sc = T(clip) / nrm
-                    n_bound += 1
-                    if absd:
-                        A[k] = sc * A[k] + np.abs(sc * g[k]) * (float(np.sum(np.abs(g[k]) * A[k])) / float(nrm) ** 2 + 3.0)
-                    g[k] = g[k] * sc
+    ga, gc, Aa, Ac, norms, n_bound = _shape_and_clip(ar, actor, critic, ga, gc, Aa, Ac, clip, mut)
     return dict(g=dict(actor=ga, critic=gc), A=dict(actor=Aa, critic=Ac) if absd else None, loss=(loss_c, loss_a),
                 A_loss=(A_lc, float(np.mean(Qpia))) if absd else None, relu_pre=ac["relu_pre"] + cc["relu_pre"] + cc2["relu_pre"],
                 norms=norms, n_bound=n_bound)
@@ -649,30 +670,33 @@ def _u(g):
     return LR1 * C1 * g / (np.sqrt(C2 * g * g) + EPSILON)
 
 
-def step1_ratios(theta0, g64, A, m, v, theta1):
+def step1_ratios(theta0, g64, A, m, v, theta1, c_grad=C_GRAD, theta0_err=0.0):
     """One parameter array after the iteration against the fp64 gradient: (m, v, theta), each the largest err / allowed over
     all elements, <= 1 accepted.  delta = C_GRAD 2^-24 A;
         |m - c1 g64| <= c1 delta + 2^-24 |c1 g64|            |v - c2 g64^2| <= c2 (2 |g64| delta + delta^2) + 3 2^-24 c2 g64^2
         theta1 in theta0 - [u(g64 + delta), u(g64 - delta)] widened by w = 8 2^-24 |u| + 2^-23 |theta0|
     (the single-workgroup kernels take the hardware rcp and sqrt; theta: 1 + the distance outside the interval in units of
-    w, so that inside is <= 1 as well)."""
+    w, so that inside is <= 1 as well).  ``c_grad``: the constant in delta; ``theta0_err``: what theta0 itself may be off by
+    where it is a float32 result (the Pop-Art rescaled output layer), added to w."""
     theta0, g64, A, m, v, theta1 = (np.asarray(x, np.float64) for x in (theta0, g64, A, m, v, theta1))
-    delta = C_GRAD * EPS32 * A
+    delta = c_grad * EPS32 * A
     rm = ratio(np.abs(m - C1 * g64), C1 * delta + EPS32 * np.abs(C1 * g64))
     rv = ratio(np.abs(v - C2 * g64 * g64), C2 * (2 * np.abs(g64) * delta + delta * delta) + 3 * EPS32 * C2 * g64 * g64)
     u_hi, u_lo = _u(g64 + delta), _u(g64 - delta)
-    w = 8 * EPS32 * np.maximum(np.abs(u_hi), np.abs(u_lo)) + 2 * EPS32 * np.abs(theta0)
+    w = 8 * EPS32 * np.maximum(np.abs(u_hi), np.abs(u_lo)) + 2 * EPS32 * np.abs(theta0) + theta0_err
     outside = np.maximum(np.maximum((theta0 - u_hi - w) - theta1, theta1 - (theta0 - u_lo + w)), 0.0)
     rt = ratio(np.where(outside > 0, outside + w, 0.0), w)
     return rm, rv, rt
 
 
-def target_ratio(target0, theta1, target1, tau):
+def target_ratio(target0, theta1, target1, tau, target0_err=0.0):
     """the soft update of the NEW parameters: |target' - ((1 - tau) target + tau theta')| / (4 2^-24 (|target| + tau |theta'|));
-    tau = the kernel's float32 value"""
+    tau = the kernel's float32 value; ``target0_err``: what target0 itself may be off by (as theta0_err above), (1 - tau) of
+    which is added to the allowed error"""
     target0, theta1, target1 = (np.asarray(x, np.float64) for x in (target0, theta1, target1))
     tau = float(np.float32(tau))
-    return ratio(np.abs(target1 - ((1.0 - tau) * target0 + tau * theta1)), 4 * EPS32 * (np.abs(target0) + tau * np.abs(theta1)))
+    return ratio(np.abs(target1 - ((1.0 - tau) * target0 + tau * theta1)),
+                 4 * EPS32 * (np.abs(target0) + tau * np.abs(theta1)) + (1.0 - tau) * target0_err)
 
 
 def adam1_32(theta, g):

@@ -1,6 +1,7 @@
 """DDPG return normalisation and Pop-Art on the multi-workgroup learner (``ssc_ddpg_train_ws_popart``) against the fp64
 restatement of tests/popart_cases.py, and the properties around it: preserved outputs, the identities of the two switches
-on their own, reproducibility, statistics carried across calls, workspace guards and the denormalising read-outs."""
+on their own, reproducibility, statistics carried across calls, workspace guards and the denormalising read-outs.
+The derived float32 bound on ONE iteration of every Pop-Art kernel is tests/test_gpu_ddpg_popart_matrix.py."""
 import ctypes
 
 import numpy as np
