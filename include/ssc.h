@@ -1171,6 +1171,42 @@ int ssc_mlp_train_steps(const ssc_mlp_train_desc *net, const float *d_X, const f
 int ssc_mlp_train_step(const ssc_mlp_train_desc *net, const float *d_X, const float *d_Z, const int32_t *d_idx,
                        int32_t batch, float *d_loss, void *d_workspace, size_t workspace_bytes, ssc_stream_t stream);
 
+/* The arguments of one ssc_mlp_train_steps call.  Declared tag first like the other *_many items;
+ * tests/test_mlp_train_many_host.py holds the struct's size and offsets to the ctypes mirror. */
+struct ssc_mlp_train_many_item {
+    ssc_mlp_train_desc net;
+    const float   *d_X, *d_Z;      /* per model; read only, may be shared between models */
+    const int32_t *d_idx;          /* [n_steps][batch]; read only, may be shared */
+    int32_t        batch, n_steps; /* per model; n_steps == 0: the model is skipped, nothing else of its item is read */
+    float         *d_loss;         /* [n_steps] or NULL, per model */
+    void          *d_workspace;
+    size_t         workspace_bytes;/* >= ssc_mlp_train_workspace_bytes(&net, batch) */
+};
+typedef struct ssc_mlp_train_many_item ssc_mlp_train_many_item;
+
+/* ssc_mlp_train_steps for n_models independent models (the dynamics models of a sweep's seeds) in one begin launch plus
+ * max_p n_steps_p step launches, where per-model calls take sum_p (n_steps_p + 1).  Grid row p of a
+ * step launch runs model p's ceil(batch_p / 32) workgroups (grid x = the largest model's count; surplus workgroups, and
+ * all workgroups of a model whose steps are done, leave at once, before any barrier); the last workgroup of a model
+ * sums that model's partials and applies Adam.  Workgroups of different models share nothing: after the call every
+ * model's parameters, moments, adam_t, losses and workspace hold, bit for bit, what its own ssc_mlp_train_steps call with
+ * the item's arguments leaves -- ONE call: the bias-correction powers are recomputed at the start of a call and advanced by
+ * multiplication inside it, so two many-calls equal two single calls per model, not one longer one.
+ * The conventions are ssc_rollout_many's: the host array is validated completely before any HIP call, the caller's device
+ * copy of the same bytes must be complete on `stream`, the library copies nothing, model indices appear in
+ * ssc_last_error().
+ * Uniform over a call: the kernel instantiation the model's own call dispatches (in <= 3 and out <= 2 | in <= 4 and
+ * out <= 3 | the rest); SSC_EINVAL names the first model that differs from the first trained one.  Per model, read at run
+ * time: hidden width, in, out, batch, n_steps, lr and the Adam constants, d_loss set or NULL.
+ * A model the one-launch step does not cover (n_layers != 2, hidden > 512, in > 12, out > 8, or SSC_DYN_TRAIN_GENERIC set)
+ * is SSC_EUNSUPPORTED naming it; every other item passes ssc_mlp_train_steps's checks with its codes.
+ * What a model's workgroups write -- every layer's W, b, mW, vW, mb, vb, adam_t, d_loss[n_steps], the workspace -- may,
+ * among the models with n_steps > 0, overlap no other written range and no model's d_X, d_Z (taken as their first row:
+ * the row count is the caller's) or d_idx: SSC_EINVAL naming both models.  What is only read may coincide.
+ * n_models 1..65535.  Every n_steps == 0: SSC_OK without a launch (the validation-only call the wrappers use). */
+int ssc_mlp_train_steps_many(const ssc_mlp_train_many_item *h_items, const ssc_mlp_train_many_item *d_items,
+                             int32_t n_models, ssc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Random-rollout data collection -> dynamics-model training set (SURVEY.md section 8a row A17 and the
  * data format either side of it): CollectSamples.collect_samples / do_rollout

@@ -124,6 +124,11 @@ class MlpTrainDesc(Structure):
                 ("adam_t", c_void_p), ("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("epsilon", c_float)]
 
 
+class MlpTrainManyItem(Structure):
+    _fields_ = [("net", MlpTrainDesc), ("d_X", c_void_p), ("d_Z", c_void_p), ("d_idx", c_void_p), ("batch", c_int32),
+                ("n_steps", c_int32), ("d_loss", c_void_p), ("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
 class DdpgDesc(Structure):
     _fields_ = [("obs_dim", c_int32), ("act_dim", c_int32), ("actor_h1", c_int32), ("actor_h2", c_int32),
                 ("critic_h1", c_int32), ("critic_h2", c_int32), ("last_layer_tanh", c_int32), ("batch_size", c_int32),
@@ -227,7 +232,7 @@ STRUCTS = {
     "ssc_pair_cursor": PairCursor, "ssc_rollout_many_item": RolloutManyItem, "ssc_replay_append_item": ReplayAppendItem,
     "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem, "ssc_ddpg_eval_many_item": DdpgEvalManyItem,
     "ssc_ddpg_stats_many_item": DdpgStatsManyItem, "ssc_param_noise_many_item": ParamNoiseManyItem,
-    "ssc_param_noise_cursor": ParamNoiseCursor,
+    "ssc_param_noise_cursor": ParamNoiseCursor, "ssc_mlp_train_many_item": MlpTrainManyItem,
 }
 
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
@@ -342,6 +347,7 @@ _SIGNATURES = {
                                     c_void_p, c_size_t, c_void_p]),
     "ssc_mlp_train_step": (c_int, [POINTER(MlpTrainDesc), c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                    c_size_t, c_void_p]),
+    "ssc_mlp_train_steps_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "ssc_mlp_workspace_bytes": (c_size_t, [POINTER(MlpDesc), c_int64, c_int]),
     "ssc_mlp_forward": (c_int, [POINTER(MlpDesc), c_int64, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "ssc_mse_batches": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

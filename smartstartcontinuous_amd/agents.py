@@ -1722,6 +1722,13 @@ class NND_MB_agent(NavigationRLAgent):
         if self.use_existing_dynamics_model:                     # :463-468: restore instead of training
             self.dyn_model.load(os.path.join(self.load_dir, "models", "finalModel.npz"))
             return 0
+        args = self._dynamics_training_args(dataX_new, dataZ_new, nEpoch, fraction_use_new, rng)
+        loss = self.dyn_model.train(*args, batchsize=batchsize, lr=lr, rng=rng)
+        self._save_trained_dynamics_model()
+        return loss
+
+    def _dynamics_training_args(self, dataX_new, dataZ_new, nEpoch, fraction_use_new, rng):
+        """(dataX, dataZ, dataX_new, dataZ_new, nEpoch, fraction_use_new) of ``DynamicsModel.train`` for this agent"""
         if self._train_inputs is None:
             raise RuntimeError("NND_MB_agent was built without training_data")
         if dataX_new is None and dataZ_new is None:
@@ -1732,12 +1739,48 @@ class NND_MB_agent(NavigationRLAgent):
             zn = np.zeros((0, out_dim)) if dataZ_new is None else np.asarray(dataZ_new)
         nEpoch = self.nEpochs if nEpoch is None else nEpoch
         fraction_use_new = self.fraction_use_new if fraction_use_new is None else fraction_use_new
-        loss = self.dyn_model.train(self._train_inputs, self._train_outputs, xn, zn, nEpoch, fraction_use_new,
-                                    batchsize=batchsize, lr=lr, rng=rng)
+        return self._train_inputs, self._train_outputs, xn, zn, nEpoch, fraction_use_new
+
+    def _save_trained_dynamics_model(self):
         if self.save_resulting_dynamics_model:                   # :475-480 (an .npz instead of a TF checkpoint)
             d = os.path.join(self.save_dir, "models")
             os.makedirs(d, exist_ok=True)
             n_train = 1 + self.num_episodes_finished // self.num_episodes_for_aggregation
             self.dyn_model.save(os.path.join(d, "model_numTrain%d.npz" % n_train))
             self.dyn_model.save(os.path.join(d, "finalModel.npz"))
-        return loss
+
+
+def train_dynamics_models(nnd_agents, rngs, dataX_new=None, dataZ_new=None, nEpoch=None, fraction_use_new=None, batchsize=512,
+                          lr=0.001, population=None):
+    """``agent.train_dynamics_model(..., rng=rngs[p])`` for every ``NND_MB_agent`` of a list (the seeds of a sweep), the
+    training itself through ``navigator.DynamicsModelPopulation``: one launch per Adam step for all of them.  Per agent
+    as before: ``use_existing_dynamics_model`` restores instead of training (its loss is 0), the aggregated data set is
+    drawn with the agent's own rng, the trained model is saved where the agent saves it.  ``dataX_new`` / ``dataZ_new``:
+    ``None`` or one entry per agent; ``nEpoch``, ``fraction_use_new``, ``batchsize``, ``lr``: one value, or one per agent.
+    ``population``: a ``DynamicsModelPopulation`` over the TRAINED agents' models kept from an earlier call (its item
+    tables stay on the device).  Returns the list of losses."""
+    n = len(nnd_agents)
+    if not isinstance(rngs, (list, tuple)) or len(rngs) != n:
+        raise ValueError("train_dynamics_models: one rng per agent")
+    per = lambda v, what: navigator._per_model(v, n, what)
+    xs, zs = per(dataX_new, "dataX_new"), per(dataZ_new, "dataZ_new")
+    epochs, fracs, sizes, lrs = per(nEpoch, "nEpoch"), per(fraction_use_new, "fraction_use_new"), per(batchsize, "batchsize"), per(lr, "lr")
+    losses, train = [0] * n, []
+    for p, a in enumerate(nnd_agents):
+        if a.use_existing_dynamics_model:
+            a.dyn_model.load(os.path.join(a.load_dir, "models", "finalModel.npz"))
+        else:
+            train.append(p)
+    if not train:
+        return losses
+    args = [nnd_agents[p]._dynamics_training_args(xs[p], zs[p], epochs[p], fracs[p], rngs[p]) for p in train]
+    if population is None:
+        population = navigator.DynamicsModelPopulation([nnd_agents[p].dyn_model for p in train])
+    elif [id(m) for m in population.models] != [id(nnd_agents[p].dyn_model) for p in train]:
+        raise ValueError("train_dynamics_models: population does not hold the trained agents' models")
+    got = population.train([a[:4] for a in args], [a[4] for a in args], [a[5] for a in args], batchsize=[sizes[p] for p in train],
+                           lr=[lrs[p] for p in train], rngs=[rngs[p] for p in train])
+    for p, loss in zip(train, got):
+        losses[p] = loss
+        nnd_agents[p]._save_trained_dynamics_model()
+    return losses

@@ -12,9 +12,15 @@
 //     output delta and per-tile loss sums) -> per hidden layer a backward-data GEMM with the ReLU mask -> ONE launch
 //     with the weight-gradient GEMMs of all layers, Adam in the epilogue; all on the exact-fp32 MFMA through one
 //     32x32-tile routine (gemm32_tile).  2 L + 1 launches per step.
+// ssc_mlp_train_steps_many runs the fused step of a whole population of models in one launch per step
+// (mlp_train_fused_many_kernel: grid row p = model p, the same body, the model's own ticket / partials / LDS carve-up).
 // The bias-corrected step size comes from a device-side step counter, so any number of consecutive steps is
 // enqueued by one call without a host round trip.
+#include <stdio.h>
 #include <stdlib.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "ssc_device.h"
 #include "ssc_host.h"
@@ -241,13 +247,38 @@ struct FusedTrainArgs {
     float *loss;         // [1] or NULL
 };
 
+// Everything of FusedTrainArgs but idx and loss (they move with the step), from a call's arguments: on the host for
+// ssc_mlp_train_steps, in the workgroup for ssc_mlp_train_steps_many -- one rule for the geometry and the workspace layout
+// (ticket at byte 0, step state at 64, per-block gradients from 256).
+__host__ __device__ inline FusedTrainArgs fused_pack(const ssc_mlp_train_desc &net, const float *X, const float *Z, int B,
+                                                     void *workspace) {
+    FusedTrainArgs g;
+    g.X = X; g.Z = Z; g.idx = nullptr; g.B = B;
+    g.in = net.dims[0]; g.hd = net.dims[1]; g.out = net.dims[2];
+    g.hd_pad = 16; g.hd_shift = 4;
+    while (g.hd_pad < g.hd) { g.hd_pad <<= 1; ++g.hd_shift; }
+    g.S = kFT / g.hd_pad;
+    g.G = (B + kFRows - 1) / kFRows;
+    g.W1 = net.W[0]; g.b1 = net.b[0]; g.W2 = net.W[1]; g.b2 = net.b[1];
+    g.mW1 = net.mW[0]; g.vW1 = net.vW[0]; g.mb1 = net.mb[0]; g.vb1 = net.vb[0];
+    g.mW2 = net.mW[1]; g.vW2 = net.vW[1]; g.mb2 = net.mb[1]; g.vb2 = net.vb[1];
+    g.adam_t = net.adam_t; g.lr = net.lr; g.beta1 = net.beta1; g.beta2 = net.beta2; g.eps = net.epsilon;
+    g.ticket = static_cast<uint32_t *>(workspace);
+    g.state = reinterpret_cast<FusedStepState *>(static_cast<char *>(workspace) + 64);
+    g.partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + 256);
+    g.loss = nullptr;
+    return g;
+}
+
 static inline size_t fused_lds_floats(int hd_pad, int S, int IN, int OUT) {
     return (size_t)kFRows * (hd_pad + 1) + (size_t)hd_pad * OUT + (size_t)kFRows * IN + 2 * (size_t)kFRows * OUT +
            (S > 1 ? (size_t)kFT * (IN + 1 + OUT) : 0) + kFRows + 8;
 }
 
+// The step of one model; blockIdx.x is the workgroup's index among the model's G.  Shared by the single-model kernel and
+// the population kernel below, so both leave the same bits.
 template <int IN, int OUT>
-__global__ __launch_bounds__(kFT) void mlp_train_fused_kernel(FusedTrainArgs g) {
+__device__ __forceinline__ void mlp_train_fused_body(const FusedTrainArgs &g) {
     extern __shared__ float lds[];
     float *h_s = lds;                                   // [32][hd_pad + 1] hidden activations of the block's rows
     float *w2_s = h_s + kFRows * (g.hd_pad + 1);        // [hd_pad][OUT]
@@ -474,6 +505,11 @@ __global__ __launch_bounds__(kFT) void mlp_train_fused_kernel(FusedTrainArgs g) 
     }
 }
 
+template <int IN, int OUT>
+__global__ __launch_bounds__(kFT) void mlp_train_fused_kernel(FusedTrainArgs g) {
+    mlp_train_fused_body<IN, OUT>(g);
+}
+
 // once per ssc_mlp_train_steps call: ticket = 0, beta powers and step size of the first step of the call
 __global__ void fused_begin_kernel(const int32_t *adam_t, float lr, float b1, float b2, uint32_t *ticket, FusedStepState *st) {
     const int tt = adam_t[0] + 1;
@@ -481,6 +517,38 @@ __global__ void fused_begin_kernel(const int32_t *adam_t, float lr, float b1, fl
     st->pw1 = p1; st->pw2 = p2;
     st->lr_t = (float)((double)lr * sqrt(1.0 - p2) / (1.0 - p1));
     ticket[0] = 0u;
+}
+
+// A population of models in one launch per step (ssc_mlp_train_steps_many): blockIdx.y is the model, whose workgroups
+// are blockIdx.x < G_p of a grid as wide as the largest model needs.  A surplus workgroup, and every workgroup of a model
+// that has no step `step`, leaves before any barrier, LDS write or ticket; a working one packs the arguments its model's
+// own call would pass and runs the same body, so ticket, partials and LDS offsets are the model's own.
+template <int IN, int OUT>
+__global__ __launch_bounds__(kFT) void mlp_train_fused_many_kernel(const ssc_mlp_train_many_item *__restrict__ items,
+                                                                   int32_t step) {
+    const ssc_mlp_train_many_item &it = items[blockIdx.y];
+    if (step >= it.n_steps) return;        // n_steps == 0: nothing else of the item is read
+    const int B = it.batch;
+    if ((int)blockIdx.x >= (B + kFRows - 1) / kFRows) return;
+    FusedTrainArgs g = fused_pack(it.net, it.d_X, it.d_Z, B, it.d_workspace);
+    g.idx = it.d_idx + (size_t)step * B;
+    g.loss = it.d_loss ? it.d_loss + step : nullptr;
+    mlp_train_fused_body<IN, OUT>(g);
+}
+
+// once per ssc_mlp_train_steps_many call: thread p is model p's fused_begin_kernel
+__global__ __launch_bounds__(256) void fused_begin_many_kernel(const ssc_mlp_train_many_item *__restrict__ items, int32_t n_models) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_models) return;
+    const ssc_mlp_train_many_item &it = items[p];
+    if (it.n_steps <= 0) return;
+    const ssc_mlp_train_desc &net = it.net;
+    FusedStepState *st = reinterpret_cast<FusedStepState *>(static_cast<char *>(it.d_workspace) + 64);
+    const int tt = net.adam_t[0] + 1;
+    const double p1 = pow((double)net.beta1, (double)tt), p2 = pow((double)net.beta2, (double)tt);
+    st->pw1 = p1; st->pw2 = p2;
+    st->lr_t = (float)((double)net.lr * sqrt(1.0 - p2) / (1.0 - p1));
+    static_cast<uint32_t *>(it.d_workspace)[0] = 0u;
 }
 
 static bool fused_eligible(const ssc_mlp_train_desc *net) {
@@ -505,6 +573,27 @@ static int launch_fused(const FusedTrainArgs &g, hipStream_t s) {
             return rc;
     }
     hipLaunchKernelGGL((mlp_train_fused_kernel<IN, OUT>), dim3(g.G), dim3(kFT), lds_bytes, s, g);
+    return SSC_OK;
+}
+
+// the instantiation ssc_mlp_train_steps dispatches for a fused-eligible net: 0 <3,2>, 1 <4,3>, 2 <12,8>
+static int fused_class(const ssc_mlp_train_desc *net) {
+    const int in = net->dims[0], out = net->dims[2];
+    return (in <= 3 && out <= 2) ? 0 : (in <= 4 && out <= 3) ? 1 : 2;
+}
+
+// step launches of a population: grid (g_max, n_models), the dynamic LDS of the largest model
+template <int IN, int OUT>
+static int launch_fused_many(const ssc_mlp_train_many_item *d_items, int n_models, int g_max, size_t lds_bytes, int steps,
+                             hipStream_t s) {
+    if (lds_bytes > 64 * 1024) {      // per device, so per call (see launch_fused)
+        if (int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_train_fused_many_kernel<IN, OUT>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes),
+                               "hipFuncSetAttribute(mlp_train_fused_many_kernel)"))
+            return rc;
+    }
+    for (int k = 0; k < steps; ++k)
+        hipLaunchKernelGGL((mlp_train_fused_many_kernel<IN, OUT>), dim3(g_max, n_models), dim3(kFT), lds_bytes, s, d_items, k);
     return SSC_OK;
 }
 
@@ -619,22 +708,30 @@ static int generic_step(const ssc_mlp_train_desc *net, const float *d_X, const f
     return SSC_OK;
 }
 
+// the argument checks of one ssc_mlp_train_steps call; `who` leads the message (the entry point, and the model for a population)
+static int train_check(const char *who, const ssc_mlp_train_desc *net, const float *d_X, const float *d_Z, const int32_t *d_idx,
+                       int32_t B, int32_t n_steps, void *d_workspace, size_t workspace_bytes) {
+    SSC_REQUIRE(net->n_layers >= 1 && net->n_layers <= SSC_MAX_LAYERS, "%s: bad n_layers", who);
+    SSC_REQUIRE(B >= 1 && B <= 65536, "%s: batch %d out of range", who, B);
+    SSC_REQUIRE(n_steps >= 0, "%s: n_steps %d < 0", who, n_steps);
+    for (int l = 0; l <= net->n_layers; ++l)
+        SSC_REQUIRE(net->dims[l] >= 1 && net->dims[l] <= 8192, "%s: bad dims[%d]", who, l);
+    for (int l = 0; l < net->n_layers; ++l)
+        SSC_REQUIRE(net->W[l] && net->b[l] && net->mW[l] && net->vW[l] && net->mb[l] && net->vb[l],
+                    "%s: NULL parameter / moment pointer (layer %d)", who, l);
+    if (n_steps == 0) return SSC_OK;
+    SSC_REQUIRE(net->adam_t && d_X && d_Z && d_idx, "%s: NULL pointer", who);
+    const size_t need = ssc_mlp_train_workspace_bytes(net, B);
+    SSC_REQUIRE(d_workspace && workspace_bytes >= need, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+    return SSC_OK;
+}
+
 int ssc_mlp_train_steps(const ssc_mlp_train_desc *net, const float *d_X, const float *d_Z, const int32_t *d_idx,
                         int32_t B, int32_t n_steps, float *d_loss, void *d_workspace, size_t workspace_bytes,
                         ssc_stream_t stream) {
     SSC_REQUIRE(net != nullptr, "ssc_mlp_train_steps: net NULL");
-    SSC_REQUIRE(net->n_layers >= 1 && net->n_layers <= SSC_MAX_LAYERS, "ssc_mlp_train_steps: bad n_layers");
-    SSC_REQUIRE(B >= 1 && B <= 65536, "ssc_mlp_train_steps: batch %d out of range", B);
-    SSC_REQUIRE(n_steps >= 0, "ssc_mlp_train_steps: n_steps %d < 0", n_steps);
-    for (int l = 0; l <= net->n_layers; ++l)
-        SSC_REQUIRE(net->dims[l] >= 1 && net->dims[l] <= 8192, "ssc_mlp_train_steps: bad dims[%d]", l);
-    for (int l = 0; l < net->n_layers; ++l)
-        SSC_REQUIRE(net->W[l] && net->b[l] && net->mW[l] && net->vW[l] && net->mb[l] && net->vb[l],
-                    "ssc_mlp_train_steps: NULL parameter / moment pointer (layer %d)", l);
+    if (int rc = train_check("ssc_mlp_train_steps", net, d_X, d_Z, d_idx, B, n_steps, d_workspace, workspace_bytes)) return rc;
     if (n_steps == 0) return SSC_OK;
-    SSC_REQUIRE(net->adam_t && d_X && d_Z && d_idx, "ssc_mlp_train_steps: NULL pointer");
-    const size_t need = ssc_mlp_train_workspace_bytes(net, B);
-    SSC_REQUIRE(d_workspace && workspace_bytes >= need, "ssc_mlp_train_steps: workspace %zu < %zu", workspace_bytes, need);
     hipStream_t s = as_stream(stream);
     if (!fused_eligible(net)) {
         for (int k = 0; k < n_steps; ++k)
@@ -642,32 +739,103 @@ int ssc_mlp_train_steps(const ssc_mlp_train_desc *net, const float *d_X, const f
                 return rc;
         return check_launch("ssc_mlp_train_steps");
     }
-    FusedTrainArgs g;
-    g.X = d_X; g.Z = d_Z; g.B = B;
-    g.in = net->dims[0]; g.hd = net->dims[1]; g.out = net->dims[2];
-    g.hd_pad = 16; g.hd_shift = 4;
-    while (g.hd_pad < g.hd) { g.hd_pad <<= 1; ++g.hd_shift; }
-    g.S = kFT / g.hd_pad;
-    g.G = (B + kFRows - 1) / kFRows;
-    g.W1 = net->W[0]; g.b1 = net->b[0]; g.W2 = net->W[1]; g.b2 = net->b[1];
-    g.mW1 = net->mW[0]; g.vW1 = net->vW[0]; g.mb1 = net->mb[0]; g.vb1 = net->vb[0];
-    g.mW2 = net->mW[1]; g.vW2 = net->vW[1]; g.mb2 = net->mb[1]; g.vb2 = net->vb[1];
-    g.adam_t = net->adam_t; g.lr = net->lr; g.beta1 = net->beta1; g.beta2 = net->beta2; g.eps = net->epsilon;
-    g.ticket = static_cast<uint32_t *>(d_workspace);
-    g.state = reinterpret_cast<FusedStepState *>(static_cast<char *>(d_workspace) + 64);
-    g.partial = reinterpret_cast<float *>(static_cast<char *>(d_workspace) + 256);
+    FusedTrainArgs g = fused_pack(*net, d_X, d_Z, B, d_workspace);
     hipLaunchKernelGGL(fused_begin_kernel, dim3(1), dim3(1), 0, s, net->adam_t, net->lr, net->beta1, net->beta2, g.ticket,
                        g.state);
+    const int cls = fused_class(net);
     for (int k = 0; k < n_steps; ++k) {
         g.idx = d_idx + (size_t)k * B;
         g.loss = d_loss ? d_loss + k : nullptr;
-        int rc;
-        if (g.in <= 3 && g.out <= 2) rc = launch_fused<3, 2>(g, s);
-        else if (g.in <= 4 && g.out <= 3) rc = launch_fused<4, 3>(g, s);
-        else rc = launch_fused<12, 8>(g, s);
+        const int rc = cls == 0 ? launch_fused<3, 2>(g, s) : cls == 1 ? launch_fused<4, 3>(g, s) : launch_fused<12, 8>(g, s);
         if (rc) return rc;
     }
     return check_launch("ssc_mlp_train_steps");
+}
+
+namespace {
+// a byte range a population's launches write (owned) or only read, and the model it belongs to
+struct ModelRange {
+    uintptr_t begin, end;
+    int model;
+    bool written;
+    bool operator<(const ModelRange &o) const { return begin < o.begin; }
+};
+}  // namespace
+
+int ssc_mlp_train_steps_many(const ssc_mlp_train_many_item *h_items, const ssc_mlp_train_many_item *d_items, int32_t n_models,
+                             ssc_stream_t stream) {
+    SSC_REQUIRE(n_models >= 1, "ssc_mlp_train_steps_many: n_models %d < 1", n_models);
+    if (n_models > 65535)
+        return set_error(SSC_EUNSUPPORTED, "ssc_mlp_train_steps_many: %d models > 65535 (one grid row each)", n_models);
+    SSC_REQUIRE(h_items != nullptr && d_items != nullptr, "ssc_mlp_train_steps_many: NULL item array");
+    static const int kIn[3] = {3, 4, 12}, kOut[3] = {2, 3, 8};
+    std::vector<ModelRange> ranges;
+    int first = -1, cls = 0, g_max = 0, steps_max = 0;
+    size_t lds_max = 0;
+    for (int p = 0; p < n_models; ++p) {
+        const ssc_mlp_train_many_item &it = h_items[p];
+        char who[56];
+        snprintf(who, sizeof who, "ssc_mlp_train_steps_many: model %d", p);
+        SSC_REQUIRE(it.n_steps >= 0, "%s: n_steps %d < 0", who, it.n_steps);
+        if (it.n_steps == 0) continue;     // skipped: its workgroups leave at once, nothing else of the item is read
+        const ssc_mlp_train_desc *net = &it.net;
+        if (int rc = train_check(who, net, it.d_X, it.d_Z, it.d_idx, it.batch, it.n_steps, it.d_workspace, it.workspace_bytes))
+            return rc;
+        if (!fused_eligible(net))
+            return set_error(SSC_EUNSUPPORTED, "%s: outside the fused kernel's reach (one hidden layer <= 512, in <= 12, out <= 8, "
+                             "SSC_DYN_TRAIN_GENERIC unset); train it with ssc_mlp_train_steps", who);
+        const int c = fused_class(net);
+        if (first < 0) { first = p; cls = c; }
+        SSC_REQUIRE(c == cls, "%s runs the <%d,%d> kernel, model %d the <%d,%d> kernel: one instantiation per call", who, kIn[c],
+                    kOut[c], first, kIn[cls], kOut[cls]);
+        int hd_pad = 16;
+        while (hd_pad < net->dims[1]) hd_pad <<= 1;
+        const size_t lds = fused_lds_floats(hd_pad, kFT / hd_pad, kIn[c], kOut[c]) * sizeof(float);
+        lds_max = lds > lds_max ? lds : lds_max;
+        const int G = (it.batch + kFRows - 1) / kFRows;
+        g_max = G > g_max ? G : g_max;
+        steps_max = it.n_steps > steps_max ? it.n_steps : steps_max;
+        auto add = [&](const void *ptr, size_t bytes, bool written) {
+            const uintptr_t b = reinterpret_cast<uintptr_t>(ptr);
+            ranges.push_back(ModelRange{b, b + bytes, p, written});
+        };
+        for (int l = 0; l < 2; ++l) {
+            const size_t nw = (size_t)net->dims[l] * net->dims[l + 1] * 4, nb = (size_t)net->dims[l + 1] * 4;
+            add(net->W[l], nw, true); add(net->mW[l], nw, true); add(net->vW[l], nw, true);
+            add(net->b[l], nb, true); add(net->mb[l], nb, true); add(net->vb[l], nb, true);
+        }
+        add(net->adam_t, 4, true);
+        if (it.d_loss) add(it.d_loss, (size_t)it.n_steps * 4, true);
+        add(it.d_workspace, it.workspace_bytes, true);
+        // the data sets' row counts are the caller's: their first row stands for them
+        add(it.d_X, (size_t)net->dims[0] * 4, false);
+        add(it.d_Z, (size_t)net->dims[2] * 4, false);
+        add(it.d_idx, (size_t)it.n_steps * it.batch * 4, false);
+    }
+    // what a model's workgroups write, nothing else writes or reads; what is only read may coincide
+    std::sort(ranges.begin(), ranges.end());
+    const size_t none = ranges.size();
+    for (size_t k = 0, top = none, top_w = none; k < ranges.size(); ++k) {
+        // top: the range before this one that reaches furthest, top_w: the written one that does
+        const ModelRange &r = ranges[k];
+        const size_t against = r.written ? top : top_w;
+        if (against != none) {
+            const ModelRange &o = ranges[against];
+            SSC_REQUIRE(o.end <= r.begin, "ssc_mlp_train_steps_many: models %d and %d: a %s range of model %d overlaps a %s range of model %d",
+                        std::min(o.model, r.model), std::max(o.model, r.model), r.written ? "written" : "read", r.model,
+                        o.written ? "written" : "read", o.model);
+        }
+        if (r.written && (top_w == none || r.end > ranges[top_w].end)) top_w = k;
+        if (top == none || r.end > ranges[top].end) top = k;
+    }
+    if (first < 0) return SSC_OK;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(fused_begin_many_kernel, dim3(blocks_for(n_models)), dim3(256), 0, s, d_items, n_models);
+    const int rc = cls == 0   ? launch_fused_many<3, 2>(d_items, n_models, g_max, lds_max, steps_max, s)
+                   : cls == 1 ? launch_fused_many<4, 3>(d_items, n_models, g_max, lds_max, steps_max, s)
+                              : launch_fused_many<12, 8>(d_items, n_models, g_max, lds_max, steps_max, s);
+    if (rc) return rc;
+    return check_launch("ssc_mlp_train_steps_many");
 }
 
 int ssc_mlp_train_step(const ssc_mlp_train_desc *net, const float *d_X, const float *d_Z, const int32_t *d_idx,

@@ -8,6 +8,7 @@ Everything here is a thin wrapper over the C ABI (include/ssc.h): tensors in, te
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -18,6 +19,27 @@ _stream = _ffi.stream         # the name this module had for it
 
 
 _PREC = {"f32": _ffi.SSC_PREC_F32, "bf16_mfma": _ffi.SSC_PREC_BF16_MFMA}
+
+
+def train_index_batches(n_old, n_new, nEpoch, fraction_use_new, batchsize, rng):
+    """The host half of ``Dyn_Model.train`` (dynamics_model.py:60-122): yields, per epoch, the int32 matrix
+    [n_batches, batchsize] of row numbers into the concatenation (old rows, new rows) -- every batch mixes
+    ``batchsize * fraction_use_new`` new rows with a walk through the shuffled old rows -- or ``None`` for an epoch
+    without a full batch.  The calls on ``rng`` and their order are the reference's."""
+    b_new = n_new if n_new < batchsize * fraction_use_new else int(batchsize * fraction_use_new)   # :60-67
+    b_old = int(batchsize - b_new)
+    perm_new = np.arange(n_new)
+    for _ in range(nEpoch):
+        old = rng.choice(np.arange(n_old), size=(n_old,), replace=False)                          # :78
+        if b_old > 0:
+            batches = []
+            for batch in range(int(np.floor(n_old / b_old))):                                     # :82
+                new_idx = rng.randint(0, n_new, (b_new,)) if n_new > 0 else np.zeros(0, np.int64)   # :88
+                batches.append(np.concatenate([old[batch * b_old:(batch + 1) * b_old], n_old + perm_new[new_idx]]))
+        else:
+            batches = [n_old + perm_new[b * b_new:(b + 1) * b_new] for b in range(int(np.floor(n_new / b_new)))]
+            perm_new = perm_new[rng.permutation(n_new)]                                           # :120-122
+        yield np.stack(batches).astype(np.int32) if batches else None
 
 
 class DynamicsModel:
@@ -147,6 +169,15 @@ class DynamicsModel:
         self.invalidate()
         return losses
 
+    def _train_sets(self, dataX, dataZ, dataX_new, dataZ_new):
+        """(X, Z) of a training: the old rows followed by the new ones, fp32 on the device"""
+        def f(a, cols):       # device tensors (collect_samples.TrainingSet) stay where they are
+            if torch.is_tensor(a):
+                return a.to(device=self.device, dtype=torch.float32).reshape(-1, cols)
+            return torch.as_tensor(np.asarray(a, np.float32).reshape(-1, cols), device=self.device)
+        return (torch.cat([f(dataX, self.in_dim), f(dataX_new, self.in_dim)]),
+                torch.cat([f(dataZ, self.out_dim), f(dataZ_new, self.out_dim)]))
+
     def train(self, dataX, dataZ, dataX_new, dataZ_new, nEpoch, fraction_use_new, batchsize=512, lr=0.001,
               rng=None):
         """``Dyn_Model.train`` (dynamics_model.py:52-171): every batch mixes ``batchsize*fraction_use_new``
@@ -154,29 +185,12 @@ class DynamicsModel:
         uploaded once; only index vectors travel per iteration.  Returns the mean training loss of the
         last epoch, like the reference's first return value."""
         rng = rng if rng is not None else np.random
-        def f(a, cols):       # device tensors (collect_samples.TrainingSet) stay where they are
-            if torch.is_tensor(a):
-                return a.to(device=self.device, dtype=torch.float32).reshape(-1, cols)
-            return torch.as_tensor(np.asarray(a, np.float32).reshape(-1, cols), device=self.device)
         n_old, n_new = len(dataX), len(dataX_new)
-        X = torch.cat([f(dataX, self.in_dim), f(dataX_new, self.in_dim)])
-        Z = torch.cat([f(dataZ, self.out_dim), f(dataZ_new, self.out_dim)])
-        b_new = n_new if n_new < batchsize * fraction_use_new else int(batchsize * fraction_use_new)   # :60-67
-        b_old = int(batchsize - b_new)
-        perm_new = np.arange(n_new)
+        X, Z = self._train_sets(dataX, dataZ, dataX_new, dataZ_new)
         epoch_losses = []
-        for _ in range(nEpoch):
-            old = rng.choice(np.arange(n_old), size=(n_old,), replace=False)                          # :78
-            if b_old > 0:
-                batches = []
-                for batch in range(int(np.floor(n_old / b_old))):                                     # :82
-                    new_idx = rng.randint(0, n_new, (b_new,)) if n_new > 0 else np.zeros(0, np.int64)   # :88
-                    batches.append(np.concatenate([old[batch * b_old:(batch + 1) * b_old], n_old + perm_new[new_idx]]))
-            else:
-                batches = [n_old + perm_new[b * b_new:(b + 1) * b_new] for b in range(int(np.floor(n_new / b_new)))]
-                perm_new = perm_new[rng.permutation(n_new)]                                           # :120-122
-            if batches:       # the epoch's index vectors travel in one copy, its steps are enqueued by one call
-                idx = torch.as_tensor(np.stack(batches).astype(np.int32), device=self.device)
+        for batches in train_index_batches(n_old, n_new, nEpoch, fraction_use_new, batchsize, rng):
+            if batches is not None:   # the epoch's index vectors travel in one copy, its steps are enqueued by one call
+                idx = torch.as_tensor(batches, device=self.device)
                 epoch_losses.append(self.train_steps(X, Z, idx, lr=lr))
         # the only device -> host read of the whole training: the mean loss of the last epoch
         return float(epoch_losses[-1].mean().item()) if epoch_losses else 0.0
@@ -299,6 +313,169 @@ class DynamicsModel:
                                                     _ffi.ptr(A), _ffi.ptr(S), prec, _ffi.ptr(ws), ws.numel(),
                                                     _ffi.stream()))
         return S
+
+
+# ---- a population of dynamics models (one per seed of a sweep) trained together ----------------------------------------
+DYN_POPULATION_GROUPED = True       # False: every model trains through its own train_steps
+# the smallest group one ssc_mlp_train_steps_many call serves; smaller groups train alone (profiles/dyn_train_population)
+DYN_POPULATION_MIN_GROUP = 2
+
+
+def _per_model(value, n, what):
+    """one value for every model, or one per model"""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != n:
+            raise ValueError("%s: %d values for %d models" % (what, len(value), n))
+        return list(value)
+    return [value] * n
+
+
+class DynamicsModelPopulation:
+    """The dynamics models of a population (the seeds ``SmartStart_DDPG_Baselines_experimenter.py`` fans out) trained
+    with one launch per step for all of them: ``ssc_mlp_train_steps_many``.  Every model ends up, bit for bit, where its
+    own ``train_steps`` / ``train`` calls with the same arguments leave it.
+
+    Models are grouped by the kernel instantiation their own call dispatches; a group of at least
+    ``DYN_POPULATION_MIN_GROUP`` models goes through one many-call, everything else -- smaller groups, shapes outside the
+    fused kernel (more than one hidden layer, hidden > 512, in > 12, out > 8), another device than the first model's --
+    through its own ``train_steps``.  ``ways`` names the way per model, ``fused`` tells whether all went grouped."""
+
+    def __init__(self, models):
+        self.models = list(models)
+        if not self.models:
+            raise ValueError("DynamicsModelPopulation: no models")
+        self._items = {}         # way -> population.DeviceItems of its group
+        self._sent = {}          # way -> the bytes last uploaded
+        self._loss = None        # the grouped models' losses of one call, cloned before they are handed out
+        self._idx = None         # train(): the epoch's index matrices of all models, one upload
+
+    @staticmethod
+    def way_of(model):
+        """``"fused<IN,OUT>"`` -- the instantiation ``ssc_mlp_train_steps`` dispatches for the model -- or ``"alone"``"""
+        dims = [int(model.W[0].shape[0])] + [int(w.shape[1]) for w in model.W]
+        if os.environ.get("SSC_DYN_TRAIN_GENERIC") is not None or len(dims) != 3 or dims[0] > 12 or dims[1] > 512 or dims[2] > 8:
+            return "alone"
+        return "fused<3,2>" if dims[0] <= 3 and dims[2] <= 2 else "fused<4,3>" if dims[0] <= 4 and dims[2] <= 3 else "fused<12,8>"
+
+    @property
+    def ways(self):
+        ways = [self.way_of(m) for m in self.models]
+        dev0 = getattr(self.models[0], "device", None)
+        for p, m in enumerate(self.models):
+            if not DYN_POPULATION_GROUPED or getattr(m, "device", None) != dev0:
+                ways[p] = "alone"
+        return [w if w == "alone" or ways.count(w) >= DYN_POPULATION_MIN_GROUP else "alone" for w in ways]
+
+    @property
+    def fused(self):
+        return all(w != "alone" for w in self.ways)
+
+    def train_steps(self, Xs, Zs, idxs, lr=0.001):
+        """``models[p].train_steps(Xs[p], Zs[p], idxs[p], lr[p])`` for every p; ``idxs[p]`` is int32 [n_steps_p, B_p] on the
+        device, or ``None``: the model is skipped.  ``lr``: one value or one per model.  Returns the list of per-step loss
+        tensors (``None`` for a skipped model).  No host synchronisation."""
+        P = len(self.models)
+        if not (len(Xs) == len(Zs) == len(idxs) == P):
+            raise ValueError("DynamicsModelPopulation.train_steps: one X, Z and idx per model")
+        lrs = _per_model(lr, P, "lr")
+        ways, losses = self.ways, [None] * P
+        for p, m in enumerate(self.models):
+            if ways[p] == "alone" and idxs[p] is not None:
+                losses[p] = m.train_steps(Xs[p], Zs[p], idxs[p], lr=lrs[p])
+        for way in sorted(set(ways) - {"alone"}):
+            group = [p for p in range(P) if ways[p] == way]
+            self._train_group(way, group, Xs, Zs, idxs, lrs, losses)
+        return losses
+
+    def _train_group(self, way, group, Xs, Zs, idxs, lrs, losses):
+        from .population import DeviceItems
+        lib, device = self.models[group[0]].lib, self.models[group[0]].device
+        work = [p for p in group if idxs[p] is not None and idxs[p].shape[0] > 0]
+        if not work:
+            return
+        seg = lambda n: (int(n) + 127) & ~127       # every model's losses start 512-byte aligned, like a tensor of their own
+        total = sum(seg(idxs[p].shape[0]) for p in work)
+        if self._loss is None or self._loss.numel() < total or self._loss.device != device:
+            self._loss = torch.empty(max(total, 64), dtype=torch.float32, device=device)
+        fresh = (_ffi.MlpTrainManyItem * len(group))()
+        keep, at = [], 0          # keep: tensors made contiguous for this call stay alive until it is enqueued
+        with torch.cuda.device(device):
+            for it, p in zip(fresh, group):
+                if p not in work:
+                    continue      # n_steps = 0: the rest of the item is not read
+                m = self.models[p]
+                n_steps, B = (int(v) for v in idxs[p].shape)
+                X, Z, idx = Xs[p].contiguous(), Zs[p].contiguous(), idxs[p].contiguous()
+                keep += [X, Z, idx]
+                it.net = m._train_desc(lrs[p])
+                ws = m._workspace(lib.ssc_mlp_train_workspace_bytes(ctypes.byref(it.net), B))
+                it.d_X, it.d_Z, it.d_idx, it.batch, it.n_steps = X.data_ptr(), Z.data_ptr(), idx.data_ptr(), B, n_steps
+                it.d_loss = self._loss.data_ptr() + 4 * at
+                it.d_workspace, it.workspace_bytes = ws.data_ptr(), ws.numel()
+                at += seg(n_steps)
+            di = self._items.get(way)
+            if di is None or di.n != len(group) or di.device != device:
+                di = self._items[way] = DeviceItems(_ffi.MlpTrainManyItem, len(group), device)
+                self._sent.pop(way, None)
+            image = bytes(fresh)
+            if self._sent.get(way) != image:          # a pointer, a shape, a step count or a constant changed
+                di.wait()
+                ctypes.memmove(di.h_ptr, ctypes.addressof(fresh), len(image))
+                di.upload()
+                self._sent[way] = image
+            _ffi.check(lib.ssc_mlp_train_steps_many(di.h_ptr, di.d_ptr, len(group), _ffi.stream()))
+            out = self._loss[:total].clone()
+        at = 0
+        for p in work:
+            n_steps = int(idxs[p].shape[0])
+            losses[p] = out[at:at + n_steps]
+            at += seg(n_steps)
+            self.models[p].invalidate()
+
+    def train(self, data, nEpoch, fraction_use_new, batchsize=512, lr=0.001, rngs=None):
+        """``models[p].train(*data[p], nEpoch[p], fraction_use_new[p], batchsize[p], lr[p], rng=rngs[p])`` for every p with
+        one many-call per epoch; ``data[p]`` = (dataX, dataZ, dataX_new, dataZ_new).  ``nEpoch``, ``fraction_use_new``,
+        ``batchsize`` and ``lr`` take one value or one per model.  ``rngs``: one generator PER MODEL -- a stream shared
+        between models cannot reproduce their own runs.  Returns the list of last-epoch mean losses, read back in one
+        device -> host copy for the whole population."""
+        P = len(self.models)
+        if not isinstance(rngs, (list, tuple)) or len(rngs) != P or any(r is None or r is np.random for r in rngs) \
+                or len({id(r) for r in rngs}) != P:
+            raise ValueError("DynamicsModelPopulation.train: rngs must hold one generator of its own per model")
+        if len(data) != P:
+            raise ValueError("DynamicsModelPopulation.train: one data tuple per model")
+        nEpochs, fracs = _per_model(nEpoch, P, "nEpoch"), _per_model(fraction_use_new, P, "fraction_use_new")
+        sizes, lrs = _per_model(batchsize, P, "batchsize"), _per_model(lr, P, "lr")
+        sets = [m._train_sets(*d) for m, d in zip(self.models, data)]
+        Xs, Zs = [s[0] for s in sets], [s[1] for s in sets]
+        gens = [train_index_batches(len(d[0]), len(d[2]), nEpochs[p], fracs[p], sizes[p], rngs[p]) for p, d in enumerate(data)]
+        device = self.models[0].device
+        last = [None] * P
+        for _ in range(max(nEpochs)):
+            host = [next(g, None) for g in gens]
+            live = [p for p in range(P) if host[p] is not None]
+            if not live:
+                continue
+            # the epoch's index matrices of all models travel in one copy, its steps are enqueued by one call per group
+            flat = np.concatenate([host[p].reshape(-1) for p in live])
+            if self._idx is None or self._idx.numel() < flat.size or self._idx.device != device:
+                self._idx = torch.empty(max(flat.size, 1024), dtype=torch.int32, device=device)
+            self._idx[:flat.size].copy_(torch.from_numpy(flat))
+            idxs, at = [None] * P, 0
+            for p in live:
+                view = self._idx[at:at + host[p].size].view(host[p].shape)
+                idxs[p] = view if self.models[p].device == device else view.to(self.models[p].device)
+                at += host[p].size
+            for p, l in enumerate(self.train_steps(Xs, Zs, idxs, lr=lrs)):
+                if l is not None:
+                    last[p] = l
+        got = [p for p in range(P) if last[p] is not None]
+        out = [0.0] * P
+        if got:      # the only device -> host read of the whole training
+            means = torch.stack([last[p].mean().to(device) for p in got]).cpu()
+            for k, p in enumerate(got):
+                out[p] = float(means[k].item())
+        return out
 
 
 def mpc_sampling(N, low, high, seed, problem_id0=0, t=0, t_base=None, active=None, live_list=None, n_live=None):
