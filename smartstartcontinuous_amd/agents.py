@@ -22,6 +22,7 @@ from .numerical import (distances_left, elliptical_euclidean_distance_function_g
                         get_start_waypoints_final_states_steps, path_deltas_stds_and_means_per_dim,
                         path_shortcutter, radii_calc)
 from .obs_rms import ObsRms
+from .population import DeviceItems, IndexDraw
 from .replay_buffer import ReplayBuffer
 from .vec_env import ActorPolicy
 
@@ -825,29 +826,162 @@ POPULATION_WIDE_MIN_GROUP = 2
 POPULATION_POPART_MIN_GROUP = 2
 
 
+def ddpg_population_route(facts):
+    """The learner way of every agent of a :class:`DDPGPopulation` from per-agent facts only: ``facts[p]`` = (agent p's
+    ``ssc_ddpg_desc``, popart, has statistics, the addresses of its nine parameter / optimiser arrays).  -> (``ways``, the
+    groups as [(way, [agent, ...]), ...] in launch order: one ``"one_workgroup"`` group per (obs_dim, lastLayerTanh,
+    statistics) key, then the ``"wide"`` group, then the ``"wide_popart"`` one).  Which learner a shape takes is the
+    library's ``ssc_ddpg_learner_path``, the ``SSC_DDPG_INTERPRETER`` / ``SSC_DDPG_WIDE`` switches included."""
+    P = len(facts)
+    ptrs = [x for f in facts for x in f[3]]
+    if len(set(ptrs)) < len(ptrs):                           # two workgroups on one array would race
+        return ("alone",) * P, []
+    lib, path_way = _ffi.lib(), {_ffi.SSC_DDPG_PATH_FIXED: "one_workgroup", _ffi.SSC_DDPG_PATH_WIDE: "wide"}
+    ways = ["wide_popart" if popart else path_way.get(lib.ssc_ddpg_learner_path(ctypes.byref(d), 1, int(rms)), "alone")
+            for d, popart, rms, _ in facts]
+    keys = {}
+    for p, (d, _, rms, _) in enumerate(facts):
+        if ways[p] == "one_workgroup":
+            keys.setdefault((d.obs_dim, bool(d.last_layer_tanh), bool(rms)), []).append(p)
+    if len(keys) != 1 or ways.count("one_workgroup") != P:   # (a uniform one-workgroup population is one launch regardless)
+        if not POPULATION_GROUPED_WIDE:
+            return ("alone",) * P, []
+        for way, least in (("wide", POPULATION_WIDE_MIN_GROUP), ("wide_popart", POPULATION_POPART_MIN_GROUP)):
+            if ways.count(way) < least:
+                ways = ["alone" if w == way else w for w in ways]
+    groups = [("one_workgroup", ps) for ps in keys.values()]
+    groups += [(way, [p for p in range(P) if ways[p] == way]) for way in ("wide", "wide_popart") if way in ways]
+    return tuple(ways), groups
+
+
+def _loss_rows(block, n, copy):
+    """agent after agent, its rows [n_p, 2] of a loss block (None where n_p is 0) -- views of a fresh copy with ``copy``"""
+    block, out, off = block.clone() if copy else block, [], 0
+    for k in n:
+        out.append(block[off:off + k] if k > 0 else None)
+        off += k
+    return out
+
+
+class _LearnerGroup:
+    """The agents ``ps`` of a population on one grouped learner launch: items, index and loss tensors, built when the call's
+    signature changes and kept until it changes again.  Our own draw is one :class:`IndexDraw` for all rings where at
+    least ``shared_draw`` agents train and all have one batch size <= 64 (the sampler's one-wave kernel; agent p reads its
+    first n[p] batches of its row), else one ``ssc_replay_sample`` per ring."""
+    shared_draw = 2
+
+    def __init__(self, pop, way, ps, descs, views, n, batch_idx, rms):
+        ag, dev = pop.agents, pop.device
+        self.lib, self.device, self.way, self.ps, self.n = pop.lib, dev, way, ps, [n[p] for p in ps]
+        active = [p for p in ps if n[p] > 0]
+        sizes = {ag[p].batch_size for p in active}
+        self.draw = None
+        if batch_idx is None and len(active) >= self.shared_draw and len(sizes) == 1 and max(sizes) <= 64:
+            self.draw = IndexDraw(len(active), max(n[p] for p in active), max(sizes), dev)
+        self.idx = [None if n[p] == 0 else batch_idx[p] if batch_idx is not None else self.draw.idx[active.index(p)] if self.draw
+                    else torch.empty((n[p], ag[p].batch_size), dtype=torch.int32, device=dev) for p in ps]
+        self.losses = torch.empty((sum(self.n), 2), dtype=torch.float32, device=dev)
+        self.rows = _loss_rows(self.losses, self.n, False)
+
+    def _fill(self, items, descs, views, rms):
+        for it, p, k, row, idx in zip(items, self.ps, self.n, self.rows, self.idx):
+            v = views[p]
+            it.ddpg, it.n_iters, it.d_rms = descs[p], k, rms[p]
+            it.replay = _ffi.ReplayView(*(x.data_ptr() for x in v), v[0].shape[0])
+            if k > 0:
+                it.d_losses, it.d_batch_idx = row.data_ptr(), idx.data_ptr()
+
+    def train(self, replays, out, copy):
+        """one call: the index draw (``replays``: train_from; None: train_on), the launch, the agents' slots of ``out``"""
+        if not any(self.n):
+            return
+        with torch.cuda.device(self.device):
+            if replays is not None and self.draw is not None:
+                self.draw.draw([replays[p].take_sample_key(k, self.draw.B) for p, k in zip(self.ps, self.n) if k > 0])
+            elif replays is not None:                    # every ring draws under its own key, as its sample_indices would
+                for p, k, idx in zip(self.ps, self.n, self.idx):
+                    if k > 0:
+                        seed, counter0, size = replays[p].take_sample_key(k, idx.shape[1])
+                        _ffi.check(self.lib.ssc_replay_sample(seed, counter0, size, k, idx.shape[1], _ffi.ptr(idx),
+                                                              _ffi.stream(self.device)))
+            self._launch()
+            rows = _loss_rows(self.losses, self.n, True) if copy else self.rows
+        for p, r in zip(self.ps, rows):
+            out[p] = r
+
+
+class _OneWorkgroupGroup(_LearnerGroup):
+    """agents of one (obs_dim, lastLayerTanh, statistics) key on ``ssc_ddpg_train_many``, one workgroup each"""
+    shared_draw = 1
+
+    def __init__(self, pop, way, ps, descs, views, n, batch_idx, rms):
+        super().__init__(pop, way, ps, descs, views, n, batch_idx, rms)
+        self.items = DeviceItems(_ffi.DdpgManyItem, len(ps), self.device)
+        self._fill(self.items.items, descs, views, rms)
+        self.items.upload()
+
+    def _launch(self):
+        _ffi.check(self.lib.ssc_ddpg_train_many(self.items.h_ptr, self.items.d_ptr, len(self.ps), _ffi.stream(self.device)))
+
+
+class _PlanGroup(_LearnerGroup):
+    """the ``"wide"`` agents on ``ssc_ddpg_train_many_wide`` or the ``"wide_popart"`` ones on ``ssc_ddpg_train_many_popart``:
+    host items, each agent on its own workspace (the one its ``train_on`` keeps), and the plan the library builds from them
+    (``plan``: its pinned-host and device copies)"""
+
+    def __init__(self, pop, way, ps, descs, views, n, batch_idx, rms):
+        super().__init__(pop, way, ps, descs, views, n, batch_idx, rms)
+        lib, popart = self.lib, way == "wide_popart"
+        item_t, ws_bytes, plan_bytes, plan, self._train = (
+            (_ffi.DdpgManyPopartItem, lib.ssc_ddpg_train_popart_workspace_bytes, lib.ssc_ddpg_train_many_popart_plan_bytes,
+             lib.ssc_ddpg_train_many_popart_plan, lib.ssc_ddpg_train_many_popart) if popart else
+            (_ffi.DdpgManyWideItem, lib.ssc_ddpg_train_workspace_bytes, lib.ssc_ddpg_train_many_wide_plan_bytes,
+             lib.ssc_ddpg_train_many_wide_plan, lib.ssc_ddpg_train_many_wide))
+        self.items = (item_t * len(ps))()
+        self._fill(self.items, descs, views, rms)
+        self.ws = []                                     # (alive as long as the plan names them)
+        for it, p in zip(self.items, ps):
+            a = pop.agents[p]
+            if popart:
+                it.d_ret_rms = a.ret_rms.block.data_ptr()
+            need = int(ws_bytes(ctypes.byref(descs[p])))
+            ws = getattr(a, "_train_ws", None)
+            if ws is None or ws.numel() < need:
+                ws = a._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            it.d_workspace, it.workspace_bytes = ws.data_ptr(), ws.numel()
+            self.ws.append(ws)
+        nbytes = int(plan_bytes(len(ps)))
+        self.plan = DeviceItems(ctypes.c_uint8, nbytes, self.device)
+        _ffi.check(plan(ctypes.addressof(self.items), len(ps), self.plan.h_ptr, nbytes))
+        self.plan.upload()
+
+    def _launch(self):
+        _ffi.check(self._train(ctypes.addressof(self.items), self.plan.h_ptr, self.plan.d_ptr, len(self.ps), _ffi.stream(self.device)))
+
+
 class DDPGPopulation:
     """P independent :class:`DDPG_Baselines_agent` objects -- seeds x hyper-parameter grids, what the reference fans out
     over processes (experimenter.py) -- trained by ONE learner launch, one workgroup per agent (``ssc_ddpg_train_many``),
     on batch indices drawn by one launch (``ssc_replay_sample_many``).  The agents are wrapped, not copied: every result is
     bit for bit what ``agent.train_from`` / ``agent.train_on`` gives agent by agent.
 
-    The launch serves the shipped shape only (64-32 actor and critic, batch 64, one action, obs_dim 2 or 3, no LayerNorm /
-    critic_l2_reg / clip_norm / Pop-Art; one obs_dim and lastLayerTanh for all, normalize_observations for all or for
-    none, no array shared by two agents) and only while neither ``SSC_DDPG_INTERPRETER`` nor ``SSC_DDPG_WIDE`` is set.
-    ``fused`` tells whether the last call went that way as a whole.
+    The launch serves the agents ``ssc_ddpg_learner_path`` -- the library's own rule, the ``SSC_DDPG_INTERPRETER`` /
+    ``SSC_DDPG_WIDE`` switches included -- sends to the one-workgroup kernel (the shipped 64-32 shape at batch 64), one
+    launch per (obs_dim, lastLayerTanh, statistics) key, and no array may be shared by two agents.  ``fused`` tells whether
+    the last call went in one such launch as a whole.
 
-    Any other population is split four ways (``ways``: one of ``"one_workgroup"``, ``"wide"``, ``"wide_popart"``,
-    ``"alone"`` per agent, for the last call).  The agents ``ssc_ddpg_learner_path`` -- the library's own rule, the two
-    switches included -- sends to the multi-workgroup kernels (wider layers, other batch sizes, LayerNorm, critic_l2_reg, clip_norm, statistics on a
-    shape without a normalising one-workgroup build) train together in the grouped launches of
-    ``ssc_ddpg_train_many_wide``: 2 launches per iteration for all of them (3 with critic_l2_reg / clip_norm) on a plan
-    this object owns.  The agents of the shipped shape go through ``ssc_ddpg_train_many`` as child populations, one per
-    (obs_dim, lastLayerTanh, statistics) key.  The Pop-Art agents (``normalize_returns`` with ``enable_popart``), of any
-    shape, train together in the grouped launches of ``ssc_ddpg_train_many_popart``: 4 launches per iteration for all of
-    them (5 with critic_l2_reg / clip_norm), each agent on its own ``ret_rms`` block and workspace.  Everything else -- the
-    step interpreter's shapes, the tiled 64-32 path, a lone wide agent, fewer Pop-Art agents than
-    ``POPULATION_POPART_MIN_GROUP``, agents that share an array -- runs ``agent.train_from`` / ``agent.train_on`` as before,
-    and so does every agent when ``POPULATION_GROUPED_WIDE`` is False.
+    :func:`ddpg_population_route` gives every agent its way (``ways``: one of ``"one_workgroup"``, ``"wide"``,
+    ``"wide_popart"``, ``"alone"`` per agent, for the last call) and the groups.  The agents the library sends to the
+    multi-workgroup kernels (wider layers, other batch sizes, LayerNorm, critic_l2_reg, clip_norm, statistics on a shape
+    without a normalising one-workgroup build) train together in the grouped launches of ``ssc_ddpg_train_many_wide``: 2
+    launches per iteration for all of them (3 with critic_l2_reg / clip_norm) on a plan this object owns.  The Pop-Art
+    agents (``normalize_returns`` with ``enable_popart``), of any shape, train together in the grouped launches of
+    ``ssc_ddpg_train_many_popart``: 4 launches per iteration for all of them (5 with critic_l2_reg / clip_norm), each agent
+    on its own ``ret_rms`` block and workspace.  Everything else -- the step interpreter's shapes, the tiled 64-32 path,
+    fewer wide agents than ``POPULATION_WIDE_MIN_GROUP`` or Pop-Art ones than ``POPULATION_POPART_MIN_GROUP``, agents that
+    share an array -- runs ``agent.train_from`` / ``agent.train_on`` as before, and so does every agent of a population
+    that is not one launch as a whole when ``POPULATION_GROUPED_WIDE`` is False.  A call runs the lone agents first, then
+    the one-workgroup groups, the wide group and the Pop-Art group.
 
     Index and loss tensors and the pinned-host and device copies of the launch descriptors stay with the population and
     are rebuilt only when a pointer, an iteration count or a ring changes: in steady state a call uploads the P sampling
@@ -857,8 +991,6 @@ class DDPGPopulation:
     What the agents of a sweep are compared by comes in one launch per phase too: :meth:`evaluate_device` (eval/return,
     eval/Q) and :meth:`get_stats_device` (the ``get_stats`` diagnostics), for any mix of network shapes -- and so does the
     adaption interval of the agents with parameter-space noise: :meth:`param_noise_cycle`."""
-
-    B = 64
 
     def __init__(self, agents):
         self.agents = list(agents)
@@ -872,34 +1004,13 @@ class DDPGPopulation:
         self.ways = None
         self._sig = None
         self._groups = None
-        self._items_event = self._keys_event = None
 
     def __len__(self):
         return len(self.agents)
 
-    # ---- which way a call goes -------------------------------------------------------------------
-    @staticmethod
-    def _forced_elsewhere():
-        """the A/B switches of ddpg_train_any keep their meaning: they send every agent to another learner"""
-        return any((os.environ.get(k) or "")[:1] == "1" for k in ("SSC_DDPG_INTERPRETER", "SSC_DDPG_WIDE"))
-
-    @classmethod
-    def _shipped_shape(cls, a):
-        c = a._critic_desc
-        return (a.batch_size == cls.B and a.obs_dim in (2, 3) and a.act_dim == 1 and (a.h1, a.h2) == (64, 32)
-                and (c.h1, c.h2) == (64, 32) and "ln1_g" not in a.weights and a.critic_l2_reg == 0.0 and a.clip_norm is None
-                and not a.popart)
-
     @staticmethod
     def _arrays(a):
         return (a.actor_flat, a.critic_flat, a.target_actor_flat, a.target_critic_flat, *a._adam_actor, *a._adam_critic, a._adam_t)
-
-    def _fusable(self, ptrs):
-        ag = self.agents
-        return (not self._forced_elsewhere() and all(self._shipped_shape(a) for a in ag)
-                and all(a.obs_dim == ag[0].obs_dim and a.lastLayerTanh == ag[0].lastLayerTanh for a in ag)
-                and all((a.obs_rms is None) == (ag[0].obs_rms is None) for a in ag)
-                and len(set(ptrs)) == len(ptrs))
 
     # ---- the two public calls --------------------------------------------------------------------
     def _iters(self, n_iters):
@@ -917,38 +1028,15 @@ class DDPGPopulation:
         tensors [n_iters_p, 2]; None for an agent whose ring holds fewer than ``batch_size`` records (it is left exactly as
         it is).  ``n_iters``: None (each agent's ``num_train_iterations``), one count, or one per agent.  Every ring's index
         stream (``seed``, batches drawn so far) moves exactly as its own ``sample_indices`` would move it."""
-        return self._train_from(replays, n_iters, copy)
-
-    def _train_from(self, replays, n_iters, copy):
-        # (the body of train_from: a split population calls it on its children, which are no calls of the public method)
         replays = list(replays)
         if len(replays) != len(self.agents):
             raise ValueError("one replay ring per agent")
         n = [k if len(r) >= a.batch_size else 0 for k, r, a in zip(self._iters(n_iters), replays, self.agents)]
-        views = [(r.s, r.a, r.r, r.t, r.s2) for r in replays]
-        if not self._prepare(views, n, None):
-            return self._train_split(replays, views, None, n, copy)
-        st = self._state
-        if st["active"]:
-            with torch.cuda.device(self.device):
-                if self._keys_event is not None:
-                    self._keys_event.synchronize()           # the last upload has left the pinned keys
-                for slot, p in enumerate(st["active"]):
-                    k = st["keys"][slot]
-                    k.seed, k.counter0, k.size = replays[p].take_sample_key(n[p], self.B)
-                st["d_keys"].copy_(st["h_keys"], non_blocking=True)
-                self._keys_event = torch.cuda.Event()
-                self._keys_event.record()
-                _ffi.check(self.lib.ssc_replay_sample_many(st["h_keys"].data_ptr(), st["d_keys"].data_ptr(), len(st["active"]),
-                                                           st["n_max"], self.B, _ffi.ptr(st["idx"]), _ffi.stream(self.device)))
-        return self._launch(copy)
+        return self._train([(r.s, r.a, r.r, r.t, r.s2) for r in replays], n, None, replays, copy)
 
     def train_on(self, views, batch_idx, n_iters, copy=False):
         """The index-explicit form: ``views[p]`` = agent p's (s, a, r, t, s2) device arrays, ``batch_idx[p]`` int32
         [n_iters[p], agent p's batch_size] (ignored where ``n_iters[p]`` is 0) -> list of loss tensors, None where ``n_iters[p]`` is 0."""
-        return self._train_on(views, batch_idx, n_iters, copy)
-
-    def _train_on(self, views, batch_idx, n_iters, copy):
         n = self._iters(n_iters)
         views, batch_idx = [tuple(v) for v in views], list(batch_idx)
         if len(views) != len(self.agents) or len(batch_idx) != len(self.agents):
@@ -956,15 +1044,25 @@ class DDPGPopulation:
         for a, k, idx in zip(self.agents, n, batch_idx):
             if k > 0 and (tuple(idx.shape) != (k, a.batch_size) or idx.dtype != torch.int32 or not idx.is_contiguous()):
                 raise ValueError(f"batch_idx must be contiguous int32 [{k}, {a.batch_size}]")
-        if not self._prepare(views, n, batch_idx):
-            return self._train_split(None, views, batch_idx, n, copy)
-        return self._launch(copy)
+        return self._train(views, n, batch_idx, None, copy)
 
-    # ---- descriptors -----------------------------------------------------------------------------
+    def _train(self, views, n, batch_idx, replays, copy):
+        """the call: the agents that train alone, one after the other, then every group's launch in ``_groups`` order;
+        ``replays`` (train_from) or ``batch_idx`` (train_on) is None"""
+        self._prepare(views, n, batch_idx)
+        ag, out = self.agents, [None] * len(self.agents)
+        for p, way in enumerate(self.ways):
+            if way == "alone" and n[p] > 0:
+                out[p] = ag[p].train_from(replays[p], n[p]) if batch_idx is None else ag[p].train_on(*views[p], batch_idx[p], n[p])
+        for g in self._groups:
+            g.train(replays, out, copy)
+        return out
+
     def _prepare(self, views, n, batch_idx):
-        """Decide the way of this call and bring the launch descriptors up to date -> ``fused``."""
+        """Route the agents (-> ``ways``, ``fused``) and build the groups (-> ``_groups``) unless nothing they depend on
+        changed since the last call."""
         ag = self.agents
-        ptrs = [t.data_ptr() for a in ag for t in self._arrays(a)]
+        ptrs = [tuple(t.data_ptr() for t in self._arrays(a)) for a in ag]
         rms = [None if a.obs_rms is None else a._rms_block().data_ptr() for a in ag]
         switches = tuple(os.environ.get(k) for k in ("SSC_DDPG_INTERPRETER", "SSC_DDPG_WIDE")) + (POPULATION_GROUPED_WIDE, POPULATION_WIDE_MIN_GROUP, POPULATION_POPART_MIN_GROUP)
         sig = (switches, tuple(ptrs), tuple(rms), tuple(None if a.ret_rms is None else a.ret_rms.block.data_ptr() for a in ag), tuple(n),
@@ -974,191 +1072,14 @@ class DDPGPopulation:
                       a.popart) for a in ag),
                torch.cuda.current_stream(self.device).cuda_stream)
         if sig == self._sig:
-            return self.fused
-        self._sig, self._state, self._groups = sig, None, None
-        self.fused = self._fusable(ptrs)
-        self.ways = ("one_workgroup",) * len(ag)
-        if not self.fused:
-            self._split(views, n, batch_idx, ptrs, rms)
-            return False
-        P, B = len(ag), self.B
-        active = [p for p in range(P) if n[p] > 0]
-        st = dict(active=active, n=list(n), n_max=max(n) if active else 0)
+            return
+        descs = [a.ddpg_desc() for a in ag]
+        self.ways, groups = ddpg_population_route([(d, a.popart, r is not None, x) for d, a, r, x in zip(descs, ag, rms, ptrs)])
+        self.fused = groups == [("one_workgroup", list(range(len(ag))))]
         with torch.cuda.device(self.device):
-            st["losses"] = torch.empty((sum(n), 2), dtype=torch.float32, device=self.device)
-            if batch_idx is None and active:      # our own draw: rows [slot][n_max][64], agent p reads its first n[p] batches
-                st["idx"] = torch.empty((len(active), st["n_max"], B), dtype=torch.int32, device=self.device)
-                st["h_keys"] = torch.empty(len(active) * ctypes.sizeof(_ffi.ReplaySampleKey), dtype=torch.uint8).pin_memory()
-                st["d_keys"] = torch.empty(st["h_keys"].numel(), dtype=torch.uint8, device=self.device)
-                st["keys"] = (_ffi.ReplaySampleKey * len(active)).from_address(st["h_keys"].data_ptr())
-            items = (_ffi.DdpgManyItem * P)()
-            off, rows = 0, []
-            for p, a in enumerate(ag):
-                it, v = items[p], views[p]
-                it.ddpg = a.ddpg_desc()
-                it.replay = _ffi.ReplayView(*(x.data_ptr() for x in v), v[0].shape[0])
-                it.n_iters = n[p]
-                rows.append(st["losses"][off:off + n[p]] if n[p] > 0 else None)
-                if n[p] > 0:
-                    it.d_losses = rows[-1].data_ptr()
-                    it.d_batch_idx = (st["idx"][active.index(p)] if batch_idx is None else batch_idx[p]).data_ptr()
-                it.d_rms = rms[p]
-                off += n[p]
-            st["rows"], nbytes = rows, ctypes.sizeof(items)
-            if self._items_event is not None:
-                self._items_event.synchronize()
-            st["h_items"] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-            ctypes.memmove(st["h_items"].data_ptr(), items, nbytes)
-            st["d_items"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            st["d_items"].copy_(st["h_items"], non_blocking=True)
-            self._items_event = torch.cuda.Event()
-            self._items_event.record()
-        self._state = st
-        return True
-
-    # ---- a population the single launch does not serve: three ways ---------------------------------
-    def _split(self, views, n, batch_idx, ptrs, rms):
-        """Route every agent (-> ``ways``) and build what the grouped routes keep between calls (-> ``_groups``)."""
-        ag, P = self.agents, len(self.agents)
-        ways = ["alone"] * P
-        if POPULATION_GROUPED_WIDE and len(set(ptrs)) == len(ptrs):
-            for p, a in enumerate(ag):
-                if a.popart:
-                    ways[p] = "wide_popart"
-                    continue
-                path = self.lib.ssc_ddpg_learner_path(ctypes.byref(a.ddpg_desc()), 1, int(rms[p] is not None))
-                ways[p] = {_ffi.SSC_DDPG_PATH_WIDE: "wide", _ffi.SSC_DDPG_PATH_FIXED: "one_workgroup"}.get(path, "alone")
-            if ways.count("wide") < POPULATION_WIDE_MIN_GROUP:
-                ways = ["alone" if w == "wide" else w for w in ways]
-            if ways.count("wide_popart") < POPULATION_POPART_MIN_GROUP:
-                ways = ["alone" if w == "wide_popart" else w for w in ways]
-        self.ways = tuple(ways)
-        children = {}
-        for p, a in enumerate(ag):
-            if ways[p] == "one_workgroup":
-                children.setdefault((a.obs_dim, bool(a.lastLayerTanh), rms[p] is not None), []).append(p)
-        wide, pop = ([p for p in range(P) if ways[p] == w] for w in ("wide", "wide_popart"))
-        self._groups = dict(alone=[p for p in range(P) if ways[p] == "alone"],
-                            children=[(ps, DDPGPopulation([ag[p] for p in ps])) for ps in children.values()],
-                            wide=self._wide_state(wide, views, n, batch_idx, rms) if wide else None,
-                            wide_popart=self._wide_state(pop, views, n, batch_idx, rms, popart=True) if pop else None)
-
-    def _wide_state(self, wide, views, n, batch_idx, rms, popart=False):
-        """Items, workspaces, index and loss tensors and the plan (pinned host copy, device copy) of the agents on the
-        grouped multi-workgroup launches -- the plain ones or, ``popart``, the Pop-Art ones; kept until the call's
-        signature changes."""
-        ag, W, lib = self.agents, len(wide), self.lib
-        item_t, ws_bytes, plan_bytes, plan, train = (
-            (_ffi.DdpgManyPopartItem, lib.ssc_ddpg_train_popart_workspace_bytes, lib.ssc_ddpg_train_many_popart_plan_bytes,
-             lib.ssc_ddpg_train_many_popart_plan, lib.ssc_ddpg_train_many_popart) if popart else
-            (_ffi.DdpgManyWideItem, lib.ssc_ddpg_train_workspace_bytes, lib.ssc_ddpg_train_many_wide_plan_bytes,
-             lib.ssc_ddpg_train_many_wide_plan, lib.ssc_ddpg_train_many_wide))
-        st = dict(agents=wide, n=[n[p] for p in wide], train=train)
-        with torch.cuda.device(self.device):
-            st["losses"] = torch.empty((sum(st["n"]), 2), dtype=torch.float32, device=self.device)
-            items = st["items"] = (item_t * W)()
-            off, st["rows"], st["idx"] = 0, [], []
-            # our own draw: one launch for all rings where every agent has the same batch size <= 64 (the sampler's one-wave
-            # kernel; rows [slot][n_max][B], agent p reads its first n[p] batches), else one launch per ring
-            active = [p for p in wide if n[p] > 0]
-            sizes = {ag[p].batch_size for p in active}
-            st["keys"] = None
-            if batch_idx is None and len(active) > 1 and len(sizes) == 1 and max(sizes) <= 64:
-                st["active"], st["n_max"], st["B"] = active, max(n[p] for p in active), max(sizes)
-                st["idx_all"] = torch.empty((len(active), st["n_max"], st["B"]), dtype=torch.int32, device=self.device)
-                st["h_keys"] = torch.empty(len(active) * ctypes.sizeof(_ffi.ReplaySampleKey), dtype=torch.uint8).pin_memory()
-                st["d_keys"] = torch.empty(st["h_keys"].numel(), dtype=torch.uint8, device=self.device)
-                st["keys"] = (_ffi.ReplaySampleKey * len(active)).from_address(st["h_keys"].data_ptr())
-            for it, p in zip(items, wide):
-                a, v, k = ag[p], views[p], n[p]
-                it.ddpg = d = a.ddpg_desc()
-                it.replay = _ffi.ReplayView(*(x.data_ptr() for x in v), v[0].shape[0])
-                it.n_iters, it.d_rms = k, rms[p]
-                if popart:
-                    it.d_ret_rms = a.ret_rms.block.data_ptr()
-                need = int(ws_bytes(ctypes.byref(d)))      # the agent's own, as train_on keeps it
-                ws = getattr(a, "_train_ws", None)
-                if ws is None or ws.numel() < need:
-                    ws = a._train_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                it.d_workspace, it.workspace_bytes = ws.data_ptr(), ws.numel()
-                st.setdefault("ws", []).append(ws)                                          # (alive as long as the plan names it)
-                st["rows"].append(st["losses"][off:off + k] if k > 0 else None)
-                idx = None
-                if k > 0:
-                    idx = (batch_idx[p] if batch_idx is not None else st["idx_all"][active.index(p)] if st["keys"] is not None
-                           else torch.empty((k, a.batch_size), dtype=torch.int32, device=self.device))
-                    it.d_losses, it.d_batch_idx = st["rows"][-1].data_ptr(), idx.data_ptr()
-                st["idx"].append(idx)
-                off += k
-            nbytes = int(plan_bytes(W))
-            if self._items_event is not None:
-                self._items_event.synchronize()
-            st["h_plan"] = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-            _ffi.check(plan(ctypes.addressof(items), W, st["h_plan"].data_ptr(), nbytes))
-            st["d_plan"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            st["d_plan"].copy_(st["h_plan"], non_blocking=True)
-            self._items_event = torch.cuda.Event()
-            self._items_event.record()
-        return st
-
-    def _train_split(self, replays, views, batch_idx, n, copy):
-        """The call on a split population; ``replays`` (train_from) or ``batch_idx`` (train_on) is None."""
-        ag, g = self.agents, self._groups
-        out = [None] * len(ag)
-        for p in g["alone"]:
-            if n[p] > 0:
-                out[p] = ag[p].train_from(replays[p], n[p]) if batch_idx is None else ag[p].train_on(*views[p], batch_idx[p], n[p])
-        for ps, child in g["children"]:
-            k = [n[p] for p in ps]
-            got = (child._train_from([replays[p] for p in ps], k, copy) if batch_idx is None
-                   else child._train_on([views[p] for p in ps], [batch_idx[p] for p in ps], k, copy))
-            for p, rows in zip(ps, got):
-                out[p] = rows
-        for st in (g["wide"], g["wide_popart"]):
-            if st is not None and any(st["n"]):
-                self._train_grouped(st, replays, batch_idx, n, copy, out)
-        return out
-
-    def _train_grouped(self, st, replays, batch_idx, n, copy, out):
-        """one grouped call (plain or Pop-Art) on its kept state; fills the agents' slots of ``out``"""
-        ag = self.agents
-        with torch.cuda.device(self.device):
-            if batch_idx is None and st["keys"] is not None:
-                if self._keys_event is not None:
-                    self._keys_event.synchronize()           # the last upload has left the pinned keys
-                for key, p in zip(st["keys"], st["active"]):
-                    key.seed, key.counter0, key.size = replays[p].take_sample_key(n[p], st["B"])
-                st["d_keys"].copy_(st["h_keys"], non_blocking=True)
-                self._keys_event = torch.cuda.Event()
-                self._keys_event.record()
-                _ffi.check(self.lib.ssc_replay_sample_many(st["h_keys"].data_ptr(), st["d_keys"].data_ptr(), len(st["active"]),
-                                                           st["n_max"], st["B"], _ffi.ptr(st["idx_all"]), _ffi.stream(self.device)))
-            elif batch_idx is None:     # every ring draws under its own key, as its sample_indices would
-                for p, k, idx in zip(st["agents"], st["n"], st["idx"]):
-                    if k > 0:
-                        B = ag[p].batch_size
-                        seed, counter0, size = replays[p].take_sample_key(k, B)
-                        _ffi.check(self.lib.ssc_replay_sample(seed, counter0, size, k, B, _ffi.ptr(idx), _ffi.stream(self.device)))
-            _ffi.check(st["train"](ctypes.addressof(st["items"]), st["h_plan"].data_ptr(), st["d_plan"].data_ptr(), len(st["agents"]),
-                                   _ffi.stream(self.device)))
-            block = st["losses"].clone() if copy else st["losses"]
-        off = 0
-        for p, k in zip(st["agents"], st["n"]):
-            out[p] = block[off:off + k] if k > 0 else None
-            off += k
-
-    def _launch(self, copy):
-        st = self._state
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.ssc_ddpg_train_many(st["h_items"].data_ptr(), st["d_items"].data_ptr(), len(self.agents),
-                                                    _ffi.stream(self.device)))
-            if not copy:
-                return list(st["rows"])
-            block, out, off = st["losses"].clone(), [], 0
-            for k in st["n"]:
-                out.append(block[off:off + k] if k > 0 else None)
-                off += k
-            return out
+            self._groups = [(_OneWorkgroupGroup if way == "one_workgroup" else _PlanGroup)(self, way, ps, descs, views, n, batch_idx, rms)
+                            for way, ps in groups]
+        self._sig = sig
 
     # ---- evaluation and diagnostics: what a sweep's agents are compared by, one launch per phase ---------------------
     # Both calls wrap the per-agent methods' kernels (``ssc_ddpg_eval_rollout_many`` / ``ssc_ddpg_stats_many``: grid row p
@@ -1357,7 +1278,7 @@ class DDPGPopulation:
         one-wave sampler), agents on different devices, an agent without ``param_noise_cycle``, a refusal by the library's
         own validation -- runs the per-agent calls; ``pn_fused`` tells which way the last call went.  Stream-ordered, no
         host read."""
-        from .population import DeviceItems, served
+        from .population import served
         from .rl_train import adapt_and_perturb
         ag, P = self.agents, len(self.agents)
         replays = list(replays)
@@ -1389,14 +1310,13 @@ class DDPGPopulation:
             if self.pn_fused:
                 n = len(noisy)
                 with torch.cuda.device(self.device):
-                    st = dict(B=B, items=DeviceItems(_ffi.ParamNoiseManyItem, n, self.device),
+                    st = dict(items=DeviceItems(_ffi.ParamNoiseManyItem, n, self.device),
                               cursors=DeviceItems(_ffi.ParamNoiseCursor, n, self.device),
-                              keys=DeviceItems(_ffi.ReplaySampleKey, max(len(active), 1), self.device),
-                              idx=torch.zeros((max(len(active), 1), 1, B), dtype=torch.int32, device=self.device))
+                              draw=IndexDraw(max(len(active), 1), 1, B, self.device))
                     for j, (it, p, d) in enumerate(zip(st["items"].items, noisy, out)):
                         a, r = ag[p], replays[p]
                         it.actor, it.d_obs = a._desc, r.s.data_ptr()
-                        it.d_idx = st["idx"][active.index(j)].data_ptr() if j in active else None
+                        it.d_idx = st["draw"].idx[active.index(j)].data_ptr() if j in active else None
                         it.d_rms = None if rms[j] is None else rms[j].data_ptr()
                         it.n, it.d_src = a.actor_flat.numel(), a.actor_flat.data_ptr()
                         it.skip0_begin, it.skip0_end, it.skip1_begin, it.skip1_end = a._pn_skip
@@ -1413,12 +1333,7 @@ class DDPGPopulation:
             st["cursors"].upload()
             with torch.cuda.device(self.device):
                 if active:
-                    st["keys"].wait()
-                    for k, j in zip(st["keys"].items, active):
-                        k.seed, k.counter0, k.size = plan[j]["key"]
-                    st["keys"].upload()
-                    _ffi.check(self.lib.ssc_replay_sample_many(st["keys"].h_ptr, st["keys"].d_ptr, len(active), 1, st["B"],
-                                                               _ffi.ptr(st["idx"]), _ffi.stream(self.device)))
+                    st["draw"].draw([plan[j]["key"] for j in active])
                 # the library's own rules decide: validation precedes every HIP call, so a refusal has launched nothing
                 self.pn_fused = served(self.lib.ssc_param_noise_cycle_many(st["items"].h_ptr, st["items"].d_ptr, st["cursors"].h_ptr,
                                                                            st["cursors"].d_ptr, len(noisy), _ffi.stream(self.device)))

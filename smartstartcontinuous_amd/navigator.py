@@ -321,6 +321,12 @@ DYN_POPULATION_GROUPED = True       # False: every model trains through its own 
 DYN_POPULATION_MIN_GROUP = 2
 
 
+def _on(t, device):
+    """Does tensor ``t`` live on ``device``?  A tensor's device carries its index; ``torch.device("cuda")`` names the
+    current device without one, and compares unequal to every indexed device."""
+    return t.device == (device if device.index is not None else torch.device(device.type, torch.cuda.current_device()))
+
+
 def _per_model(value, n, what):
     """one value for every model, or one per model"""
     if isinstance(value, (list, tuple, np.ndarray)):
@@ -395,7 +401,7 @@ class DynamicsModelPopulation:
             return
         seg = lambda n: (int(n) + 127) & ~127       # every model's losses start 512-byte aligned, like a tensor of their own
         total = sum(seg(idxs[p].shape[0]) for p in work)
-        if self._loss is None or self._loss.numel() < total or self._loss.device != device:
+        if self._loss is None or self._loss.numel() < total or not _on(self._loss, device):
             self._loss = torch.empty(max(total, 64), dtype=torch.float32, device=device)
         fresh = (_ffi.MlpTrainManyItem * len(group))()
         keep, at = [], 0          # keep: tensors made contiguous for this call stay alive until it is enqueued
@@ -458,7 +464,7 @@ class DynamicsModelPopulation:
                 continue
             # the epoch's index matrices of all models travel in one copy, its steps are enqueued by one call per group
             flat = np.concatenate([host[p].reshape(-1) for p in live])
-            if self._idx is None or self._idx.numel() < flat.size or self._idx.device != device:
+            if self._idx is None or self._idx.numel() < flat.size or not _on(self._idx, device):
                 self._idx = torch.empty(max(flat.size, 1024), dtype=torch.int32, device=device)
             self._idx[:flat.size].copy_(torch.from_numpy(flat))
             idxs, at = [None] * P, 0

@@ -1,12 +1,12 @@
 """Launch descriptors of the population entry points (``ssc_rollout_many``, ``ssc_replay_append_many``,
 ``ssc_decay_schedule_many``, ``ssc_obs_rms_update_many``, ``ssc_ddpg_eval_rollout_many``, ``ssc_ddpg_stats_many``,
-``ssc_param_noise_cycle_many``).
+``ssc_param_noise_cycle_many``, the ``DDPGPopulation`` learner).
 
 Each of those calls takes a host array that the library validates and the caller's device copy of the same bytes.
-``DeviceItems`` is that pair for one ctypes struct; ``PairCursors`` is the small per-chunk array (``ssc_pair_cursor``:
-``step0`` for the rollout, ``replay_start`` for the append) that a steady-state chunk uploads and nothing else.
-``agents.DDPGPopulation._prepare`` is the model: pinned host memory, a non-blocking copy, and an event that guards the
-pinned bytes against being rewritten while an upload still reads them.
+``DeviceItems`` is that pair for one ctypes struct: pinned host memory, a non-blocking copy, and an event that guards the
+pinned bytes against being rewritten while an upload still reads them.  ``PairCursors`` is the small per-chunk array
+(``ssc_pair_cursor``: ``step0`` for the rollout, ``replay_start`` for the append) that a steady-state chunk uploads and
+nothing else; ``IndexDraw`` is the same for the sampling keys of ``ssc_replay_sample_many``.
 """
 from __future__ import annotations
 
@@ -76,6 +76,27 @@ class PairCursors(DeviceItems):
 
     def replay_start(self):
         return [int(c.replay_start) for c in self.items]
+
+
+class IndexDraw:
+    """Batch indices of up to ``n`` rings in one ``ssc_replay_sample_many``: the keys (``keys``, a ``DeviceItems`` of
+    ``ReplaySampleKey``) and ``idx`` int32 [n, n_max, B]; ring j's batches are row j, its consumer reads its first ones."""
+
+    def __init__(self, n, n_max, B, device):
+        self.keys = DeviceItems(_ffi.ReplaySampleKey, n, device)
+        self.n_max, self.B = int(n_max), int(B)
+        self.idx = torch.empty((self.keys.n, self.n_max, self.B), dtype=torch.int32, device=self.keys.device)
+
+    def draw(self, keys):
+        """upload ``keys`` ((seed, counter0, size) of rings 0 .. len(keys) - 1) and draw their rows on the current stream"""
+        k = self.keys
+        k.wait()
+        for it, key in zip(k.items, keys):
+            it.seed, it.counter0, it.size = key
+        k.upload()
+        with torch.cuda.device(k.device):
+            _ffi.check(_ffi.lib().ssc_replay_sample_many(k.h_ptr, k.d_ptr, len(keys), self.n_max, self.B, _ffi.ptr(self.idx),
+                                                         _ffi.stream(k.device)))
 
 
 def served(rc):

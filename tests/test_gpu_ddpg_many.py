@@ -298,13 +298,17 @@ def assert_losses_equal(got, want):
     assert all(torch.equal(x, y) for x, y in zip(got, want) if x is not None)
 
 
-def _population_vs_agents(ssc, agents, twins, fused, records=(256, 256, 40, 200)):
+def _population_vs_agents(ssc, agents, twins, fused, records=(256, 256, 40, 200), kept=None):
+    """three train_from calls against the twins' own; ``kept``: a list that gets, per call, every one-workgroup group's
+    DeviceItems (items, sampling keys)"""
     replays, twin_replays = ([make_replay(ssc, p, n) for p, n in enumerate(records)] for _ in range(2))
     untouched = [t.clone() for t in agent_tensors(agents[2])]
     pop = ssc.DDPGPopulation(agents)
     for call in range(3):          # the second and third call reuse the descriptors
         got = pop.train_from(replays, copy=True)
         assert pop.fused is fused
+        if kept is not None:
+            kept.append([(g.items, g.draw.keys) for g in pop._groups])
         want = [a.train_from(r) for a, r in zip(twins, twin_replays)]
         assert_losses_equal(got, want)
         assert got[2] is None and [g.shape[0] for g in got if g is not None] == [a.num_train_iterations for a in agents[:2] + agents[3:]]
@@ -316,8 +320,13 @@ def _population_vs_agents(ssc, agents, twins, fused, records=(256, 256, 40, 200)
 
 
 def test_population_train_from_is_bitwise_the_agents_own(ssc):
+    from smartstartcontinuous_amd.population import DeviceItems
     agents, twins = ([make_agent(ssc, p) for p in range(4)] for _ in range(2))
-    pop, replays, twin_replays = _population_vs_agents(ssc, agents, twins, True)
+    kept = []
+    pop, replays, twin_replays = _population_vs_agents(ssc, agents, twins, True, kept=kept)
+    assert len(kept[0]) == 1 and all(isinstance(x, DeviceItems) for x in kept[0][0])
+    for later in kept[1:]:                 # the second and third calls: the same descriptors, only the keys uploaded
+        assert len(later) == 1 and all(x is y for x, y in zip(later[0], kept[0][0]))
     # a ring fills up: the descriptors are rebuilt and the third agent joins
     replays[2].count = twin_replays[2].count = 64
     got = pop.train_from(replays, n_iters=2)

@@ -316,13 +316,13 @@ def test_population_under_the_wide_switch_is_all_wide(ssc, monkeypatch, single_a
 @pytest.mark.parametrize("shape", [(128, 64), (64, 32)])
 def test_population_with_mixed_statistics_is_grouped(ssc, shape, single_agent_calls):
     """Statistics on agent 3 only: among wide agents it runs in the statistics instantiation of the gradient launch, the
-    others in the plain one; among agents of the shipped shape it is a child population of its own.  Each equals its twin."""
+    others in the plain one; among agents of the shipped shape it is a one-workgroup group of its own.  Each equals its twin."""
     agents, twins = ([agent_of(ssc, p, shape, normalize_observations=p == 3) for p in range(4)] for _ in range(2))
     with_statistics(agents, twins, [3])
     pop, _, _ = _population_vs_agents(ssc, agents, twins, False)
     assert pop.ways == (("wide",) * 4 if shape == (128, 64) else ("one_workgroup",) * 4) and single_agent_calls == []
     if shape == (64, 32):
-        assert sorted(ps for ps, _ in pop._groups["children"]) == [[0, 1, 2], [3]]
+        assert sorted(g.ps for g in pop._groups if g.way == "one_workgroup") == [[0, 1, 2], [3]]
 
 
 @pytest.mark.parametrize("which", ["mixed", "wide_switch", "statistics"])

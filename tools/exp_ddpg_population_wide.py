@@ -72,10 +72,10 @@ CASES = (("reference_grid", lambda ssc: grid(ssc, 1)),
 def plan_lds_bytes(ssc, pop):
     """per wide agent, the dynamic LDS of its gradient workgroups: the last word of its plan row (WideRowTail::lds_bytes)"""
     import torch
-    st = pop._groups["wide"]
-    lib, W = ssc._ffi.lib(), len(st["agents"])
+    g = next(g for g in pop._groups if g.way == "wide")
+    lib, W = ssc._ffi.lib(), len(g.ps)
     row = int(lib.ssc_ddpg_train_many_wide_plan_bytes(2) - lib.ssc_ddpg_train_many_wide_plan_bytes(1)) - 16
-    words = st["h_plan"][:W * row].view(torch.int32).view(W, row // 4)
+    words = g.plan.host[:W * row].view(torch.int32).view(W, row // 4)
     return [int(x) for x in words[:, -1]]
 
 
@@ -112,7 +112,7 @@ def population(out_dir):
             for arm in pops:
                 times[arm].append(window(arm))
         g, y = stat(times["grouped"]), stat(times["per_agent"])
-        lds = plan_lds_bytes(ssc, pops["grouped"]) if pops["grouped"]._groups and pops["grouped"]._groups["wide"] else []
+        lds = plan_lds_bytes(ssc, pops["grouped"]) if "wide" in pops["grouped"].ways else []
         row = dict(case=name, agents=P, batch=agents[0].batch_size, iters=ITERS, calls_per_window=calls,
                    ways={w: ways["grouped"].count(w) for w in ("one_workgroup", "wide", "alone")}, grouped=g, per_agent=y,
                    per_agent_over_grouped=y["median_ms"] / g["median_ms"], won=g["max_ms"] < y["min_ms"],
