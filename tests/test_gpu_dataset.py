@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import ssc_oracle as O
+from tests.data_cases import stats_reference_of
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -100,8 +101,11 @@ def test_column_stats_zscore_and_noise(ssc):
     xd = torch.as_tensor(x, device="cuda")
     mean, std = cs.column_stats(xd)
     m_ref, s_ref = O.column_stats(x)
-    assert np.allclose(mean.cpu().numpy(), m_ref, rtol=1e-13, atol=1e-15)
-    assert np.allclose(std.cpu().numpy(), s_ref, rtol=1e-12, atol=1e-15) and std[3].item() == 0.0
+    # the bound derived from the kernel's summation order (test_gpu_data_matrix.py::test_column_stats_within_the_derived_bound),
+    # against math.fsum on the same data: about 25 u relative here, where 1e-13 and 1e-12 stood
+    r = stats_reference_of(x)
+    assert np.all(np.abs(mean.cpu().numpy() - r["mean"]) <= r["e_mean"])
+    assert np.all(np.abs(std.cpu().numpy() - r["std"]) <= r["e_std"]) and std[3].item() == 0.0
     mean2, std2 = cs.column_stats(xd)
     assert torch.equal(mean, mean2) and torch.equal(std, std2)          # fixed summation order
     # z-score into the network-input matrix: columns 1..4 of a 6-wide matrix
