@@ -4,7 +4,9 @@
   1. random-policy rollouts of N envs (one fused launch) -> (s, a, s' - s) training set, statistics, z-scores;
   2. Dyn_Model.train on the device (fused one-launch steps for one hidden layer, fp32-MFMA GEMMs otherwise);
      with --population P the models of P seeds train together, one launch per step for all of them;
-  3. P envs each follow a recorded path with MPC as the rollout policy (HIP-graph replay of the 5-launch step).
+  3. P envs each follow a recorded path with MPC as the rollout policy (HIP-graph replay of the 5-launch step);
+     with --population P the envs of all seeds sit in ONE VecEnv and one graph steps them (navigator.NavigatorPopulation:
+     the forward simulation of every seed's model is one ssc_mpc_forward_sim_many launch when the models are fp32 1 x <=128).
 """
 import argparse
 import os
@@ -39,10 +41,9 @@ def collect(args, seed):
     return collector, inputs, outputs, norm
 
 
-def follow(args, seed, model, collector):
-    """every problem follows the states of one recorded validation rollout"""
+def plans(args, collector):
+    """the states of args.problems recorded validation rollouts and the plans (waypoints, distances left, radii) along them"""
     states, _, _, _ = collector.collect_samples(args.problems, 200)
-    P = args.problems
     wps, lefts, radii = [], [], []
     for path in states:
         stds, means = num.path_deltas_stds_and_means_per_dim(path)
@@ -51,6 +52,13 @@ def follow(args, seed, model, collector):
         short = num.path_shortcutter(path, dist, 1)
         wp = np.asarray(num.get_start_waypoints_final_states_steps(short, 1))
         wps.append(wp); radii.append(rad); lefts.append(num.distances_left(wp, dist))
+    return states, wps, lefts, radii
+
+
+def follow(args, seed, model, collector):
+    """every problem follows the states of one recorded validation rollout"""
+    states, wps, lefts, radii = plans(args, collector)
+    P = args.problems
     problems = nav.MpcProblemSet(wps, lefts, radii, [0] * P, theta=1.0, gamma=0.75, horizontal_penalty_factor=0.5)
     batch = nav.NavigatorBatch(model, problems, num_control_samples=args.samples, horizon=args.horizon, seed=seed)
     venv = ssc.VecEnv("MountainCarContinuous-v0", P, seed=seed + 2)
@@ -70,6 +78,37 @@ def follow(args, seed, model, collector):
         print("waypoint reached per env:", idx.tolist(), "of", [len(w) for w in wps])
 
 
+def follow_population(args, seeds, pop, collectors):
+    """the navigators of ALL seeds in one VecEnv of len(seeds) * args.problems envs: env range p follows seed p's paths with
+    seed p's dynamics model, one captured graph steps everybody (navigator.NavigatorPopulation)"""
+    states, wps, lefts, radii = [], [], [], []
+    for collector in collectors:
+        for have, new in zip((states, wps, lefts, radii), plans(args, collector)):
+            have.extend(new)
+    n = len(states)
+    problems = nav.MpcProblemSet(wps, lefts, radii, [0] * n, theta=1.0, gamma=0.75, horizontal_penalty_factor=0.5)
+    batch = nav.NavigatorPopulation(pop, problems, args.problems, num_control_samples=args.samples, horizon=args.horizon,
+                                    seed=seeds[0])
+    venv = ssc.VecEnv("MountainCarContinuous-v0", n, seed=seeds[0] + 2)
+    venv.reset()
+    start = torch.as_tensor(np.stack([p[0] for p in states]), dtype=torch.float32, device="cuda")
+    venv.s0.copy_(start[:, 0]); venv.s1.copy_(start[:, 1])
+    venv.rollout(8, policy=ssc.MpcPolicy(batch))            # warm-up + graph capture
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    venv.rollout(args.follow_steps, policy=ssc.MpcPolicy(batch))
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    idx = problems.cur_idx.cpu().numpy()
+    print("seeds %s: %d envs followed their paths for %d MPC steps from ONE graph (%d x %d samples, horizon %d) in %.1f ms = "
+          "%.3f ms per step; forward simulation per model: %s"
+          % (seeds, n, args.follow_steps, n, args.samples, args.horizon, dt * 1e3, dt * 1e3 / args.follow_steps,
+             ", ".join(batch.sim_ways)))
+    for p, seed in enumerate(seeds):
+        sl = slice(p * args.problems, (p + 1) * args.problems)
+        print("seed %d waypoint reached per env:" % seed, idx[sl].tolist(), "of", [len(w) for w in wps[sl]])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rollouts", type=int, default=4096)
@@ -84,7 +123,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--population", type=int, default=1,
                     help="P seeds collect their own data, train their models TOGETHER (one launch per Adam step for all of "
-                         "them: navigator.DynamicsModelPopulation) and each follows its paths")
+                         "them: navigator.DynamicsModelPopulation) and follow their paths in ONE VecEnv from one graph "
+                         "(navigator.NavigatorPopulation)")
     ap.add_argument("--precision", choices=["bf16_mfma", "f32"], default="bf16_mfma",
                     help="forward simulation of the MPC: bf16 MFMA kernel (default) or the fp32 parity path")
     args = ap.parse_args()
@@ -107,8 +147,10 @@ def main():
     print("trained %d model(s) %dx%d for %d epochs (%d steps, %s) in %.1f ms, last-epoch losses %s"
           % (len(models), args.layers, args.depth, args.epochs, steps, how, (time.perf_counter() - t0) * 1e3,
              ", ".join("%.4f" % v for v in losses)))
-    for seed, model, (collector, _, _, _) in zip(seeds, models, sets):
-        follow(args, seed, model, collector)
+    if args.population <= 1:
+        follow(args, seeds[0], models[0], sets[0][0])
+    else:
+        follow_population(args, seeds, pop, [s[0] for s in sets])
 
 
 if __name__ == "__main__":

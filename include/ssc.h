@@ -333,6 +333,35 @@ int ssc_mpc_forward_sim(const ssc_mlp_desc *mlp, const ssc_norm *norm, const ssc
                         float *d_A_out, float *d_S, int precision, void *d_workspace, size_t workspace_bytes,
                         ssc_stream_t stream);
 
+/* One dynamics model of a population and the problems it simulates.  Declared tag first like the other *_many items;
+ * tests/test_mpc_sim_many_host.py holds the struct's size and offsets to the ctypes mirror. */
+struct ssc_mpc_sim_many_item {
+    ssc_mlp_desc mlp;        /* one hidden layer, depth <= 128: the fused fp32 family (state <= 3, state + act <= 4) */
+    ssc_norm     norm;       /* this model's statistics, by value */
+    int32_t      problem0;   /* the item's problems: [problem0, problem0 + n_problems) of the call's */
+    int32_t      n_problems; /* problem-major arrays; 0: the item is skipped and nothing else of it is read */
+};
+typedef struct ssc_mpc_sim_many_item ssc_mpc_sim_many_item;
+
+/* ssc_mpc_forward_sim(.., SSC_PREC_F32, ..) for a population of models in ONE launch (the navigators of a sweep's seeds,
+ * DESIGN.md section 4.5b): contiguous ranges of the call's m / n_samples problems use different networks and different
+ * z-score statistics.  Grid row y runs item y's workgroups (grid x = the largest item's count; surplus workgroups leave at
+ * once, before any barrier) through the very kernel bodies of the single call.  Afterwards d_S [H+1][m][state_dim] and
+ * d_A_out [m][H][act_dim] (may be NULL) hold, bit for bit, what one ssc_mpc_forward_sim call per item with n_problems > 0
+ * leaves in the same buffers when its d_problem_active is AND-ed with "problem in the item's range": rows of problems no
+ * item owns, and rows the caller's mask switches off, are left untouched; d_t_base is honoured; the Philox stream is that
+ * of (seed, problem_id0 + problem, sample, t) with the call's GLOBAL problem index, so nothing depends on the item split.
+ * Conventions of the other *_many calls: the host array is validated completely before any HIP call, the caller's device
+ * copy of the same bytes must be complete on `stream`, the library copies nothing, item indices appear in
+ * ssc_last_error().  n_items 1..65535.  The single call's checks apply to the call and to every item with n_problems > 0
+ * (its codes); an item outside the fused fp32 family is SSC_EUNSUPPORTED naming it; a range outside
+ * [0, m / n_samples) or two overlapping ranges are SSC_EINVAL (gaps are legal); sampling->d_live_list / d_n_live must be
+ * NULL (SSC_EINVAL: a compact list maps slots to arbitrary problems, a workgroup's weights would not be uniform).
+ * Weights may be shared between items.  m == 0, or every item empty: SSC_OK without a launch. */
+int ssc_mpc_forward_sim_many(const ssc_mpc_sim_many_item *h_items, const ssc_mpc_sim_many_item *d_items, int32_t n_items,
+                             const ssc_mpc_sampling *sampling, int64_t m, int32_t H, int32_t state_dim, int32_t act_dim,
+                             const float *d_s0, int64_t s0_rows, float *d_A_out, float *d_S, ssc_stream_t stream);
+
 /* generate_scores_add_delta (NND_MB_agent.py:566-628) + argmax (:625-626) per problem.
  * d_S [H+1][P*N][state_dim] (output of ssc_dyn_forward_sim); d_scores [P*N]; d_best_idx [P]
  * (index within the problem, lowest index on ties like np.argmax); d_best_score [P]. */

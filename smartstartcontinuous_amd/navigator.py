@@ -354,6 +354,7 @@ class DynamicsModelPopulation:
         self._sent = {}          # way -> the bytes last uploaded
         self._loss = None        # the grouped models' losses of one call, cloned before they are handed out
         self._idx = None         # train(): the epoch's index matrices of all models, one upload
+        self._sim_scratch = {}   # (model, H, rows) -> the [H+1, rows, d] states of a model that simulates alone
 
     @staticmethod
     def way_of(model):
@@ -482,6 +483,127 @@ class DynamicsModelPopulation:
             for k, p in enumerate(got):
                 out[p] = float(means[k].item())
         return out
+
+    # ---- forward simulation: contiguous problem ranges, one model each (ssc_mpc_forward_sim_many) ----------------------
+    @staticmethod
+    def sim_way_of(model):
+        """``"many"``: the model's own fp32 call runs the fused small-network family, which one many-call serves for a
+        whole population; ``"alone"``: bf16 MFMA, more than one hidden layer, depth > 128, state > 3 or state + act > 4"""
+        dims = [int(model.W[0].shape[0])] + [int(w.shape[1]) for w in model.W]
+        d, a = int(model.state_dim), int(model.act_dim)
+        small = len(dims) == 3 and dims[1] <= 128 and d <= 3 and d + a <= 4 and a <= 3
+        return "many" if model.precision == "f32" and small else "alone"
+
+    @property
+    def sim_ways(self):
+        """The way per model: a pure function of shapes, precisions, devices, the group's size and the two switches"""
+        dev0 = getattr(self.models[0], "device", None)
+        ways = [self.sim_way_of(m) if NAV_POPULATION_GROUPED and getattr(m, "device", None) == dev0 else "alone"
+                for m in self.models]
+        return [w if ways.count("many") >= NAV_POPULATION_MIN_GROUP else "alone" for w in ways]
+
+    def sync_sim_items(self, problems_per_model):
+        """The item table of the many-call (one item per model, empty for a model that simulates alone), re-uploaded only
+        when its bytes change.  Returns the ``DeviceItems``, or ``None`` when no model goes the grouped way.  A captured
+        graph must find the table uploaded: ``NavigatorPopulation.begin_chunk`` calls this in front of the capture."""
+        from .population import DeviceItems
+        P, ways = len(self.models), self.sim_ways
+        counts = [int(c) for c in _per_model(problems_per_model, P, "problems_per_model")]
+        if "many" not in ways:
+            return None
+        device = self.models[0].device
+        fresh = (_ffi.MpcSimManyItem * P)()
+        at = 0
+        for it, m, way, n in zip(fresh, self.models, ways, counts):
+            if way == "many" and n > 0:
+                it.mlp, it.norm, it.problem0, it.n_problems = m.desc, m.norm, at, n
+            at += n
+        di = self._items.get("sim")
+        if di is None or di.n != P or di.device != device:
+            di = self._items["sim"] = DeviceItems(_ffi.MpcSimManyItem, P, device)
+            self._sent.pop("sim", None)
+        image = bytes(fresh)
+        if self._sent.get("sim") != image:              # a weight pointer, a shape, the statistics or the split changed
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("DynamicsModelPopulation: the item table changed inside a graph capture; "
+                                   "call sync_sim_items() in front of it")
+            di.wait()
+            ctypes.memmove(di.h_ptr, ctypes.addressof(fresh), len(image))
+            di.upload()
+            self._sent["sim"] = image
+        return di
+
+    def do_forward_sim_sampled(self, state0, sampling, problems_per_model, H, out=None, A_out=None):
+        """``do_forward_sim_sampled`` for a problem-major batch whose problems belong to different models: model p owns
+        the next ``problems_per_model[p]`` problems (one count, or one per model) of ``sampling.n_samples`` candidate rows
+        each.  The models of ``sim_ways == "many"`` go through ONE ``ssc_mpc_forward_sim_many`` launch; every other model
+        through its own call into a scratch [H+1, m_p, d] and a strided copy into its rows (the masked single call is no
+        substitute: the streamed MFMA kernel ignores the mask).  Every row ends up, bit for bit, where its model's own
+        call with ``problem_id0 + first problem`` leaves it.  Returns S [H+1, m, d]."""
+        P, N, H = len(self.models), int(sampling.n_samples), int(H)
+        counts = [int(c) for c in _per_model(problems_per_model, P, "problems_per_model")]
+        first = self.models[0]
+        device, d, a = first.device, first.state_dim, first.act_dim
+        if any((m.state_dim, m.act_dim) != (d, a) for m in self.models):
+            raise ValueError("DynamicsModelPopulation.do_forward_sim_sampled: one state / action space per call")
+        total = sum(counts)
+        M = total * N
+        s0 = torch.as_tensor(state0, dtype=torch.float32, device=device).contiguous()
+        s0_rows = 1 if s0.dim() == 1 else s0.shape[0]
+        S = out if out is not None else torch.empty((H + 1, M, d), dtype=torch.float32, device=device)
+        if tuple(S.shape) != (H + 1, M, d) or not S.is_contiguous():
+            raise ValueError("out must be a contiguous [H + 1, m, state_dim] tensor")
+        ways = self.sim_ways
+        if "alone" in ways and A_out is None:
+            A_out = torch.empty((M, H, a), dtype=torch.float32, device=device)
+        di = self.sync_sim_items(counts)
+        with torch.cuda.device(device):
+            if di is not None:
+                _ffi.check(first.lib.ssc_mpc_forward_sim_many(di.h_ptr, di.d_ptr, P, ctypes.byref(sampling), M, H, d, a,
+                                                              _ffi.ptr(s0), s0_rows, _ffi.ptr(A_out), _ffi.ptr(S), _ffi.stream()))
+            at = 0
+            for p, (m, way, n) in enumerate(zip(self.models, ways, counts)):
+                if way == "alone" and n > 0:
+                    self._sim_alone(p, m, at, n, N, H, s0, s0_rows, M, sampling, S, A_out)
+                at += n
+        return S
+
+    def sim_scratch(self, p, H, rows):
+        """the [H+1, rows, d] states of model p when it simulates alone (kept: a captured graph writes there)"""
+        key, model = (p, int(H), int(rows)), self.models[p]
+        if key not in self._sim_scratch:
+            self._sim_scratch[key] = torch.empty((H + 1, rows, model.state_dim), dtype=torch.float32, device=model.device)
+        return self._sim_scratch[key]
+
+    def _sim_alone(self, p, model, p0, n, N, H, s0, s0_rows, M, sampling, S, A_out):
+        """model p's own call on problems [p0, p0 + n): its rows of A_out are contiguous, its rows of S are not"""
+        rows = slice(p0 * N, (p0 + n) * N)
+        if s0_rows == 1:
+            s0_p = s0
+        else:
+            per = M // s0_rows                      # rows sharing one start state
+            if (p0 * N) % per or (n * N) % per:
+                raise ValueError("a start state is shared between rows of two models")
+            s0_p = s0[p0 * N // per:(p0 + n) * N // per]
+        sp = _ffi.MpcSampling()
+        ctypes.memmove(ctypes.addressof(sp), ctypes.addressof(sampling), ctypes.sizeof(sp))
+        sp.problem_id0 = int(sampling.problem_id0) + p0
+        masked = bool(sampling.d_problem_active)
+        if masked:
+            sp.d_problem_active = int(sampling.d_problem_active) + p0
+        if sampling.d_live_list or sampling.d_n_live:
+            raise ValueError("DynamicsModelPopulation.do_forward_sim_sampled: no compact live list")
+        scratch = self.sim_scratch(p, H, n * N)
+        if masked:
+            scratch.copy_(S[:, rows])               # rows the mask switches off keep what they held
+        model.do_forward_sim_sampled(s0_p, sp, n * N, H, out=scratch, A_out=A_out[rows])
+        S[:, rows].copy_(scratch)
+
+
+# ---- the navigators of a population: contiguous env ranges, one dynamics model each -------------------------------------
+NAV_POPULATION_GROUPED = True       # False: every model simulates through its own call and a strided copy (the yardstick)
+# the smallest number of fused-family models one ssc_mpc_forward_sim_many call serves (profiles/nav_population)
+NAV_POPULATION_MIN_GROUP = 2
 
 
 def mpc_sampling(N, low, high, seed, problem_id0=0, t=0, t_base=None, active=None, live_list=None, n_live=None):
@@ -741,6 +863,14 @@ def mpc_select_action(A, S, best_idx, P, noise_amount, seed, problem_id0=0, t=0,
     return action, path
 
 
+def _model_key(model):
+    """What a captured forward simulation bakes in of one dynamics model"""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return (model.precision, tuple(ptr(w) for w in model.W), tuple(ptr(b) for b in model.b),
+            bytes(model.norm),   # the fp32 path takes the statistics by value: baked into the capture
+            ptr(model._image), ptr(model._ws))
+
+
 class NavigatorBatch:
     """P navigators (one per env) sharing one dynamics model: the vectorised counterpart of
     ``NND_MB_agent.get_action`` / ``observe`` (NND_MB_agent.py:339-373, 498-520) -- per step ONE sample /
@@ -768,11 +898,15 @@ class NavigatorBatch:
         # three launches: forward simulation (drawing its own candidate sequences), scoring pass A, scoring pass B +
         # selection; every problem's state is the start of its N candidate rows (np.tile, :215-217): s0_rows = P
         sp = mpc_sampling(self.N, self.low, self.high, self.seed, self.problem_id0, t)
-        S = self.model.do_forward_sim_sampled(states.float().contiguous(), sp, self.P * self.N, self.H, out=self._S)
+        S = self._simulate(states.float().contiguous(), sp)
         _, best, action, _ = mpc_score_select(self.problems, S, sampling=sp, act_dim=len(self.low),
                                               noise_amount=self.noise_amount, seed=self.seed, problem_id0=self.problem_id0,
                                               t=t, want_path=False)
         return action, best
+
+    def _simulate(self, state0, sp, A_out=None):
+        """The one place an MPC step touches the dynamics model: all P x N candidate rows from ``state0`` [P, d]."""
+        return self.model.do_forward_sim_sampled(state0, sp, self.P * self.N, self.H, out=self._S, A_out=A_out)
 
     def observe(self, new_states):
         """Waypoint bookkeeping after env.step (NND_MB_agent.observe :360-373; goal test :425-432)."""
@@ -816,7 +950,7 @@ class NavigatorBatch:
             raise ValueError("the envs of this engine take one action component")
         # (the forward simulation draws the candidate sequences itself and leaves them in fb["A"] for the step kernel)
         sp = mpc_sampling(self.N, self.low, self.high, self.seed, self.problem_id0, 0, t_base=fb["t"])
-        S = self.model.do_forward_sim_sampled(fb["plan"], sp, self.P * self.N, self.H, out=self._S, A_out=fb["A"])
+        S = self._simulate(fb["plan"], sp, A_out=fb["A"])
         self._score_and_step(env, chunk, ring, S, _ffi.lib().ssc_mpc_rollout_step)
 
     def begin_chunk(self, env):
@@ -836,18 +970,20 @@ class NavigatorBatch:
         (test_graph_keys_cover_what_the_step_launches_bake_in) lists both and replaces them one at a time: what a launch
         starts to use belongs here AND there."""
         ptr = lambda t: None if t is None else t.data_ptr()
-        model, pr, fb = self.model, self.problems, self._fused_buffers(env.device)
+        pr, fb = self.problems, self._fused_buffers(env.device)
         return (self.P, self.N, self.H, env.n, env.kind, bytes(env.params), env._seed, env.env_id0,
                 tuple(ptr(x) for x in (env.s0, env.s1, env.steps, env.ep_ret, env.ou_x, env.stats)),
                 None if chunk is None else tuple(ptr(c) for c in (chunk.obs, chunk.act, chunk.rew, chunk.done, chunk.obs2)),
                 None if ring is None else (ptr(ring.cursor), ptr(ring.env_id), ptr(ring.length), ptr(ring.ret), ring.capacity),
-                model.precision, tuple(ptr(w) for w in model.W), tuple(ptr(b) for b in model.b),
-                bytes(model.norm),   # the fp32 path takes the statistics by value: baked into the capture
-                ptr(model._image), ptr(model._ws),
+                *self._model_key(),
                 tuple(ptr(x) for x in (pr.wp, pr.left, pr.wp_off, pr.radii, pr.cur_idx)), pr.theta, pr.gamma, pr.hpf, pr.per_row,
                 tuple(ptr(x) for x in (self._S, self.actions_done, self.at_goal, self.start_idx)),
                 tuple(ptr(fb[k]) for k in sorted(fb)), self.noise_amount, self.seed, self.problem_id0, self.give_up,
                 self.final_steps, tuple(self.low.tolist()), tuple(self.high.tolist()))
+
+    def _model_key(self):
+        """graph_key's part for what ``_simulate`` bakes in"""
+        return _model_key(self.model)
 
     def _score_and_step(self, env, chunk, ring, S, step_fn, *lead):
         """The tail of a fused step: score the simulated candidates ``S`` (``ssc_mpc_score``), then ONE launch ``step_fn``
@@ -870,3 +1006,49 @@ class NavigatorBatch:
                 ctypes.byref(ring_s) if ring_s is not None else None,
                 _ffi.ptr(env.stats), env._seed, env.env_id0, _ffi.ptr(fb["t"]), _ffi.ptr(fb["k"]), _ffi.ptr(fb["ticket"]),
                 _ffi.ptr(fb["plan"]), _ffi.stream()))
+
+
+class NavigatorPopulation(NavigatorBatch):
+    """The navigators of a whole sweep in ONE batch: ``problems`` holds ``sum(envs_per_model)`` problems, the next
+    ``envs_per_model[p]`` of them follow their plans with dynamics model p.  Everything of an MPC step but the forward
+    simulation never sees the network, so this is a :class:`NavigatorBatch` whose one model call goes to
+    ``DynamicsModelPopulation.do_forward_sim_sampled``: one captured graph steps every seed's navigators
+    (``VecEnv.rollout(K, MpcPolicy(nav))``, eager and graph).  Env e of model p gets, bit for bit, what a
+    ``NavigatorBatch(models[p], problem_id0 = problem_id0 + first env of p)`` of its own gives it."""
+
+    def __init__(self, models, problems, envs_per_model, **kw):
+        self.models = models if isinstance(models, DynamicsModelPopulation) else DynamicsModelPopulation(models)
+        n = len(self.models.models)
+        self.envs_per_model = [int(c) for c in _per_model(envs_per_model, n, "envs_per_model")]
+        if sum(self.envs_per_model) != problems.P:
+            raise ValueError("NavigatorPopulation: %d problems for %d envs" % (problems.P, sum(self.envs_per_model)))
+        super().__init__(None, problems, **kw)
+
+    @property
+    def sim_ways(self):
+        return self.models.sim_ways
+
+    def _simulate(self, state0, sp, A_out=None):
+        return self.models.do_forward_sim_sampled(state0, sp, self.envs_per_model, self.H, out=self._S, A_out=A_out)
+
+    def begin_chunk(self, env):
+        fb = self._fused_buffers(env.device)
+        fb["t"].fill_(env.t)
+        fb["k"].zero_()
+        fb["plan"].copy_(env.observe())
+        for m in self.models.models:
+            m.refresh_prepared_image()
+        self.models.sync_sim_items(self.envs_per_model)      # uploaded in front of the capture, not inside it
+        for p, (way, n) in enumerate(zip(self.models.sim_ways, self.envs_per_model)):
+            if way == "alone" and n > 0:
+                self.models.sim_scratch(p, self.H, n * self.N)
+        return fb
+
+    def _model_key(self):
+        """every model's weight pointers, statistics bytes, precision, image and workspace; the split, the way per model,
+        the item table's addresses and the scratch of the models that simulate alone"""
+        pop = self.models
+        di = pop._items.get("sim")
+        return (tuple(_model_key(m) for m in pop.models), tuple(self.envs_per_model), tuple(pop.sim_ways),
+                None if di is None else (di.h_ptr, di.d_ptr),
+                tuple(sorted((k, v.data_ptr()) for k, v in pop._sim_scratch.items())))
