@@ -6,7 +6,9 @@
      with --population P the models of P seeds train together, one launch per step for all of them;
   3. P envs each follow a recorded path with MPC as the rollout policy (HIP-graph replay of the 5-launch step);
      with --population P the envs of all seeds sit in ONE VecEnv and one graph steps them (navigator.NavigatorPopulation:
-     the forward simulation of every seed's model is one ssc_mpc_forward_sim_many launch when the models are fp32 1 x <=128).
+     the forward simulation of every seed's model is one ssc_mpc_forward_sim_many launch when the models are fp32 1 x <=128
+     and one ssc_mpc_forward_sim_many_mfma launch when they are bf16 MFMA models of one class -- the default, and any
+     --layers / --depth with one hidden layer up to 512 units or two up to 128; the sim_ways line names the way per model).
 """
 import argparse
 import os
@@ -101,7 +103,7 @@ def follow_population(args, seeds, pop, collectors):
     dt = time.perf_counter() - t0
     idx = problems.cur_idx.cpu().numpy()
     print("seeds %s: %d envs followed their paths for %d MPC steps from ONE graph (%d x %d samples, horizon %d) in %.1f ms = "
-          "%.3f ms per step; forward simulation per model: %s"
+          "%.3f ms per step\nsim_ways: %s"
           % (seeds, n, args.follow_steps, n, args.samples, args.horizon, dt * 1e3, dt * 1e3 / args.follow_steps,
              ", ".join(batch.sim_ways)))
     for p, seed in enumerate(seeds):

@@ -362,6 +362,41 @@ int ssc_mpc_forward_sim_many(const ssc_mpc_sim_many_item *h_items, const ssc_mpc
                              const ssc_mpc_sampling *sampling, int64_t m, int32_t H, int32_t state_dim, int32_t act_dim,
                              const float *d_s0, int64_t s0_rows, float *d_A_out, float *d_S, ssc_stream_t stream);
 
+/* One bf16-MFMA dynamics model of a population and the problems it simulates.  The kernel reads the packed image only (the
+ * statistics are inside it, ssc_dyn_prepare); `mlp` serves the host's shape checks and names the class.
+ * tests/test_mpc_sim_many_mfma_host.py holds the struct's size and offsets to the ctypes mirror. */
+struct ssc_mpc_sim_many_mfma_item {
+    ssc_mlp_desc mlp;         /* host side: shape checks and the class; the kernel reads the image only */
+    const void  *d_image;     /* written by ssc_dyn_prepare(&mlp, &norm, ...); 16-byte aligned */
+    size_t       image_bytes; /* >= ssc_dyn_workspace_bytes(&mlp, m, SSC_PREC_BF16_MFMA) */
+    int32_t      problem0;    /* the item's problems: [problem0, problem0 + n_problems) of the call's */
+    int32_t      n_problems;  /* 0: the item is skipped and nothing else of it is read */
+};
+typedef struct ssc_mpc_sim_many_mfma_item ssc_mpc_sim_many_mfma_item;
+
+/* The instantiation class of the MFMA simulation kernel that one many-call can serve this network with (>= 0), or -1:
+ * not covered by the MFMA path, streamed W2 (two hidden layers deeper than 128), more than 4 inputs or outputs, or a
+ * network that is not state_dim + act_dim -> state_dim.  Classes: 0, 1, 2 = one hidden layer of <= 32, <= 128, <= 512 units;
+ * 3 / 4 = two equal hidden layers of <= 32 units with b2 as the accumulator's input / in two spare k slots (depth <= 30);
+ * 5 / 6 = the same for <= 128 units (k slots: depth <= 126).  A pure function of the shape. */
+int ssc_dyn_mfma_many_class(const ssc_mlp_desc *mlp, int32_t state_dim, int32_t act_dim);
+
+/* ssc_mpc_forward_sim(.., SSC_PREC_BF16_MFMA_PREPARED, ..) -- Dyn_Model.do_forward_sim (dynamics_model.py:204-240) fed by
+ * candidates drawn in the kernel -- for a population of models in ONE launch.  Grid row y runs
+ * item y; its row tiles of 256 rows are anchored at the item's first row, so the partition into tiles and waves is that of
+ * the model's own call on its own rows.  Afterwards the item's rows of d_S [H+1][m][state_dim] and d_A_out [m][H][act_dim]
+ * (may be NULL) hold, bit for bit, what the model's own call leaves in a [H+1][rows][state_dim] buffer of its rows alone
+ * when it is given problem_id0 + problem0 and the mask from byte problem0 on; a row's start state is the one its row OF THE
+ * CALL selects (d_s0[row / (m / s0_rows)]).  Rows of problems no item owns, and waves the mask lets the kernel skip, are left
+ * untouched; d_t_base is honoured.  Conventions and checks of ssc_mpc_forward_sim_many; in addition every item with
+ * n_problems > 0 must have a class, ALL OF THEM THE SAME ONE (SSC_EUNSUPPORTED naming two items and their classes), a
+ * non-NULL 16-byte-aligned image of sufficient size, and at most 2^31 - 1 rows.  The call allocates nothing and makes one
+ * launch.  m == 0, or every item empty: SSC_OK without a launch. */
+int ssc_mpc_forward_sim_many_mfma(const ssc_mpc_sim_many_mfma_item *h_items, const ssc_mpc_sim_many_mfma_item *d_items,
+                                  int32_t n_items, const ssc_mpc_sampling *sampling, int64_t m, int32_t H, int32_t state_dim,
+                                  int32_t act_dim, const float *d_s0, int64_t s0_rows, float *d_A_out /* may be NULL */,
+                                  float *d_S, ssc_stream_t stream);
+
 /* generate_scores_add_delta (NND_MB_agent.py:566-628) + argmax (:625-626) per problem.
  * d_S [H+1][P*N][state_dim] (output of ssc_dyn_forward_sim); d_scores [P*N]; d_best_idx [P]
  * (index within the problem, lowest index on ties like np.argmax); d_best_score [P]. */

@@ -133,6 +133,11 @@ class MpcSimManyItem(Structure):
     _fields_ = [("mlp", MlpDesc), ("norm", Norm), ("problem0", c_int32), ("n_problems", c_int32)]
 
 
+class MpcSimManyMfmaItem(Structure):
+    _fields_ = [("mlp", MlpDesc), ("d_image", c_void_p), ("image_bytes", c_size_t), ("problem0", c_int32),
+                ("n_problems", c_int32)]
+
+
 class DdpgDesc(Structure):
     _fields_ = [("obs_dim", c_int32), ("act_dim", c_int32), ("actor_h1", c_int32), ("actor_h2", c_int32),
                 ("critic_h1", c_int32), ("critic_h2", c_int32), ("last_layer_tanh", c_int32), ("batch_size", c_int32),
@@ -237,7 +242,7 @@ STRUCTS = {
     "ssc_decay_item": DecayItem, "ssc_obs_rms_item": ObsRmsItem, "ssc_ddpg_eval_many_item": DdpgEvalManyItem,
     "ssc_ddpg_stats_many_item": DdpgStatsManyItem, "ssc_param_noise_many_item": ParamNoiseManyItem,
     "ssc_param_noise_cursor": ParamNoiseCursor, "ssc_mlp_train_many_item": MlpTrainManyItem,
-    "ssc_mpc_sim_many_item": MpcSimManyItem,
+    "ssc_mpc_sim_many_item": MpcSimManyItem, "ssc_mpc_sim_many_mfma_item": MpcSimManyMfmaItem,
 }
 
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
@@ -364,6 +369,9 @@ _SIGNATURES = {
                                     c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "ssc_mpc_forward_sim_many": (c_int, [c_void_p, c_void_p, c_int32, POINTER(MpcSampling), c_int64, c_int32, c_int32, c_int32,
                                          c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ssc_dyn_mfma_many_class": (c_int, [POINTER(MlpDesc), c_int32, c_int32]),
+    "ssc_mpc_forward_sim_many_mfma": (c_int, [c_void_p, c_void_p, c_int32, POINTER(MpcSampling), c_int64, c_int32, c_int32,
+                                              c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "ssc_mpc_score_select": (c_int, [POINTER(MpcProblems), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      POINTER(MpcSampling), c_int32, c_float, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),

@@ -355,6 +355,7 @@ class DynamicsModelPopulation:
         self._loss = None        # the grouped models' losses of one call, cloned before they are handed out
         self._idx = None         # train(): the epoch's index matrices of all models, one upload
         self._sim_scratch = {}   # (model, H, rows) -> the [H+1, rows, d] states of a model that simulates alone
+        self._sim_mfma = {}      # "mfma<..>" way -> DeviceItems of the class's many-call (sync_sim_items)
 
     @staticmethod
     def way_of(model):
@@ -486,21 +487,43 @@ class DynamicsModelPopulation:
 
     # ---- forward simulation: contiguous problem ranges, one model each (ssc_mpc_forward_sim_many) ----------------------
     @staticmethod
+    def mfma_sim_class(dims, d, a):
+        """``ssc_dyn_mfma_many_class`` restated on shapes (tests/test_mpc_sim_many_mfma_host.py holds the two together):
+        ``"mfma<UT,NFC>"`` / ``"mfma<UT,NFC,biask>"`` -- the kernel instantiation one ``ssc_mpc_forward_sim_many_mfma`` call
+        serves: UT 32-unit tiles per hidden layer, NFC hidden layers, b2 in spare k slots -- or ``None``: not 1-2 equal hidden
+        layers, depth > 512, two layers deeper than 128 (streamed W2), more than 4 inputs or outputs"""
+        nfc = len(dims) - 2
+        if nfc not in (1, 2) or min(dims) < 1 or d < 1 or a < 1:
+            return None
+        depth = dims[1]
+        if depth > 512 or (nfc == 2 and dims[2] != depth) or dims[0] != d + a or dims[-1] != d or dims[0] > 4 or dims[-1] > 4:
+            return None
+        UT = 1 if depth <= 32 else 4 if depth <= 128 else 16
+        if nfc == 2 and UT > 4:
+            return None
+        return "mfma<%d,%d%s>" % (UT, nfc, ",biask" if nfc == 2 and depth + 2 <= 32 * UT else "")
+
+    @staticmethod
     def sim_way_of(model):
         """``"many"``: the model's own fp32 call runs the fused small-network family, which one many-call serves for a
-        whole population; ``"alone"``: bf16 MFMA, more than one hidden layer, depth > 128, state > 3 or state + act > 4"""
+        whole population; ``"mfma<..>"``: a bf16 MFMA model of a class ``ssc_mpc_forward_sim_many_mfma`` serves
+        (``mfma_sim_class``); ``"alone"``: everything else -- two hidden layers deeper than 128, more than two layers,
+        fp32 deeper than 128, wider inputs or outputs"""
         dims = [int(model.W[0].shape[0])] + [int(w.shape[1]) for w in model.W]
         d, a = int(model.state_dim), int(model.act_dim)
         small = len(dims) == 3 and dims[1] <= 128 and d <= 3 and d + a <= 4 and a <= 3
-        return "many" if model.precision == "f32" and small else "alone"
+        if model.precision == "f32" and small:
+            return "many"
+        return (model.precision == "bf16_mfma" and DynamicsModelPopulation.mfma_sim_class(dims, d, a)) or "alone"
 
     @property
     def sim_ways(self):
-        """The way per model: a pure function of shapes, precisions, devices, the group's size and the two switches"""
+        """The way per model: a pure function of shapes, precisions, devices, the groups' sizes and the switches"""
         dev0 = getattr(self.models[0], "device", None)
         ways = [self.sim_way_of(m) if NAV_POPULATION_GROUPED and getattr(m, "device", None) == dev0 else "alone"
                 for m in self.models]
-        return [w if ways.count("many") >= NAV_POPULATION_MIN_GROUP else "alone" for w in ways]
+        need = lambda w: NAV_POPULATION_MIN_GROUP if w == "many" else NAV_POPULATION_MFMA_MIN_GROUP
+        return [w if w != "alone" and ways.count(w) >= need(w) else "alone" for w in ways]
 
     def sync_sim_items(self, problems_per_model):
         """The item table of the many-call (one item per model, empty for a model that simulates alone), re-uploaded only
@@ -509,6 +532,7 @@ class DynamicsModelPopulation:
         from .population import DeviceItems
         P, ways = len(self.models), self.sim_ways
         counts = [int(c) for c in _per_model(problems_per_model, P, "problems_per_model")]
+        self._sync_mfma_items(ways, counts)
         if "many" not in ways:
             return None
         device = self.models[0].device
@@ -523,21 +547,56 @@ class DynamicsModelPopulation:
             di = self._items["sim"] = DeviceItems(_ffi.MpcSimManyItem, P, device)
             self._sent.pop("sim", None)
         image = bytes(fresh)
-        if self._sent.get("sim") != image:              # a weight pointer, a shape, the statistics or the split changed
+        self._upload_items("sim", di, fresh, image)
+        return di
+
+    def _upload_items(self, key, di, fresh, image):
+        """send an item table only when its bytes changed, and never inside a capture"""
+        if self._sent.get(key) != image:                # a weight pointer, an image, a shape, the statistics or the split changed
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("DynamicsModelPopulation: the item table changed inside a graph capture; "
                                    "call sync_sim_items() in front of it")
             di.wait()
             ctypes.memmove(di.h_ptr, ctypes.addressof(fresh), len(image))
             di.upload()
-            self._sent["sim"] = image
-        return di
+            self._sent[key] = image
+
+    def _sync_mfma_items(self, ways, counts):
+        """One compact item table per grouped MFMA class (``self._sim_mfma``: way -> DeviceItems): the class's models with
+        problems, each with its packed weight image -- CREATED here if the model has none yet, so that a capture finds it
+        (``refresh_prepared_image`` only re-packs an existing one)."""
+        from .population import DeviceItems
+        device = self.models[0].device
+        starts = [sum(counts[:p]) for p in range(len(counts))]
+        live = {}
+        for p, (m, way, n) in enumerate(zip(self.models, ways, counts)):
+            if way.startswith("mfma<") and n > 0:
+                live.setdefault(way, []).append(p)
+        for way in [w for w in self._sim_mfma if w not in live]:
+            del self._sim_mfma[way]
+            self._sent.pop(way, None)
+        for way, group in live.items():
+            fresh = (_ffi.MpcSimManyMfmaItem * len(group))()
+            for it, p in zip(fresh, group):
+                m = self.models[p]
+                if m._image is None and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("DynamicsModelPopulation: a grouped model has no packed image inside a graph capture; "
+                                       "call sync_sim_items() in front of it")
+                with torch.cuda.device(device):
+                    img = m._mfma_image()
+                m._mfma_ok = True
+                it.mlp, it.d_image, it.image_bytes, it.problem0, it.n_problems = m.desc, img.data_ptr(), img.numel(), starts[p], counts[p]
+            di = self._sim_mfma.get(way)
+            if di is None or di.n != len(group) or di.device != device:
+                di = self._sim_mfma[way] = DeviceItems(_ffi.MpcSimManyMfmaItem, len(group), device)
+                self._sent.pop(way, None)
+            self._upload_items(way, di, fresh, bytes(fresh))
 
     def do_forward_sim_sampled(self, state0, sampling, problems_per_model, H, out=None, A_out=None):
         """``do_forward_sim_sampled`` for a problem-major batch whose problems belong to different models: model p owns
         the next ``problems_per_model[p]`` problems (one count, or one per model) of ``sampling.n_samples`` candidate rows
-        each.  The models of ``sim_ways == "many"`` go through ONE ``ssc_mpc_forward_sim_many`` launch; every other model
-        through its own call into a scratch [H+1, m_p, d] and a strided copy into its rows (the masked single call is no
+        each.  The models of ``sim_ways == "many"`` go through ONE ``ssc_mpc_forward_sim_many`` launch, those of every
+        ``"mfma<..>"`` way through one ``ssc_mpc_forward_sim_many_mfma`` launch per class; every other model through its own call into a scratch [H+1, m_p, d] and a strided copy into its rows (the masked single call is no
         substitute: the streamed MFMA kernel ignores the mask).  Every row ends up, bit for bit, where its model's own
         call with ``problem_id0 + first problem`` leaves it.  Returns S [H+1, m, d]."""
         P, N, H = len(self.models), int(sampling.n_samples), int(H)
@@ -561,6 +620,11 @@ class DynamicsModelPopulation:
             if di is not None:
                 _ffi.check(first.lib.ssc_mpc_forward_sim_many(di.h_ptr, di.d_ptr, P, ctypes.byref(sampling), M, H, d, a,
                                                               _ffi.ptr(s0), s0_rows, _ffi.ptr(A_out), _ffi.ptr(S), _ffi.stream()))
+            for way in sorted(self._sim_mfma):
+                dm = self._sim_mfma[way]
+                _ffi.check(first.lib.ssc_mpc_forward_sim_many_mfma(dm.h_ptr, dm.d_ptr, dm.n, ctypes.byref(sampling), M, H, d, a,
+                                                                   _ffi.ptr(s0), s0_rows, _ffi.ptr(A_out), _ffi.ptr(S),
+                                                                   _ffi.stream()))
             at = 0
             for p, (m, way, n) in enumerate(zip(self.models, ways, counts)):
                 if way == "alone" and n > 0:
@@ -604,6 +668,8 @@ class DynamicsModelPopulation:
 NAV_POPULATION_GROUPED = True       # False: every model simulates through its own call and a strided copy (the yardstick)
 # the smallest number of fused-family models one ssc_mpc_forward_sim_many call serves (profiles/nav_population)
 NAV_POPULATION_MIN_GROUP = 2
+# the same for the bf16 MFMA models of one class and ssc_mpc_forward_sim_many_mfma (profiles/nav_population/mfma_sim.json)
+NAV_POPULATION_MFMA_MIN_GROUP = 2
 
 
 def mpc_sampling(N, low, high, seed, problem_id0=0, t=0, t_base=None, active=None, live_list=None, n_live=None):
@@ -1046,9 +1112,10 @@ class NavigatorPopulation(NavigatorBatch):
 
     def _model_key(self):
         """every model's weight pointers, statistics bytes, precision, image and workspace; the split, the way per model,
-        the item table's addresses and the scratch of the models that simulate alone"""
+        the item tables' addresses (fp32 and one per MFMA class) and the scratch of the models that simulate alone"""
         pop = self.models
         di = pop._items.get("sim")
         return (tuple(_model_key(m) for m in pop.models), tuple(self.envs_per_model), tuple(pop.sim_ways),
                 None if di is None else (di.h_ptr, di.d_ptr),
+                tuple((w, t.h_ptr, t.d_ptr, t.n) for w, t in sorted(pop._sim_mfma.items())),
                 tuple(sorted((k, v.data_ptr()) for k, v in pop._sim_scratch.items())))
