@@ -73,9 +73,11 @@ static __device__ void net_rows(const NET &n, const float *x, int in_dim, const 
         __syncthreads();
     }
     for (int a = part; a < out_dim; a += kSParts) {
-        float o = n.b3[a];
+        // the actor's chain starts from b3 (the actor kernels' bits); a head without an output tanh -- the critic -- adds
+        // b3 behind a chain that starts from zero, as critic_kernel does (smartstart.hip has the reason)
+        float o = out_tanh ? n.b3[a] : 0.0f;
         for (int j = 0; j < n.h2; ++j) o = fmaf(h2s[j * kSR + row], n.W3[j * out_dim + a], o);
-        out[a * kSR + row] = out_tanh ? tanh_fast(o) : o;
+        out[a * kSR + row] = out_tanh ? tanh_fast(o) : o + n.b3[a];
     }
     __syncthreads();
 }

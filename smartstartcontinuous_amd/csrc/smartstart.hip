@@ -58,7 +58,10 @@ __global__ __launch_bounds__(64) void critic_kernel(CriticW w, int64_t m, const 
     for (int a = 0; a < w.act_dim; ++a) hs[(w.h1 + a) * 64 + lane] = act[i * w.act_dim + a];  // :89
     const int in2 = w.h1 + w.act_dim;
     float *h2s = hs + in2 * 64;
-    float out = w.b3[0];
+    // The output chain starts from zero and b3 is added behind it: b3 follows the mean return (tens), the h2 terms are of
+    // order one, and a chain that starts from b3 rounds every partial sum at b3's size -- sqrt(h2) roundings of |b3| where
+    // this order has one (tests/forward_cases.py: the bias-first chain misses the derived float32 bound).
+    float out = 0.0f;
     for (int j = 0; j < w.h2; ++j) {
         float acc = w.b2[j];
         for (int k = 0; k < in2; ++k) acc = fmaf(hs[k * 64 + lane], w.W2[k * w.h2 + j], acc);
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(64) void critic_kernel(CriticW w, int64_t m, const 
             out = fmaf(w.last_tanh ? tanhf(n2) : fmaxf(n2, 0.0f), w.W3[j], out);
         }
     }
-    if (active) q[i] = out;
+    if (active) q[i] = out + w.b3[0];
 }
 
 constexpr int kKdeQ = 8;        // query points per block

@@ -424,11 +424,22 @@ def _tanh_bwd(d, Ed, u, Eu):
     return dd, (None if Ed is None else Ed * (1 - u * u) + np.abs(d) * (2 * np.abs(u) * Eu + 1) + np.abs(dd))
 
 
-def _hidden2(ar, n2, En2, llt):
+def _relu_E(n, En, band):
+    """E behind a relu: E(z) under the fp64 mask; with ``band`` a unit whose |z| <= band 2^-24 E(z) keeps E(z) as well (the
+    float32 value of such a unit may lie on the other side of zero: tests/forward_cases.py)"""
+    if En is None:
+        return None
+    mask = n > 0
+    if band is not None:
+        mask = mask | (np.abs(n) <= band * EPS32 * En)
+    return En * mask
+
+
+def _hidden2(ar, n2, En2, llt, relu_band=None):
     """second hidden layer's activation: (u, E(u), relu pre-activation or None)"""
     if llt:
         return _tanh_fwd(ar, n2, En2) + (None,)
-    return np.maximum(n2, ar.t(0)), (None if En2 is None else En2 * (n2 > 0)), n2
+    return np.maximum(n2, ar.t(0)), _relu_E(n2, En2, relu_band), n2
 
 
 def _hidden2_bwd(d, Ed, c, llt):
@@ -437,17 +448,19 @@ def _hidden2_bwd(d, Ed, c, llt):
     return d * (c["n2"] > 0), (None if Ed is None else Ed * (c["n2"] > 0))
 
 
-def _net_fwd(ar, p, x, Ex, llt, act=None, Eact=None):
-    """actor (act None: ends in tanh) or critic (the action joins the first hidden layer's output): (out, E(out), cache)"""
+def _net_fwd(ar, p, x, Ex, llt, act=None, Eact=None, relu_band=None):
+    """actor (act None: ends in tanh) or critic (the action joins the first hidden layer's output): (out, E(out), cache).
+    ``relu_band``: None -- E passes a relu under the fp64 mask (the learner's batches keep their pre-activations THR from
+    zero); a number -- see _relu_E"""
     z1, Ez1 = _dense(ar, x, Ex, p["W1"], p["b1"])
     n1, En1, l1 = _ln_fwd(ar, z1, Ez1, p, "ln1")
-    a1, Ea1 = np.maximum(n1, ar.t(0)), (None if En1 is None else En1 * (n1 > 0))
+    a1, Ea1 = np.maximum(n1, ar.t(0)), _relu_E(n1, En1, relu_band)
     if act is not None:
         a1 = np.concatenate([a1, act], axis=1)
         Ea1 = None if Ea1 is None else np.concatenate([Ea1, Eact], axis=1)
     z2, Ez2 = _dense(ar, a1, Ea1, p["W2"], p["b2"])
     n2, En2, l2 = _ln_fwd(ar, z2, Ez2, p, "ln2")
-    a2, Ea2, pre2 = _hidden2(ar, n2, En2, llt)
+    a2, Ea2, pre2 = _hidden2(ar, n2, En2, llt, relu_band)
     out, Eout = _dense(ar, a2, Ea2, p["W3"], p["b3"])
     if Eout is not None and "E_W3" in p:        # an output layer that is itself a float32 result (tests/popart_grad_cases.py)
         Eout = Eout + np.abs(a2) @ p["E_W3"] + p["E_b3"]
