@@ -46,6 +46,11 @@ def main():
     ap.add_argument("--sequential-selection", action="store_true", help="vec mode: select, then roll (default: the selection of a chunk overlaps its rollout and its plans go on offer one chunk later)")
     ap.add_argument("--param-noise", type=float, default=None, metavar="STDDEV",
                     help="vec mode: adaptive parameter-space noise with this initial (and desired action) stddev on the base agent, on top of the OU noise")
+    ap.add_argument("--population", type=int, default=0, metavar="P",
+                    help="vec mode: P SmartStart pairs of --envs envs each in ONE VecEnv, stepping from one captured graph "
+                         "(VecSmartStartPopulation; sequential selection)")
+    ap.add_argument("--eta", default="0.5", help="smart-start probability; with --population one value or a comma list, one per pair")
+    ap.add_argument("--actor-hidden", default="64-32", help="actor h1-h2; with --population one value or a comma list, one per pair")
     ap.add_argument("--replay-capacity", type=int, default=None, help="records in the device ring (default: two full episodes per env)")
     args = ap.parse_args()
     np.random.seed(args.seed)
@@ -63,6 +68,8 @@ def main():
                                      nnd_mb_num_fc_layers=1, nnd_mb_depth_fc_layers=32, nnd_mb_nEpochs=30,
                                      nnd_mb_precision="f32", nnd_mb_seed=args.seed)
     nav = agent.nnd_mb_agent
+    if args.mode == "vec" and args.population:
+        return vec_population(args, nav.dyn_model)
     if args.mode == "vec":
         return vec(args, nav.dyn_model)
     print("navigator data set: %d rows, std_x %s" % (nav.dataX.shape[0], np.round([nav.dyn_model.norm.std_x[i] for i in range(2)], 4)))
@@ -128,6 +135,59 @@ def vec(args, dyn_model):
              args.chunk_steps, timed(lambda: smart.rollout(args.chunk_steps, chunk)),
              timed(lambda: replay.append_chunk(chunk, reward_scale=1.0)), args.train_iters,
              timed(lambda: ddpg.train_from(replay, args.train_iters))))
+
+
+def _per_pair(text, P, cast):
+    vals = [cast(x) for x in str(text).split(",")]
+    if len(vals) not in (1, P):
+        raise SystemExit("one value or one per pair (%d): %r" % (P, text))
+    return vals * P if len(vals) == 1 else vals
+
+
+def vec_population(args, dyn_model):
+    """The sweep of SmartStart_DDPG_Baselines_experimenter.py in one process: P pairs (seeds seed .. seed + P - 1, optional
+    per-pair eta and actor sizes), every pair with a copy of the trained navigator model, one graph of four launches per step."""
+    import time
+
+    import torch
+    from smartstartcontinuous_amd import navigator as nav
+    P = args.population
+    etas = _per_pair(args.eta, P, float)
+    hidden = _per_pair(args.actor_hidden, P, lambda s: tuple(int(x) for x in s.split("-")))
+    env = ssc.VecEnv("MountainCarContinuous-v0", P * args.envs, seed=args.seed, power_scalar=args.power_scalar,
+                     max_episode_steps=args.max_steps)
+    env.reset()
+    agents = [DDPG_Baselines_agent(ssc.make("MountainCarContinuous-v0"), None, batch_size=args.batch, num_train_iterations=args.train_iters,
+                                   ou_epsilon=1.0, ou_min_epsilon=0.01, ou_epsilon_decay_factor=.99, ou_mu=0.4, ou_sigma=0.6,
+                                   ou_theta=.15, actor_lr=0.001, actor_h1=h[0], actor_h2=h[1], critic_lr=0.001, critic_h1=64,
+                                   critic_h2=32, lastLayerTanh=True, seed=args.seed + p, precision="bf16_mfma",
+                                   param_noise_stddev=args.param_noise) for p, h in enumerate(hidden)]
+    norm = {k: [getattr(dyn_model.norm, k)[i] for i in range(n)] for k, n in (("mean_x", 2), ("std_x", 2), ("mean_y", 1), ("std_y", 1),
+                                                                                  ("mean_z", 2), ("std_z", 2))}
+    models = [nav.DynamicsModel([w.cpu().numpy() for w in dyn_model.W], [b.cpu().numpy() for b in dyn_model.b], norm, state_dim=2,
+                                act_dim=1, precision=args.nav_precision) for _ in range(P)]
+    smart = ssc.VecSmartStartPopulation(env, agents, models, [args.envs] * P, eta=etas, eta_decay_factor=1., n_ss=2000,
+                                        n_plans=args.plans, num_control_samples=args.samples, horizon=4, final_steps=10,
+                                        chunk_steps=args.chunk_steps, seed=args.seed, log_modes=True,
+                                        kde_max_states=args.kde_max_states or None)
+    cap = args.replay_capacity or 2 * args.envs * args.max_steps
+    kw = dict(chunk_steps=args.chunk_steps, train_iters=args.train_iters, replay_capacity=cap, refresh_every=args.refresh_every,
+              seed=[args.seed + p for p in range(P)])
+    ssc.rl_train_vec_smartstart_population(env, smart, 2, **kw)   # warm-up: allocations, graph capture
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = ssc.rl_train_vec_smartstart_population(env, smart, args.chunks, **kw)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    steps = P * args.envs * args.chunk_steps * args.chunks
+    print("vec smartstart population: %d pairs x %d envs x %d steps x %d chunks in %.2f s = %.3g env-steps/s; actor launches %s, "
+          "simulation %s" % (P, args.envs, args.chunk_steps, args.chunks, dt, steps / dt, [w[0] for w in smart._actor_plan],
+                             sorted(set(smart.nav.sim_ways))))
+    for p, ((summary, losses, replay), pr) in enumerate(zip(res, smart.pairs)):
+        eps = summary.episodes
+        print("  pair %d (eta %.2f, actor %d-%d): %d episodes, %d reached the goal, best return %.2f, %d selections, %d plans published"
+              % (p, etas[p], hidden[p][0], hidden[p][1], len(eps), sum(1 for (_n, r) in eps if r > 0), summary.best_reward if eps else float("nan"),
+                 pr.selections, pr.pool.published))
 
 
 if __name__ == "__main__":

@@ -698,6 +698,84 @@ int ssc_ddpg_train_ws_rms(const ssc_ddpg_desc *ddpg, const ssc_replay_view *repl
                           const double *d_rms);
 
 /* ---------------------------------------------------------------------------------------
+ * A population of SmartStart pairs in one captured step
+ *
+ * The reference fans SmartStart + DDPG over seeds and hyper-parameters
+ * (examples/continuous/SmartStart_DDPG_Baselines_experimenter.py); every pair runs SmartStartContinuous.get_action /
+ * observe / start_new_episode (smartstart/smartexploration/smartexplorationcontinuous.py:307-376) on envs, an agent, an
+ * eta and a plan pool of its own.  The two calls below serve the per-pair state of ALL pairs in one launch each.
+ * ------------------------------------------------------------------------------------- */
+
+/* One actor of a population and the rows of the call's observation matrix it acts on.  Declared tag first like the other
+ * *_many items; tests/test_smartstart_many_host.py holds the struct's size and offsets to the ctypes mirror. */
+struct ssc_actor_many_item {
+    ssc_actor_desc actor;
+    const double  *d_rms;   /* this actor's RunningMeanStd block; the call's class decides whether it is read */
+    int64_t        row0;    /* the item's rows: [row0, row0 + rows) of the call's m */
+    int64_t        rows;    /* 0: the item is skipped and nothing else of it is read */
+};
+typedef struct ssc_actor_many_item ssc_actor_many_item;
+
+/* The kernel class one many-call can serve this actor with (>= 0), or -1: a descriptor ssc_actor_forward refuses.
+ * class = 2 * body + (has_rms ? 1 : 0); bodies, by ssc_actor_forward's own rule for m > 32: 0 / 1 the fp32 64-32 kernel
+ * with obs_dim 2 / 3; 2 / 3 the bf16 MFMA kernel for h1 <= 64, h2 <= 32; 4 / 5 for h1 <= 128, h2 <= 64; 6 / 7 the
+ * LDS-staged one up to 224-128; 8 the generic fp32 kernel (any sizes, LayerNorm included).  A pure function of shape,
+ * precision and has_rms. */
+int ssc_actor_many_class(const ssc_actor_desc *actor, int has_rms);
+
+/* ssc_actor_forward[_rms] for a population of actors in ONE launch: item y acts on rows [row0, row0 + rows) of d_obs
+ * [m][obs_dim] and writes the same rows of d_act [m][act_dim].  Grid row y runs item y; its blocks are anchored at row0, so
+ * the partition into blocks and waves is that of the actor's own call on its slice (grid x = the largest item's block
+ * count; surplus blocks leave before any barrier or LDS staging).  The kernel runs the device bodies the single call
+ * dispatches at m > 32, so every owned row of d_act holds, bit for bit, what ssc_actor_forward[_rms](&actor, rows,
+ * d_obs + row0 * obs_dim, d_act + row0 * act_dim, .., d_rms) leaves there -- for an item of <= 32 rows too (the single
+ * call's row kernel returns the generic kernel's bits).  Rows no item owns are untouched.
+ * One call serves ONE class (ssc_actor_many_class with has_rms = d_rms != NULL); every working item has the obs_dim and
+ * act_dim of the first.  Conventions of the other *_many calls: the host array is validated completely before any HIP
+ * call, the caller's device copy of the same bytes must be complete on `stream`, the library copies nothing, item indices
+ * appear in ssc_last_error().  n_items 1..65535 (more: SSC_EUNSUPPORTED).  The single call's per-descriptor checks apply to
+ * every item with rows > 0 (its codes) as they stand at m > 32: an fp32 network too wide for the generic kernel's LDS is
+ * SSC_EUNSUPPORTED at any row count (the single call serves <= 32 rows of it through its row kernel); two items of different classes are SSC_EUNSUPPORTED naming both and their classes, an item with
+ * no class is SSC_EUNSUPPORTED; a range outside [0, m), two overlapping ranges (gaps are legal) or NULL tables are
+ * SSC_EINVAL.  m == 0, or every item empty: SSC_OK without a launch. */
+int ssc_actor_forward_many(const ssc_actor_many_item *h_items, const ssc_actor_many_item *d_items, int32_t n_items, int64_t m,
+                           const float *d_obs, float *d_act, ssc_stream_t stream);
+
+/* One SmartStart pair of a population step: a row of a DEVICE table the host rewrites between chunks (the kernel reads it
+ * when it starts, so a captured graph follows the host's decay schedule and pool refreshes exactly as
+ * ssc_smartstart_step.d_eta / d_ou_epsilon / d_pool let a single pair's graph).  tests/test_smartstart_many_host.py holds
+ * the struct's size and offsets to the ctypes mirror. */
+struct ssc_smartstart_pair {
+    int32_t env0, n_envs;                       /* the pair's envs: [env0, env0 + n_envs) of the call's P */
+    int32_t slot0;                              /* first slot of its window of the plan arrays */
+    int32_t pool_first, pool_count, pool_slots; /* ssc_smartstart_step.d_pool, relative to slot0 */
+    float   eta, ou_epsilon;                    /* ssc_smartstart_step.d_eta / d_ou_epsilon */
+    ssc_ou_desc ou;                             /* epsilon field unused */
+};
+typedef struct ssc_smartstart_pair ssc_smartstart_pair;
+
+/* ssc_smartstart_rollout_step for n_pairs SmartStart pairs in ONE launch.  The call's P envs (one VecEnv, RNG streams keyed
+ * by the global env / problem id as ever) are split into contiguous ranges, one per pair; grid row y is pair y, its blocks
+ * anchored at env0 (grid x = the largest pair's block count).  The step is the single kernel's, arithmetic and order of
+ * loads unchanged; eta, the OU epsilon, the OU process and the plan pool come from d_pairs[y]: a fresh plan is slot
+ * slot0 + (pool_first + word % pool_count) % pool_slots of the plan arrays.  `ss` keeps mode, plan_of, d_actor_out, the
+ * action bounds, d_mode_log and mode_log_stride; its d_eta, d_ou_epsilon, d_pool and ou are not read, and d_n_live must be
+ * NULL (the population path has no compact live list).  d_stats is [n_pairs][4] (may be NULL): row y receives pair y's
+ * block sums.  The ticket counts all blocks of the 2-D grid and advances *d_t / *d_k once.
+ * Host checks before any HIP call: those of the single call; n_pairs 1..65535 (more: SSC_EUNSUPPORTED, as in the other
+ * *_many calls); ranges non-empty, in order, disjoint and
+ * inside [0, P); pool_slots >= 1, 0 <= pool_first < pool_slots, 0 <= pool_count <= pool_slots; slot0 >= 0 (SSC_EINVAL with
+ * the pair index in ssc_last_error()).  The host table is validated; the caller's device copy must be complete on
+ * `stream` and hold rows that pass the same checks whenever the launch (or a replay of its graph) runs. */
+int ssc_smartstart_rollout_step_many(const ssc_env_params *p, const ssc_mpc_problems *problems, const ssc_mpc_nav_state *nav,
+                                     const ssc_smartstart_step *ss, const ssc_smartstart_pair *h_pairs,
+                                     const ssc_smartstart_pair *d_pairs, int32_t n_pairs, const float *d_A,
+                                     const int32_t *d_best_idx, float noise_amount, uint64_t noise_seed, uint64_t problem_id0,
+                                     const ssc_rollout_state *state, const ssc_transition_log *log,
+                                     const ssc_episode_ring *ring, double *d_stats, uint64_t env_seed, uint64_t env_id0,
+                                     uint64_t *d_t, int32_t *d_k, int32_t *d_ticket, float *d_plan_state, ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * normalize_returns + enable_popart (ddpg_editted.py:129-133, 140-149, 201-217, 291-301; arXiv 1602.07714)
  * -------------------------------------------------------------------------------------
  * ret_rms is the same RunningMeanStd as above with one column: d_ret_rms = [sum | sumsq | count] in f64, caller-

@@ -138,6 +138,15 @@ class MpcSimManyMfmaItem(Structure):
                 ("n_problems", c_int32)]
 
 
+class ActorManyItem(Structure):
+    _fields_ = [("actor", ActorDesc), ("d_rms", c_void_p), ("row0", c_int64), ("rows", c_int64)]
+
+
+class SmartStartPair(Structure):
+    _fields_ = [("env0", c_int32), ("n_envs", c_int32), ("slot0", c_int32), ("pool_first", c_int32), ("pool_count", c_int32),
+                ("pool_slots", c_int32), ("eta", c_float), ("ou_epsilon", c_float), ("ou", OuDesc)]
+
+
 class DdpgDesc(Structure):
     _fields_ = [("obs_dim", c_int32), ("act_dim", c_int32), ("actor_h1", c_int32), ("actor_h2", c_int32),
                 ("critic_h1", c_int32), ("critic_h2", c_int32), ("last_layer_tanh", c_int32), ("batch_size", c_int32),
@@ -243,6 +252,7 @@ STRUCTS = {
     "ssc_ddpg_stats_many_item": DdpgStatsManyItem, "ssc_param_noise_many_item": ParamNoiseManyItem,
     "ssc_param_noise_cursor": ParamNoiseCursor, "ssc_mlp_train_many_item": MlpTrainManyItem,
     "ssc_mpc_sim_many_item": MpcSimManyItem, "ssc_mpc_sim_many_mfma_item": MpcSimManyMfmaItem,
+    "ssc_actor_many_item": ActorManyItem, "ssc_smartstart_pair": SmartStartPair,
 }
 
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
@@ -385,6 +395,14 @@ _SIGNATURES = {
                                             c_void_p, c_void_p, c_float, c_uint64, c_uint64, POINTER(RolloutState),
                                             POINTER(TransitionLog), POINTER(EpisodeRing), c_void_p, c_uint64, c_uint64, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    # a population of SmartStart pairs: all actors of one class, and the step of all pairs, in one launch each
+    "ssc_actor_many_class": (c_int, [POINTER(ActorDesc), c_int]),
+    "ssc_actor_forward_many": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ssc_smartstart_rollout_step_many": (c_int, [POINTER(EnvParams), POINTER(MpcProblems), POINTER(MpcNavState),
+                                                 POINTER(SmartStartStep), c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_float,
+                                                 c_uint64, c_uint64, POINTER(RolloutState), POINTER(TransitionLog),
+                                                 POINTER(EpisodeRing), c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p]),
     "ssc_nav_compact": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssc_mpc_score_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "ssc_mpc_score": (c_int, [POINTER(MpcProblems), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

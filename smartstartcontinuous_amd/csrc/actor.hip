@@ -7,6 +7,10 @@
 
 namespace ssc {
 
+// NOTE: the bodies of the four batched kernels below are restated as device functions in actor_device.h (actor_net_body,
+// actor_generic_body) for ssc_actor_forward_many (actor_many.hip), which must return these kernels' bits: a change here
+// belongs there too (tests/test_gpu_actor_forward_many.py compares the two bit for bit).
+
 // canonical sizes: one row per lane, fp32 VALU
 template <int OBS, int H1, int H2, class... Rms>
 __global__ __launch_bounds__(kBlock) void actor_f32_kernel(ActorWeights w, int64_t m, const float *__restrict__ obs,

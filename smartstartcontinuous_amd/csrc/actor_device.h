@@ -666,4 +666,95 @@ struct ActorMfma2 {
     __device__ float forward(const float (&obs)[2]) const { return tanh_fast(forward_pre(obs[0], obs[1])); }
 };
 
+// ---------------------------------------------------------------------------------------
+// The bodies of the batched forward kernels of actor.hip as device functions, for kernels that serve SEVERAL networks in one
+// launch (actor_many.hip: one item per grid row).  Each is the text of the __global__ of the same name: rows [0, m) of
+// obs / act, block blockIdx.x owning the rows from blockIdx.x * blockDim.x on -- a caller that serves a slice moves the two
+// pointers to the slice's first row and passes its row count, and gets the partition into blocks and waves, and the bits,
+// of the network's own call on that slice.  Block-cooperative: whole blocks call them (m >= 1).
+// ---------------------------------------------------------------------------------------
+template <class Net, int OBS, class... Rms>
+__device__ __forceinline__ void actor_net_body(const ActorWeights &w, int64_t m, const float *__restrict__ obs,
+                                               float *__restrict__ act, Rms... rms) {
+    const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = gi < m;
+    const int64_t i = active ? gi : m - 1;  // whole waves must run the collective forward
+    float o[OBS];
+    if constexpr (kObsNorm<Rms...>) {
+        ObsNorm<OBS> nrm;
+        nrm.load(rms_block(rms...), OBS);
+#pragma unroll
+        for (int c = 0; c < OBS; ++c) o[c] = nrm.apply(obs[i * OBS + c], c, w.obs_clip);
+    } else {
+#pragma unroll
+        for (int c = 0; c < OBS; ++c) o[c] = clip_obs(obs[i * OBS + c], w.obs_clip);
+    }
+    Net net;
+    net.init(w);  // block-cooperative LDS staging: no thread may have exited
+    const float a = net.forward(o);
+    if (active) act[i] = a;
+}
+
+// actor_generic_kernel's body: 64-thread blocks, h1s = dynamic LDS of (h1 + (LayerNorm ? h2 : 0)) * 64 floats
+template <class... Rms>
+__device__ __forceinline__ void actor_generic_body(const ActorWeights &w, int act_dim, int64_t m, const float *__restrict__ obs,
+                                                   float *__restrict__ act, float *h1s, Rms... rms) {
+    const int lane = threadIdx.x;
+    const int64_t gi = (int64_t)blockIdx.x * 64 + lane;
+    const bool active = gi < m;
+    const int64_t i = active ? gi : m - 1;
+    const bool ln = w.ln1_g != nullptr;   // models_editted.py:45-46, 50-51
+    float o[SSC_MAX_STATE];
+    if constexpr (kObsNorm<Rms...>) {
+        ObsNorm<SSC_MAX_STATE> nrm;
+        nrm.load(rms_block(rms...), w.obs_dim);
+#pragma unroll
+        for (int c = 0; c < SSC_MAX_STATE; ++c) o[c] = (c < w.obs_dim) ? nrm.apply(obs[i * w.obs_dim + c], c, w.obs_clip) : 0.0f;
+    } else {
+#pragma unroll
+        for (int c = 0; c < SSC_MAX_STATE; ++c) o[c] = (c < w.obs_dim) ? clip_obs(obs[i * w.obs_dim + c], w.obs_clip) : 0.0f;
+    }
+    for (int j = 0; j < w.h1; ++j) {
+        float acc = w.b1[j];
+#pragma unroll
+        for (int c = 0; c < SSC_MAX_STATE; ++c)
+            if (c < w.obs_dim) acc = fmaf(o[c], w.W1[c * w.h1 + j], acc);
+        h1s[j * 64 + lane] = ln ? acc : fmaxf(acc, 0.0f);
+    }
+    if (ln) {
+        float mean, rstd;
+        layer_norm_stats(h1s + lane, w.h1, 64, mean, rstd);
+        for (int j = 0; j < w.h1; ++j)
+            h1s[j * 64 + lane] = fmaxf(fmaf((h1s[j * 64 + lane] - mean) * rstd, w.ln1_g[j], w.ln1_b[j]), 0.0f);
+    }
+    float out[SSC_MAX_ACT];
+#pragma unroll
+    for (int a = 0; a < SSC_MAX_ACT; ++a) out[a] = (a < act_dim) ? w.b3[a] : 0.0f;
+    float *h2s = h1s + w.h1 * 64;
+    for (int j = 0; j < w.h2; ++j) {
+        float acc = w.b2[j];
+        for (int k = 0; k < w.h1; ++k) acc = fmaf(h1s[k * 64 + lane], w.W2[k * w.h2 + j], acc);
+        if (ln) { h2s[j * 64 + lane] = acc; continue; }
+        const float h2 = w.last_layer_tanh ? tanh_fast(acc) : fmaxf(acc, 0.0f);
+#pragma unroll
+        for (int a = 0; a < SSC_MAX_ACT; ++a)
+            if (a < act_dim) out[a] = fmaf(h2, w.W3[j * act_dim + a], out[a]);
+    }
+    if (ln) {
+        float mean, rstd;
+        layer_norm_stats(h2s + lane, w.h2, 64, mean, rstd);
+        for (int j = 0; j < w.h2; ++j) {
+            const float n2 = fmaf((h2s[j * 64 + lane] - mean) * rstd, w.ln2_g[j], w.ln2_b[j]);
+            const float h2 = w.last_layer_tanh ? tanh_fast(n2) : fmaxf(n2, 0.0f);
+#pragma unroll
+            for (int a = 0; a < SSC_MAX_ACT; ++a)
+                if (a < act_dim) out[a] = fmaf(h2, w.W3[j * act_dim + a], out[a]);
+        }
+    }
+    if (active)
+#pragma unroll
+        for (int a = 0; a < SSC_MAX_ACT; ++a)
+            if (a < act_dim) act[i * act_dim + a] = tanh_fast(out[a]);
+}
+
 }  // namespace ssc

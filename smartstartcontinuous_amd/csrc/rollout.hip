@@ -720,15 +720,36 @@ struct SsStepArgs {
     int32_t *n_live;   // ssc_smartstart_step::d_n_live: zeroed here for the next step's ssc_nav_compact
 };
 
-template <class EnvT, bool SS = false>
-__global__ __launch_bounds__(kBlock) void mpc_rollout_step_kernel(typename EnvT::Const ec, RolloutArgs ra, MpcStepArgs ma, SsStepArgs sa) {
+// The population form (ssc_smartstart_rollout_step_many) is an instantiation of its own: ONE extra trailing argument, the
+// device table of ssc_smartstart_pair rows, spelled as a parameter pack like the kernels' statistics block -- with an empty
+// pack the kernel keeps its parameter list and code.  Grid row y is pair y: its envs are [env0, env0 + n_envs) of the call's,
+// its blocks anchored at env0, and what the single step reads through sa.d_eta / d_eps / d_pool and the OU scalars comes from
+// row y of the table (block-uniform address: scalar loads).
+typedef const __attribute__((address_space(4))) ssc_smartstart_pair *const_ss_pair;
+template <class... Many> inline constexpr bool kSsMany = sizeof...(Many) > 0;
+template <class... Many> __device__ __forceinline__ const_ss_pair ss_pair_row(Many... many) {
+    if constexpr (sizeof...(Many) > 0) return (const_ss_pair)(many, ...) + blockIdx.y;
+    else return nullptr;
+}
+
+template <class EnvT, bool SS = false, class... Many>
+__global__ __launch_bounds__(kBlock) void mpc_rollout_step_kernel(typename EnvT::Const ec, RolloutArgs ra, MpcStepArgs ma, SsStepArgs sa,
+                                                                  Many... many) {
     constexpr int OBS = EnvT::OBS;
+    constexpr bool MANY = kSsMany<Many...>;
+    static_assert(!MANY || SS, "the pair table belongs to the SmartStart step");
+    [[maybe_unused]] const const_ss_pair pair = ss_pair_row(many...);
     // the navigator plans in observation space (checked on the host): with the dimension a constant the waypoint / radii loads of
     // the bookkeeping below are straight-line and go out together -- as a run-time bound every one of them was a branch with a
     // load and a full wait behind it, a dozen dependent round trips in a kernel that is one wave per SIMD
     ma.nav.d = OBS;
-    const int64_t gi = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (SS && gi == 0 && sa.n_live != nullptr) *sa.n_live = 0;   // simulation and scoring of this step are behind us in the stream
+    int64_t gi = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if constexpr (MANY) {   // the pair's envs; a surplus block (a smaller pair than the grid's widest) is inactive throughout
+        gi += pair->env0;
+        ra.n = (int64_t)pair->env0 + pair->n_envs;
+        if (ra.stats != nullptr) ra.stats += 4 * blockIdx.y;
+    }
+    if (!MANY && SS && gi == 0 && sa.n_live != nullptr) *sa.n_live = 0;   // simulation and scoring of this step are behind us in the stream
     const bool active = gi < ra.n;
     const int64_t i = active ? gi : ra.n - 1;
     const uint64_t t = *ma.d_t;
@@ -769,7 +790,12 @@ __global__ __launch_bounds__(kBlock) void mpc_rollout_step_kernel(typename EnvT:
             // DDPG_Baselines_agent.get_action (:206-240): actor + epsilon * OU, clip, scale twice -- ActorPolicy::act's
             // arithmetic and noise stream; the OU state moves on these steps only (the agent is not asked while navigating)
             a = sa.actor_out[i];
-            const float eps = fmaxf(*sa.d_eps, 0.0f);
+            if constexpr (MANY) {   // the products the single call's host code forms, as the same floats (correctly rounded sqrtf)
+                sa.ou_mu = pair->ou.mu;
+                sa.ou_sig_sqrt_dt = pair->ou.sigma * sqrtf(pair->ou.dt);
+                sa.ou_theta_dt = pair->ou.theta * pair->ou.dt;
+            }
+            const float eps = fmaxf(MANY ? pair->ou_epsilon : *sa.d_eps, 0.0f);
             if (eps > 0.0f) {
                 const u32x4 w = rng_words(ra.seed, ra.env_id0 + (uint64_t)i, t >> 2, TAG_OU);
                 const float g = ou_gaussian_from_words(w, t);
@@ -831,9 +857,10 @@ __global__ __launch_bounds__(kBlock) void mpc_rollout_step_kernel(typename EnvT:
                 // SmartStartContinuous.start_new_episode (:341-370) on the reset state
                 navigating = false;
                 const u32x4 w = rng_words(ra.seed, ra.env_id0 + (uint64_t)i, t, TAG_SS_EPISODE);
-                const int first = sa.d_pool[0], count = sa.d_pool[1], slots = sa.d_pool[2];
-                if (count > 0 && (float)(w.x >> 8) * (1.0f / 16777216.0f) <= *sa.d_eta) {   // np.random.rand() <= eta (:350)
-                    const int q = (first + (int)(w.y % (uint32_t)count)) % slots;
+                const int first = MANY ? pair->pool_first : sa.d_pool[0], count = MANY ? pair->pool_count : sa.d_pool[1],
+                          slots = MANY ? pair->pool_slots : sa.d_pool[2];
+                if (count > 0 && (float)(w.x >> 8) * (1.0f / 16777216.0f) <= (MANY ? pair->eta : *sa.d_eta)) {   // np.random.rand() <= eta (:350)
+                    const int q = (MANY ? pair->slot0 : 0) + (first + (int)(w.y % (uint32_t)count)) % slots;
                     sa.plan_of[i] = q;    // read by the scorer of the next step (same stream)
                     idx = 0;
                     // close_enough_to_goal(state) with a fresh plan (:425-432): the goal test alone
@@ -889,7 +916,7 @@ __global__ __launch_bounds__(kBlock) void mpc_rollout_step_kernel(typename EnvT:
     // it was 15 of this kernel's 37 us at 65 536 envs.  What the step wrote is published by the kernel boundary.
     if (threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (__hip_atomic_fetch_add(ma.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
+        if (__hip_atomic_fetch_add(ma.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)(gridDim.x * (MANY ? gridDim.y : 1u)) - 1) {
             *ma.ticket = 0;
             *ma.d_t = t + 1;
             *ma.d_k = k + 1;
@@ -1226,4 +1253,66 @@ extern "C" int ssc_smartstart_rollout_step(const ssc_env_params *p, const ssc_mp
         return set_error(SSC_EINVAL, "ssc_smartstart_rollout_step: unknown env kind %d", p->kind);
     }
     return check_launch("ssc_smartstart_rollout_step");
+}
+
+// the step for a population of SmartStart pairs: grid row y = pair y of the device table (read by the kernel at launch)
+extern "C" int ssc_smartstart_rollout_step_many(const ssc_env_params *p, const ssc_mpc_problems *pr, const ssc_mpc_nav_state *nav,
+                                                const ssc_smartstart_step *ss, const ssc_smartstart_pair *h_pairs,
+                                                const ssc_smartstart_pair *d_pairs, int32_t n_pairs, const float *d_A,
+                                                const int32_t *d_best_idx, float noise_amount, uint64_t noise_seed,
+                                                uint64_t problem_id0, const ssc_rollout_state *state, const ssc_transition_log *log,
+                                                const ssc_episode_ring *ring, double *d_stats, uint64_t env_seed, uint64_t env_id0,
+                                                uint64_t *d_t, int32_t *d_k, int32_t *d_ticket, float *d_plan_state,
+                                                ssc_stream_t stream) {
+    const char *fn = "ssc_smartstart_rollout_step_many";
+    RolloutArgs ra;
+    MpcStepArgs ma;
+    if (int rc = build_mpc_step_args(fn, p, pr, nav, d_A, d_best_idx, noise_amount, noise_seed, problem_id0, state, log, ring, d_stats,
+                                     env_seed, env_id0, d_t, d_k, d_ticket, d_plan_state, ra, ma))
+        return rc;
+    SSC_REQUIRE(ss != nullptr, "%s: NULL step descriptor", fn);
+    SSC_REQUIRE(ss->mode && ss->plan_of && ss->d_actor_out, "%s: NULL device pointer in the step descriptor", fn);
+    SSC_REQUIRE(pr->plan_of != nullptr && pr->plan_of == ss->plan_of && pr->wp_len != nullptr,
+                "%s: the problem set must use the plan pool (plan_of == ss->plan_of, wp_len)", fn);
+    SSC_REQUIRE(state->ou_x != nullptr, "%s: the base agent's OU noise needs state->ou_x", fn);
+    SSC_REQUIRE(ss->act_low <= ss->act_high && ss->mode_log_stride >= 0, "%s: bad action bounds / stride", fn);
+    SSC_REQUIRE(ss->d_n_live == nullptr, "%s: the population step has no compact live list: d_n_live must be NULL", fn);
+    SSC_REQUIRE(n_pairs >= 1, "%s: n_pairs %d < 1", fn, n_pairs);
+    if (n_pairs > 65535) return set_error(SSC_EUNSUPPORTED, "%s: n_pairs %d > 65535 (one grid row each)", fn, n_pairs);
+    SSC_REQUIRE(h_pairs != nullptr && d_pairs != nullptr, "%s: NULL pair table", fn);
+    const int64_t n = ra.n;
+    int64_t at = 0;          // the end of the range before
+    int32_t n_max = 0;
+    for (int y = 0; y < n_pairs; ++y) {
+        const ssc_smartstart_pair &q = h_pairs[y];
+        SSC_REQUIRE(q.n_envs >= 1, "%s: pair %d: n_envs %d < 1", fn, y, q.n_envs);
+        SSC_REQUIRE(q.env0 >= 0 && (int64_t)q.env0 + q.n_envs <= n, "%s: pair %d: envs [%d, %lld) outside [0, %lld)", fn, y, q.env0,
+                    (long long)q.env0 + q.n_envs, (long long)n);
+        SSC_REQUIRE(q.env0 >= at, "%s: pair %d: envs [%d, %lld) overlap pair %d's or are out of order", fn, y, q.env0,
+                    (long long)q.env0 + q.n_envs, y - 1);
+        SSC_REQUIRE(q.pool_slots >= 1 && q.pool_first >= 0 && q.pool_first < q.pool_slots && q.pool_count >= 0 &&
+                    q.pool_count <= q.pool_slots, "%s: pair %d: bad pool (first %d, count %d, slots %d)", fn, y, q.pool_first,
+                    q.pool_count, q.pool_slots);
+        SSC_REQUIRE(q.slot0 >= 0, "%s: pair %d: slot0 %d < 0", fn, y, q.slot0);
+        at = (int64_t)q.env0 + q.n_envs;
+        n_max = std::max(n_max, q.n_envs);
+    }
+    SsStepArgs sa{};
+    sa.mode = ss->mode; sa.plan_of = ss->plan_of; sa.actor_out = ss->d_actor_out;
+    sa.act_low = ss->act_low; sa.act_high = ss->act_high;
+    sa.mode_log = ss->d_mode_log; sa.mode_log_stride = ss->mode_log_stride ? ss->mode_log_stride : n;
+    SSC_REQUIRE(sa.mode_log_stride >= n, "%s: mode log stride < n", fn);
+    hipStream_t s = as_stream(stream);
+    const dim3 grid(blocks_for(n_max), (unsigned)n_pairs), block(kBlock);
+    if (p->kind == SSC_ENV_MOUNTAINCAR) {
+        if (int rc = validate_mc_params(p, fn)) return rc;
+        hipLaunchKernelGGL((mpc_rollout_step_kernel<McEnv, true, const ssc_smartstart_pair *>), grid, block, 0, s, make_mc_const(*p), ra, ma,
+                           sa, d_pairs);
+    } else if (p->kind == SSC_ENV_PENDULUM) {
+        hipLaunchKernelGGL((mpc_rollout_step_kernel<PendEnv, true, const ssc_smartstart_pair *>), grid, block, 0, s, make_pend_const(*p), ra,
+                           ma, sa, d_pairs);
+    } else {
+        return set_error(SSC_EINVAL, "%s: unknown env kind %d", fn, p->kind);
+    }
+    return check_launch(fn);
 }

@@ -775,6 +775,32 @@ class PlanPool:
         self._next = 0
         self.published = 0
         self.active = None      # optional uint8 [n_envs]: only problems marked non-zero are simulated / scored
+        self.slot0 = 0          # first slot of this pool inside the arrays it writes (a window: see ``window``)
+        self.triple = (0, 0, self.n_slots)   # host copy of ``pool``: (first slot on offer, plans on offer, slots)
+
+    def window(self, env0, n_envs, slot0, n_slots):
+        """Envs [env0, env0 + n_envs) and slots [slot0, slot0 + n_slots) of this pool as a pool of their own -- one
+        SmartStart pair of a population (``smartstart.VecSmartStartPopulation``): the round-robin ``publish``, the young-slot
+        warning and the ``triple`` are the window's, the arrays are views of this pool's, so the population's one scorer and
+        step launch read what the pair published.  Slot numbers inside the window count from 0: the kernels add ``slot0``
+        (``ssc_smartstart_pair.slot0``; ``plan_of`` holds slot0 + slot).  The window's ``pool`` triple stays on the host --
+        it travels to the device in the pair table."""
+        env0, n_envs, slot0, n_slots = int(env0), int(n_envs), int(slot0), int(n_slots)
+        if not (0 <= env0 and env0 + n_envs <= self.P and 0 <= slot0 and n_slots >= 1 and slot0 + n_slots <= self.n_slots):
+            raise ValueError("PlanPool.window: envs [%d, %d) / slots [%d, %d) outside the pool" %
+                             (env0, env0 + n_envs, slot0, slot0 + n_slots))
+        w = PlanPool.__new__(PlanPool)
+        w.device, w.P, w.d, w.n_slots, w.w_max = self.device, n_envs, self.d, n_slots, self.w_max
+        w.wp = self.wp[slot0 * self.w_max:(slot0 + n_slots) * self.w_max]
+        w.left = self.left[slot0 * self.w_max:(slot0 + n_slots) * self.w_max]
+        w.wp_off = self.wp_off[slot0:slot0 + n_slots + 1]
+        w.wp_len, w.radii = self.wp_len[slot0:slot0 + n_slots], self.radii[slot0:slot0 + n_slots]
+        w.plan_of, w.cur_idx = self.plan_of[env0:env0 + n_envs], self.cur_idx[env0:env0 + n_envs]
+        w.pool = torch.tensor([0, 0, n_slots], dtype=torch.int32)
+        w.theta, w.gamma, w.hpf, w.per_row = self.theta, self.gamma, self.hpf, self.per_row
+        w._next, w.published, w.active = 0, 0, None
+        w.slot0, w.triple = slot0, (0, 0, n_slots)
+        return w
 
     def publish(self, plans, now=None, min_age=None):
         """``plans``: list of (waypoints [W, d], distances_left [W], radii [d]) -- the per-episode quantities of
@@ -825,6 +851,7 @@ class PlanPool:
         self.wp_len.index_copy_(0, slots, dev(len_h))
         self.radii.index_copy_(0, slots, dev(radii_h))
         self.pool.copy_(torch.tensor([first, len(plans), self.n_slots], dtype=torch.int32))
+        self.triple = (first, len(plans), self.n_slots)
         self._next = (first + len(plans)) % self.n_slots
         self.published += len(plans)
 
@@ -1051,10 +1078,11 @@ class NavigatorBatch:
         """graph_key's part for what ``_simulate`` bakes in"""
         return _model_key(self.model)
 
-    def _score_and_step(self, env, chunk, ring, S, step_fn, *lead):
+    def _score_and_step(self, env, chunk, ring, S, step_fn, *lead, stats=None):
         """The tail of a fused step: score the simulated candidates ``S`` (``ssc_mpc_score``), then ONE launch ``step_fn``
         -- ``ssc_mpc_rollout_step``, or ``ssc_smartstart_rollout_step`` with its SmartStartStep in ``lead`` -- for action,
-        env step, log, statistics, waypoint advance and auto-reset."""
+        env step, log, statistics, waypoint advance and auto-reset.  ``stats``: the statistics block of the launch when it
+        is not ``env.stats`` (``ssc_smartstart_rollout_step_many``: one row per pair)."""
         fb, lib = self._fused_buffers(env.device), _ffi.lib()
         st = self.problems.as_struct(self.N, self.H)
         nav = _ffi.MpcNavState(self.problems.cur_idx.data_ptr(), self.start_idx.data_ptr(), self.actions_done.data_ptr(),
@@ -1070,7 +1098,8 @@ class NavigatorBatch:
                 float(self.noise_amount), self.seed, self.problem_id0, ctypes.byref(rs),
                 ctypes.byref(log_s) if log_s is not None else None,
                 ctypes.byref(ring_s) if ring_s is not None else None,
-                _ffi.ptr(env.stats), env._seed, env.env_id0, _ffi.ptr(fb["t"]), _ffi.ptr(fb["k"]), _ffi.ptr(fb["ticket"]),
+                _ffi.ptr(env.stats if stats is None else stats), env._seed, env.env_id0, _ffi.ptr(fb["t"]), _ffi.ptr(fb["k"]),
+                _ffi.ptr(fb["ticket"]),
                 _ffi.ptr(fb["plan"]), _ffi.stream()))
 
 

@@ -932,3 +932,81 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
             smart.end_of_generation()
             generations -= 1.0
     return summary, losses, replay
+
+
+def rl_train_vec_smartstart_population(env, smart_population, num_chunks, chunk_steps=64, replay_capacity=1 << 20,
+                                       train_iters=None, replay_last_steps=None, seed=0, ring_capacity=1 << 20, refresh_every=1,
+                                       graph=True, on_chunk=None, aggregate_every=0, aggregate_kwargs=None,
+                                       overlap_selection=False):
+    """The synchronous loop of :func:`rl_train_vec_smartstart` for ALL pairs of a :class:`smartstart.VecSmartStartPopulation`
+    -- the seeds and hyper-parameters of SmartStart_DDPG_Baselines_experimenter.py -- on the ONE ``env`` that holds every
+    pair's envs.  Per chunk: every pair's smart-start selection on its own ring (every ``refresh_every`` chunks; its
+    dynamics-model aggregation every ``aggregate_every``), ONE rollout of all pairs (one captured graph), every pair's
+    replay append from a strided column view of the one chunk (``TransitionChunk.from_columns`` over ``[..., env0:env0 + n]``,
+    row stride kept), ``ObsRmsGroup`` for the normalising pairs, ``DDPGPopulation.train_from``,
+    ``DDPGPopulation.param_noise_cycle`` for the noisy pairs, ONE drain of the episode ring split by env id into the pairs'
+    Summaries, and every pair's epsilon / eta decay once per episode per env of the pair.  Every pair's Summary, losses,
+    replay ring, agent parameters and final eta / epsilon are those of its own ``rl_train_vec_smartstart`` run on
+    ``VecEnv(n_p, env_id0 + env0_p)`` with the same arguments.  ``seed``: one replay seed for all pairs or one per pair.
+    ``on_chunk(c, out, smart_population)``.  Not in this form: ``overlap_selection=True`` (NotImplementedError).
+    Returns [(Summary, losses per chunk, replay)] per pair."""
+    if overlap_selection:
+        raise NotImplementedError("rl_train_vec_smartstart_population: overlap_selection=True is not part of the population loop; "
+                                  "run that pair through rl_train_vec_smartstart")
+    from .agents import DDPGPopulation
+    from .obs_rms import ObsRmsGroup
+    from .replay_buffer import DeviceReplayBuffer
+    from .vec_env import EpisodeRing, TransitionChunk
+    pop, pairs = smart_population, smart_population.pairs
+    agents, P = [pr.agent for pr in pairs], len(pairs)
+    for a in agents:
+        if getattr(a, "ret_rms", None) is not None:
+            raise NotImplementedError("rl_train_vec_smartstart_population: a base agent with normalize_returns / Pop-Art is not "
+                                      "supported (the selection reads the raw critic)")
+        if getattr(a, "param_noise", None) is not None and not hasattr(a, "param_noise_cycle"):
+            raise NotImplementedError("rl_train_vec_smartstart_population: a base agent with param_noise needs param_noise_cycle")
+    seeds = [int(seed)] * P if isinstance(seed, (int, np.integer)) else [int(s) for s in seed]
+    if len(seeds) != P:
+        raise ValueError("seed: one value or one per pair")
+    population = DDPGPopulation(agents)
+    summaries = [Summary("vec_smartstart_" + env.spec.id) for _ in pairs]
+    ring, chunk = EpisodeRing(ring_capacity, env.device), TransitionChunk(env.obs_dim, chunk_steps, env.n, env.device)
+    replays = [DeviceReplayBuffer(replay_capacity, env.obs_dim, 1, env.device, seed=s, track_episodes=True, n_envs=pr.n,
+                                  max_path_len=(env.spec.max_episode_steps or 1000) + 1) for pr, s in zip(pairs, seeds)]
+    sl = [slice(pr.env0, pr.env0 + pr.n) for pr in pairs]
+    views = [TransitionChunk.from_columns(chunk.obs[..., s], chunk.act[:, s], chunk.rew[:, s], chunk.obs2[..., s], chunk.done[:, s])
+             for s in sl]
+    normed = [p for p, a in enumerate(agents) if getattr(a, "obs_rms", None) is not None]
+    rms_group = ObsRmsGroup([agents[p].obs_rms for p in normed]) if normed else None
+    noisy = any(getattr(a, "param_noise", None) is not None for a in agents)
+    kept = chunk_steps if replay_last_steps is None else min(int(replay_last_steps), chunk_steps)
+    losses, generations = [[] for _ in pairs], [0.0] * P
+    for c in range(num_chunks):
+        for p, pr in enumerate(pairs):
+            if aggregate_every and c > 0 and c % aggregate_every == 0:
+                pr.train_dynamics_model(replays[p], **(aggregate_kwargs or {}))
+            if c % refresh_every == 0:
+                pr.refresh_plans(replays[p])
+        out = pop.rollout(chunk_steps, chunk, ring=ring, graph=graph)
+        for p, pr in enumerate(pairs):
+            views[p].step0, views[p].env_id0 = out.step0, out.env_id0 + pr.env0
+            replays[p].append_chunk(views[p], reward_scale=agents[p].reward_scale, last_steps=replay_last_steps)
+        if rms_group is not None and kept > 0:
+            rms_group.update_chunks([views[p] for p in normed], chunk_steps - kept, chunk_steps)
+        for p, l in enumerate(population.train_from(replays, train_iters, copy=True)):
+            if l is not None:
+                losses[p].append(l)
+        if noisy:                                 # the next chunk's acting copies, with the adapted stddevs
+            population.param_noise_cycle(replays)
+        if on_chunk is not None:
+            on_chunk(c, out, pop)
+        (ids, lens, rets), _d = ring.drain()
+        for p, pr in enumerate(pairs):
+            mine = (ids >= env.env_id0 + pr.env0) & (ids < env.env_id0 + pr.env0 + pr.n)
+            summaries[p].extend_records(lens[mine], rets[mine])
+            generations[p] += int(mine.sum()) / float(pr.n)
+            while generations[p] >= 1.0:
+                agents[p].decaying_ou_action_noise.reduce_epsilon()
+                pr.end_of_generation()
+                generations[p] -= 1.0
+    return [(summaries[p], losses[p], replays[p]) for p in range(P)]

@@ -197,7 +197,129 @@ class SmartStartContinuous(RLAgent):
         return env.render()
 
 
-class VecSmartStart:
+class SmartStartSelection:
+    """What ONE SmartStart pair does between rollout chunks, on its own agent, replay ring, dynamics model and plan pool:
+    smart-start selection and plan geometry, the acting descriptor, dynamics-model aggregation, the eta decay.  Shared by
+    :class:`VecSmartStart` (one pair, a pool of its own) and the pairs of :class:`VecSmartStartPopulation` (a window of the
+    population's pool each).  Needs ``env`` (step count and episode limit), ``agent``, ``model``, ``pool``, ``nav.seed`` and
+    the selection / geometry settings as attributes."""
+
+    # ------------------------------------------------------------------------- selection --
+    def plan_from_path(self, path):
+        """NND_MB_agent.start_new_episode_plan's geometry (NND_MB_agent.py:385-418) -> (waypoints, distances_left, radii)."""
+        from .numerical import (distances_left, elliptical_euclidean_distance_function_generator,
+                                get_start_waypoints_final_states_steps, path_deltas_stds_and_means_per_dim,
+                                path_shortcutter, radii_calc)
+        path = np.asarray(path, np.float64)
+        stds, means = path_deltas_stds_and_means_per_dim(path)
+        radii = radii_calc(means, stds, self.mean_per_stepsize, self.std_per_stepsize, self.stepsizes_in_waypoint_radii)
+        dist = elliptical_euclidean_distance_function_generator(radii)
+        if self.path_shortcutting:
+            path = path_shortcutter(path, dist, self.pool.theta)
+        wp = np.asarray(get_start_waypoints_final_states_steps(path, self.steps_per_waypoint))
+        return wp, distances_left(wp, dist), radii
+
+    def select_plans(self, replay):
+        """One smart-start selection on the device ring (get_smart_start_path, :223-305) -> up to ``n_plans`` plans
+        (waypoints, distances_left, radii) as host arrays, or None when the ring holds no complete episode start yet.
+        The device part runs on the CURRENT stream (rl_train_vec_smartstart(overlap_selection=True) makes that a side
+        stream) and the host reads its results; nothing here writes what a rollout in flight reads."""
+        if len(replay) == 0:
+            return None
+        idx = replay.get_possible_smart_start_indices(self.n_ss)                                  # :243-246
+        if idx is None:
+            return None
+        all_states = replay.get_all_states()                                                      # :258
+        if self.kde_max_states is not None and all_states.shape[0] > self.kde_max_states:
+            stride = -(-all_states.shape[0] // int(self.kde_max_states))
+            all_states = all_states[::stride].contiguous()
+        wh, norm = kde_scott_bandwidth(all_states)                                                # :260
+        volume = volume_of_n_dimensional_hyperellipsoid(self.last_radii) if self.last_radii is not None else 1   # :262-268
+        cand = replay.s2[replay.physical(idx)]                                                    # :272-273
+        values = self.agent.state_value_device(cand)                                              # :274
+        pdf = kde_evaluate(all_states, cand, wh, norm)                                            # :275
+        ucb, best = ucb_argmax(values, pdf, len(replay), volume, self.exploitation_param, self.exploration_param)
+        if self.n_plans == 1:
+            chosen = idx[best.long()]
+        else:
+            chosen = idx[torch.topk(ucb, min(self.n_plans, ucb.numel())).indices]
+        self.last_chosen = chosen
+        plans = []
+        for c in chosen.reshape(-1):
+            path = replay.get_episodic_path_to_buffer_index(c.reshape(1))
+            if path is None or path.shape[0] < 2:
+                continue
+            plans.append(self.plan_from_path(path.double().cpu().numpy()))
+        return plans
+
+    def publish_plans(self, plans):
+        """Put ``plans`` on offer (writes the pool on the current stream)."""
+        if plans:
+            self.pool.publish(plans, now=self.env.t, min_age=(self.env.spec.max_episode_steps or 1000))
+            self.last_radii = plans[0][2]
+            self.selections += 1
+
+    def refresh_plans(self, replay):
+        """``select_plans`` + ``publish_plans``.  Returns the chosen buffer indices (device tensor) or None when the ring
+        holds no complete episode start yet."""
+        self.last_chosen = None
+        plans = self.select_plans(replay)
+        if plans is None:
+            return None
+        self.publish_plans(plans)
+        return self.last_chosen
+
+    def acting_desc(self):
+        """The actor descriptor the per-step launch reads: over ``perturbed_actor_flat`` for a base agent with parameter
+        noise (pi, ddpg_editted.py:256-259) -- the same pointer slots for the life of the agent, so a captured step graph
+        stays valid while every perturbation changes the array's contents -- else the agent's own.  The selection
+        (``state_value_device``) always evaluates the PLAIN actor: get_q_value is not an acting path."""
+        a = self.agent
+        return a._perturbed_desc if getattr(a, "param_noise", None) is not None else a._desc
+
+    # ------------------------------------------------------------- dynamics-model aggregation --
+    def train_dynamics_model(self, replay, max_rows=65536, n_epoch=1, batchsize=512, lr=0.001, noise_to_signal=0.0):
+        """NND_MB_agent.train_dynamics_model (NND_MB_agent.py:437-480) for the vectorised loop: the navigator's model is
+        retrained on transitions the envs themselves produced -- an evenly strided sample of up to ``max_rows`` records of
+        the device replay ring as (s, a, s2 - s) rows (:442-449), optionally with ``add_noise`` (:451-453), z-scored with
+        the model's EXISTING statistics (:455-461) -- ``n_epoch`` passes of Adam steps on the device
+        (``DynamicsModel.train_steps``).  Nothing leaves HBM; the packed MFMA weight image is refreshed in place before
+        the next rollout, so the captured step graph keeps reading the right bytes.  Returns the mean loss of the last
+        epoch (a device -> host read) or None when the ring is still smaller than one batch."""
+        from .collect_samples import TrainingSet, add_noise_device
+        size = len(replay)
+        if size < batchsize:
+            return None
+        stride = max(1, -(-size // int(max_rows)))
+        sel = torch.arange(0, size, stride, device=replay.s.device)
+        s, a, s2 = replay.s[sel].contiguous(), replay.a[sel].contiguous(), replay.s2[sel].contiguous()
+        dz = (s2 - s).contiguous()
+        if noise_to_signal:
+            self._agg_calls = getattr(self, "_agg_calls", 0) + 1
+            add_noise_device(s, noise_to_signal, self.nav.seed, 2 * self._agg_calls)
+            add_noise_device(dz, noise_to_signal, self.nav.seed, 2 * self._agg_calls + 1)
+        nm, m = self.model.norm, self.model
+        norm = {k: [getattr(nm, k)[i] for i in range(n)] for k, n in (("mean_x", m.state_dim), ("std_x", m.state_dim),
+                                                                       ("mean_y", m.act_dim), ("std_y", m.act_dim),
+                                                                       ("mean_z", m.state_dim), ("std_z", m.state_dim))}
+        X, Z = TrainingSet(s, a, dz, None, None).normalised(norm)
+        rows = X.shape[0]
+        n_batches = rows // batchsize
+        gen = torch.Generator(device=X.device)
+        gen.manual_seed(int(self.nav.seed) + 7919 * getattr(self, "_trainings", 0))
+        losses = None
+        for _ in range(int(n_epoch)):
+            perm = torch.randperm(rows, generator=gen, device=X.device)[: n_batches * batchsize]
+            losses = self.model.train_steps(X, Z, perm.view(n_batches, batchsize).to(torch.int32), lr=lr)
+        self._trainings = getattr(self, "_trainings", 0) + 1
+        return None if losses is None else float(losses.mean().item())
+
+    def end_of_generation(self):
+        """SmartStartContinuous.end_episode (:372-376) once per episode PER ENV: eta decays."""
+        self.eta *= self.eta_decay_factor
+
+
+class VecSmartStart(SmartStartSelection):
     """``SmartStartContinuous`` for the N envs of a :class:`VecEnv` at once (smartexplorationcontinuous.py:307-376,
     vectorised): every env is either navigating to a smart-start state (per-env mode 1: the NND_MB MPC picks its
     action) or handed over to the base DDPG agent (mode 0: actor + OU noise); an env that finishes an episode starts
@@ -273,71 +395,6 @@ class VecSmartStart:
         self._graphs = StepGraphs(keep=4)
         self.selections = 0
 
-    # ------------------------------------------------------------------------- selection --
-    def plan_from_path(self, path):
-        """NND_MB_agent.start_new_episode_plan's geometry (NND_MB_agent.py:385-418) -> (waypoints, distances_left, radii)."""
-        from .numerical import (distances_left, elliptical_euclidean_distance_function_generator,
-                                get_start_waypoints_final_states_steps, path_deltas_stds_and_means_per_dim,
-                                path_shortcutter, radii_calc)
-        path = np.asarray(path, np.float64)
-        stds, means = path_deltas_stds_and_means_per_dim(path)
-        radii = radii_calc(means, stds, self.mean_per_stepsize, self.std_per_stepsize, self.stepsizes_in_waypoint_radii)
-        dist = elliptical_euclidean_distance_function_generator(radii)
-        if self.path_shortcutting:
-            path = path_shortcutter(path, dist, self.pool.theta)
-        wp = np.asarray(get_start_waypoints_final_states_steps(path, self.steps_per_waypoint))
-        return wp, distances_left(wp, dist), radii
-
-    def select_plans(self, replay):
-        """One smart-start selection on the device ring (get_smart_start_path, :223-305) -> up to ``n_plans`` plans
-        (waypoints, distances_left, radii) as host arrays, or None when the ring holds no complete episode start yet.
-        The device part runs on the CURRENT stream (rl_train_vec_smartstart(overlap_selection=True) makes that a side
-        stream) and the host reads its results; nothing here writes what a rollout in flight reads."""
-        if len(replay) == 0:
-            return None
-        idx = replay.get_possible_smart_start_indices(self.n_ss)                                  # :243-246
-        if idx is None:
-            return None
-        all_states = replay.get_all_states()                                                      # :258
-        if self.kde_max_states is not None and all_states.shape[0] > self.kde_max_states:
-            stride = -(-all_states.shape[0] // int(self.kde_max_states))
-            all_states = all_states[::stride].contiguous()
-        wh, norm = kde_scott_bandwidth(all_states)                                                # :260
-        volume = volume_of_n_dimensional_hyperellipsoid(self.last_radii) if self.last_radii is not None else 1   # :262-268
-        cand = replay.s2[replay.physical(idx)]                                                    # :272-273
-        values = self.agent.state_value_device(cand)                                              # :274
-        pdf = kde_evaluate(all_states, cand, wh, norm)                                            # :275
-        ucb, best = ucb_argmax(values, pdf, len(replay), volume, self.exploitation_param, self.exploration_param)
-        if self.n_plans == 1:
-            chosen = idx[best.long()]
-        else:
-            chosen = idx[torch.topk(ucb, min(self.n_plans, ucb.numel())).indices]
-        self.last_chosen = chosen
-        plans = []
-        for c in chosen.reshape(-1):
-            path = replay.get_episodic_path_to_buffer_index(c.reshape(1))
-            if path is None or path.shape[0] < 2:
-                continue
-            plans.append(self.plan_from_path(path.double().cpu().numpy()))
-        return plans
-
-    def publish_plans(self, plans):
-        """Put ``plans`` on offer (writes the pool on the current stream)."""
-        if plans:
-            self.pool.publish(plans, now=self.env.t, min_age=(self.env.spec.max_episode_steps or 1000))
-            self.last_radii = plans[0][2]
-            self.selections += 1
-
-    def refresh_plans(self, replay):
-        """``select_plans`` + ``publish_plans``.  Returns the chosen buffer indices (device tensor) or None when the ring
-        holds no complete episode start yet."""
-        self.last_chosen = None
-        plans = self.select_plans(replay)
-        if plans is None:
-            return None
-        self.publish_plans(plans)
-        return self.last_chosen
-
     # ------------------------------------------------------------------------------ steps --
     def _step_struct(self, chunk_k):
         e, a = self.env, self.agent
@@ -354,14 +411,6 @@ class VecSmartStart:
                 self.mode_log = torch.zeros((chunk_k, e.n), dtype=torch.uint8, device=e.device)
             ss.d_mode_log, ss.mode_log_stride = self.mode_log.data_ptr(), e.n
         return ss
-
-    def acting_desc(self):
-        """The actor descriptor the per-step launch reads: over ``perturbed_actor_flat`` for a base agent with parameter
-        noise (pi, ddpg_editted.py:256-259) -- the same pointer slots for the life of the agent, so a captured step graph
-        stays valid while every perturbation changes the array's contents -- else the agent's own.  The selection
-        (``state_value_device``) always evaluates the PLAIN actor: get_q_value is not an acting path."""
-        a = self.agent
-        return a._perturbed_desc if getattr(a, "param_noise", None) is not None else a._desc
 
     def graph_key(self, K, chunk, ring):
         """The navigator's key (``NavigatorBatch.graph_key``) plus everything this class's own launches bake into a captured
@@ -426,43 +475,262 @@ class VecSmartStart:
         env.t += K
         return out
 
-    # ------------------------------------------------------------- dynamics-model aggregation --
-    def train_dynamics_model(self, replay, max_rows=65536, n_epoch=1, batchsize=512, lr=0.001, noise_to_signal=0.0):
-        """NND_MB_agent.train_dynamics_model (NND_MB_agent.py:437-480) for the vectorised loop: the navigator's model is
-        retrained on transitions the envs themselves produced -- an evenly strided sample of up to ``max_rows`` records of
-        the device replay ring as (s, a, s2 - s) rows (:442-449), optionally with ``add_noise`` (:451-453), z-scored with
-        the model's EXISTING statistics (:455-461) -- ``n_epoch`` passes of Adam steps on the device
-        (``DynamicsModel.train_steps``).  Nothing leaves HBM; the packed MFMA weight image is refreshed in place before
-        the next rollout, so the captured step graph keeps reading the right bytes.  Returns the mean loss of the last
-        epoch (a device -> host read) or None when the ring is still smaller than one batch."""
-        from .collect_samples import TrainingSet, add_noise_device
-        size = len(replay)
-        if size < batchsize:
-            return None
-        stride = max(1, -(-size // int(max_rows)))
-        sel = torch.arange(0, size, stride, device=replay.s.device)
-        s, a, s2 = replay.s[sel].contiguous(), replay.a[sel].contiguous(), replay.s2[sel].contiguous()
-        dz = (s2 - s).contiguous()
-        if noise_to_signal:
-            self._agg_calls = getattr(self, "_agg_calls", 0) + 1
-            add_noise_device(s, noise_to_signal, self.nav.seed, 2 * self._agg_calls)
-            add_noise_device(dz, noise_to_signal, self.nav.seed, 2 * self._agg_calls + 1)
-        nm, m = self.model.norm, self.model
-        norm = {k: [getattr(nm, k)[i] for i in range(n)] for k, n in (("mean_x", m.state_dim), ("std_x", m.state_dim),
-                                                                       ("mean_y", m.act_dim), ("std_y", m.act_dim),
-                                                                       ("mean_z", m.state_dim), ("std_z", m.state_dim))}
-        X, Z = TrainingSet(s, a, dz, None, None).normalised(norm)
-        rows = X.shape[0]
-        n_batches = rows // batchsize
-        gen = torch.Generator(device=X.device)
-        gen.manual_seed(int(self.nav.seed) + 7919 * getattr(self, "_trainings", 0))
-        losses = None
-        for _ in range(int(n_epoch)):
-            perm = torch.randperm(rows, generator=gen, device=X.device)[: n_batches * batchsize]
-            losses = self.model.train_steps(X, Z, perm.view(n_batches, batchsize).to(torch.int32), lr=lr)
-        self._trainings = getattr(self, "_trainings", 0) + 1
-        return None if losses is None else float(losses.mean().item())
 
-    def end_of_generation(self):
-        """SmartStartContinuous.end_episode (:372-376) once per episode PER ENV: eta decays."""
-        self.eta *= self.eta_decay_factor
+# A kernel class of the per-step actor launch goes through ONE ssc_actor_forward_many when it has at least this many pairs;
+# smaller groups act through ssc_actor_forward[_rms] on their slices (the same bits).  Measured on an MI355X
+# (profiles/smartstart_population/actor.json; P = 1, 2, 4, 16, 64 actors x 16 and x 1024 rows; a case is won when the slowest
+# many-call window beats the fastest per-pair window): 2 is the smallest group that wins at every measured shape of the
+# fp32 64-32 class (x2.2 at P = 2), the bf16 64-32 class (x1.7-1.8), the bf16 200-100 class (x2.05) and the generic class at
+# 1024 rows (x2.0); a lone bf16 64-32 actor LOSES 5-10 % in the many-call (4.8 against 4.3-4.6 us) and belongs in its own call.
+SMARTSTART_POPULATION_ACTOR_MIN_GROUP = 2
+# ... except for generic-class pairs of <= 32 envs each: their own call is actor_row_kernel (4.3 us for 16 rows, a block per
+# row) where the many-call runs the one-row-per-lane generic body (34 us whatever the row count), so P = 2 and 4 lose
+# (x0.24, x0.49) and 16 is the smallest measured group that wins (x1.9; 64: x7.7)
+SMARTSTART_POPULATION_ACTOR_MIN_GROUP_FEW_ROWS = 16
+
+
+def _per_pair(value, n, what):
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != n:
+            raise ValueError("%s: one value or one per pair (%d), got %d" % (what, n, len(value)))
+        return list(value)
+    return [value] * n
+
+
+class PopulationPair(SmartStartSelection):
+    """One pair of a :class:`VecSmartStartPopulation`: its agent, dynamics model, envs [env0, env0 + n) of the population's
+    VecEnv and its window of the population's plan pool.  Everything it does is :class:`SmartStartSelection`'s.  (Its row of
+    the device table is an ``_ffi.SmartStartPair``, the mirror of ``ssc_smartstart_pair``.)"""
+
+    def __init__(self, population, index, agent, model, env0, n, pool, eta, eta_decay_factor, n_ss, n_plans, exploitation_param,
+                 exploration_param, path_shortcutting, steps_per_waypoint, mean_per_stepsize, std_per_stepsize,
+                 stepsizes_in_waypoint_radii, kde_max_states):
+        self.population, self.index = population, index
+        self.env, self.nav = population.env, population.nav
+        self.agent, self.model, self.env0, self.n, self.pool = agent, model, int(env0), int(n), pool
+        self.eta, self.eta_decay_factor = float(eta), float(eta_decay_factor)
+        self.n_ss, self.n_plans = int(n_ss), int(n_plans)
+        self.exploitation_param, self.exploration_param = exploitation_param, exploration_param
+        self.path_shortcutting, self.steps_per_waypoint = path_shortcutting, steps_per_waypoint
+        self.mean_per_stepsize, self.std_per_stepsize = mean_per_stepsize, std_per_stepsize
+        self.stepsizes_in_waypoint_radii = stepsizes_in_waypoint_radii
+        self.kde_max_states = kde_max_states
+        self.last_radii = None
+        self.selections = 0
+
+
+class VecSmartStartPopulation:
+    """P SmartStart pairs -- the seeds and hyper-parameters of a sweep
+    (examples/continuous/SmartStart_DDPG_Baselines_experimenter.py) -- stepping from ONE captured graph.  ONE
+    :class:`VecEnv` holds the envs of all pairs, pair p owning the next ``envs_per_pair[p]`` of them; one set of plan arrays
+    holds every pair's slots (``navigator.PlanPool.window``); every RNG stream is keyed by the global env id.  Env e of pair
+    p gets, bit for bit, what a :class:`VecSmartStart` of its own on ``VecEnv(n_p, env_id0 = env.env_id0 + env0_p)`` with the
+    same seed gives it.  One step = four launches: the actors (``ssc_actor_forward_many`` per kernel class of at least
+    ``SMARTSTART_POPULATION_ACTOR_MIN_GROUP`` pairs, else the pair's own call on its slice), the forward simulation of all
+    dynamics models (``navigator.NavigatorPopulation``), the scorer, and ``ssc_smartstart_rollout_step_many``.  The mask
+    ``mode`` lets simulation and scoring skip what is not navigating; there is NO compact live list (the many-simulation
+    refuses it).  ``eta``, ``eta_decay_factor``, ``n_ss``, ``n_plans`` and the exploitation / exploration parameters take one
+    value or one per pair; the navigator settings are shared.  Selection, plan geometry and dynamics-model aggregation of
+    pair p: ``pairs[p]`` (:class:`SmartStartSelection`)."""
+
+    def __init__(self, env, agents, dyn_models, envs_per_pair, eta=0.5, eta_decay_factor=1.0, n_ss=1000, exploitation_param=1.,
+                 exploration_param=2., n_plans=1, n_slots=None, w_max=None, num_control_samples=64, horizon=4,
+                 noise_amount=0.005, steps_before_giving_up_on_waypoint=5, final_steps=10, theta=1.0, gamma=0.75,
+                 horizontal_penalty_factor=0.5, path_shortcutting=True, mean_per_stepsize=1, std_per_stepsize=1,
+                 stepsizes_in_waypoint_radii=1, steps_per_waypoint=1, chunk_steps=64, seed=1234, log_modes=False,
+                 kde_max_states=500000):
+        from . import navigator as nav
+        from .population import DeviceItems
+        agents, dyn_models = list(agents), list(dyn_models)
+        P = len(agents)
+        if P == 0 or len(dyn_models) != P:
+            raise ValueError("VecSmartStartPopulation: one dynamics model per agent, at least one pair")
+        for a in agents:
+            if getattr(a, "ret_rms", None) is not None:
+                raise NotImplementedError("VecSmartStartPopulation: a base agent with normalize_returns / Pop-Art is not "
+                                          "supported (the selection reads the raw critic)")
+        counts = [int(c) for c in _per_pair(envs_per_pair, P, "envs_per_pair")]
+        if min(counts) < 1 or sum(counts) != env.n:
+            raise ValueError("VecSmartStartPopulation: envs_per_pair %s for %d envs" % (counts, env.n))
+        self.env, self.agents, self.models, self.envs_per_pair = env, agents, dyn_models, counts
+        dev = env.device
+        max_steps = env.spec.max_episode_steps or 1000
+        w_max = int(w_max) if w_max is not None else max_steps + 1
+        plans = [int(x) for x in _per_pair(n_plans, P, "n_plans")]
+        if n_slots is None:        # a published plan must outlive every episode that started on it (VecSmartStart's rule)
+            slots = [k * (-(-max_steps // max(int(chunk_steps), 1)) + 2) for k in plans]
+        else:
+            slots = [int(x) for x in _per_pair(n_slots, P, "n_slots")]
+        self.pool = nav.PlanPool(env.n, sum(slots), w_max, env.obs_dim, dev, theta=theta, gamma=gamma,
+                                 horizontal_penalty_factor=horizontal_penalty_factor)
+        self.nav = nav.NavigatorPopulation(dyn_models, self.pool, counts, num_control_samples=num_control_samples,
+                                           horizon=horizon, action_low=env.action_space.low, action_high=env.action_space.high,
+                                           noise_amount=noise_amount,
+                                           steps_before_giving_up_on_waypoint=steps_before_giving_up_on_waypoint,
+                                           final_steps=final_steps, seed=seed, problem_id0=env.env_id0)
+        self.nav.start_idx.zero_()
+        self.mode = torch.zeros(env.n, dtype=torch.uint8, device=dev)
+        self.pool.active = self.mode     # simulation skips dead waves, the one-launch scorer dead problems; no live list
+        self.actor_out = torch.zeros((env.n, 1), dtype=torch.float32, device=dev)
+        self.stats = torch.zeros((P, 4), dtype=torch.float64, device=dev)
+        per = lambda v, what: _per_pair(v, P, what)
+        etas, decays, nss = per(eta, "eta"), per(eta_decay_factor, "eta_decay_factor"), per(n_ss, "n_ss")
+        xi, xr = per(exploitation_param, "exploitation_param"), per(exploration_param, "exploration_param")
+        self.pairs, env0, slot0 = [], 0, 0
+        for p in range(P):
+            self.pool.plan_of[env0:env0 + counts[p]] = slot0
+            self.pairs.append(PopulationPair(
+                self, p, agents[p], dyn_models[p], env0, counts[p], self.pool.window(env0, counts[p], slot0, slots[p]),
+                eta=float(etas[p]), eta_decay_factor=float(decays[p]), n_ss=int(nss[p]), n_plans=plans[p],
+                exploitation_param=xi[p], exploration_param=xr[p], path_shortcutting=path_shortcutting,
+                steps_per_waypoint=steps_per_waypoint, mean_per_stepsize=mean_per_stepsize, std_per_stepsize=std_per_stepsize,
+                stepsizes_in_waypoint_radii=stepsizes_in_waypoint_radii, kde_max_states=kde_max_states))
+            env0, slot0 = env0 + counts[p], slot0 + slots[p]
+        self.log_modes = bool(log_modes)
+        self.mode_log = None
+        self.pair_table = DeviceItems(_ffi.SmartStartPair, P, dev)
+        self._actor_items, self._actor_sent, self._actor_plan = {}, {}, []
+        self._graphs = StepGraphs(keep=4)
+
+    # ------------------------------------------------------------------------------ tables --
+    def sync_pair_table(self):
+        """The device table ``ssc_smartstart_rollout_step_many`` reads at every launch: each pair's env range, plan window
+        and triple, eta, the agent's current OU epsilon and OU process.  Rewritten and uploaded in front of a chunk, outside
+        the capture: a replayed graph follows the host's decay schedules and pool refreshes through it."""
+        t = self.pair_table
+        t.wait()
+        for it, pr in zip(t.items, self.pairs):
+            a = pr.agent
+            it.env0, it.n_envs, it.slot0 = pr.env0, pr.n, pr.pool.slot0
+            it.pool_first, it.pool_count, it.pool_slots = pr.pool.triple
+            it.eta, it.ou_epsilon = pr.eta, float(max(a.decaying_ou_action_noise.epsilon, 0.0))
+            it.ou.mu, it.ou.sigma, it.ou.theta = float(a.ou["mu"]), float(a.ou["sigma"]), float(a.ou["theta"])
+            it.ou.dt = float(a.decaying_ou_action_noise.dt)
+        t.upload()
+        return t
+
+    def sync_actor_items(self):
+        """How the step's actor launch serves every pair -> [("many", class, DeviceItems) | ("alone", pair index)]: one
+        item table per kernel class with at least ``SMARTSTART_POPULATION_ACTOR_MIN_GROUP`` pairs (generic-class pairs of <= 32
+        envs each: ``SMARTSTART_POPULATION_ACTOR_MIN_GROUP_FEW_ROWS``), re-uploaded only when its
+        bytes change and never inside a capture."""
+        from .population import DeviceItems
+        lib, groups = _ffi.lib(), {}
+        for p, pr in enumerate(self.pairs):
+            rms = getattr(pr.agent, "obs_rms", None)
+            c = lib.ssc_actor_many_class(ctypes.byref(pr.acting_desc()), int(rms is not None))
+            groups.setdefault((c, pr.acting_desc().obs_dim, pr.acting_desc().act_dim), []).append(p)
+        plan = []
+        for key, members in sorted(groups.items()):
+            few_rows = key[0] // 2 == 8 and all(self.pairs[p].n <= 32 for p in members)      # generic class, row-kernel sized pairs
+            need = SMARTSTART_POPULATION_ACTOR_MIN_GROUP_FEW_ROWS if few_rows else SMARTSTART_POPULATION_ACTOR_MIN_GROUP
+            if key[0] < 0 or len(members) < need:
+                plan += [("alone", p) for p in members]
+                continue
+            fresh = (_ffi.ActorManyItem * len(members))()
+            for it, p in zip(fresh, members):
+                pr = self.pairs[p]
+                rms = getattr(pr.agent, "obs_rms", None)
+                it.actor, it.d_rms = pr.acting_desc(), (None if rms is None else rms.block.data_ptr())
+                it.row0, it.rows = pr.env0, pr.n
+            di = self._actor_items.get(key)
+            if di is None or di.n != len(members):
+                di = self._actor_items[key] = DeviceItems(_ffi.ActorManyItem, len(members), self.env.device)
+                self._actor_sent.pop(key, None)
+            image = bytes(fresh)
+            if self._actor_sent.get(key) != image:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("VecSmartStartPopulation: an actor item table changed inside a graph capture; "
+                                       "call sync_actor_items() in front of it")
+                di.wait()
+                ctypes.memmove(di.h_ptr, ctypes.addressof(fresh), len(image))
+                di.upload()
+                self._actor_sent[key] = image
+            plan.append(("many", key, di))
+        for key in [k for k in self._actor_items if k not in groups]:
+            del self._actor_items[key]
+            self._actor_sent.pop(key, None)
+        self._actor_plan = plan
+        return plan
+
+    # ------------------------------------------------------------------------------ steps --
+    def _step_struct(self, chunk_k):
+        e = self.env
+        ss = _ffi.SmartStartStep()
+        ss.mode, ss.plan_of, ss.d_actor_out = self.mode.data_ptr(), self.pool.plan_of.data_ptr(), self.actor_out.data_ptr()
+        ss.act_low, ss.act_high = float(e.action_space.low[0]), float(e.action_space.high[0])
+        if self.log_modes:
+            if self.mode_log is None or self.mode_log.shape != (chunk_k, e.n):
+                self.mode_log = torch.zeros((chunk_k, e.n), dtype=torch.uint8, device=e.device)
+            ss.d_mode_log, ss.mode_log_stride = self.mode_log.data_ptr(), e.n
+        return ss
+
+    def graph_key(self, K, chunk, ring):
+        """What ``VecSmartStart.graph_key`` covers, per pair, plus the item and pair tables' addresses: the navigator's key,
+        every pair's acting descriptor by value and statistics block, the split, the shared tensors, and how the actor
+        launch is grouped (class, members, table addresses).  eta, epsilon, the OU process and the pool triples are NOT
+        here: they reach a replay through the pair table."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        e, p = self.env, self.pool
+        pairs = tuple((bytes(pr.acting_desc()), ptr(getattr(getattr(pr.agent, "obs_rms", None), "block", None)), pr.env0, pr.n,
+                       pr.pool.slot0, pr.pool.n_slots) for pr in self.pairs)
+        actors = tuple((w[0], w[1]) if w[0] == "alone" else (w[0], w[1], w[2].h_ptr, w[2].d_ptr, w[2].n) for w in self._actor_plan)
+        return (K, self.nav.graph_key(e, chunk, ring), pairs, actors, (self.pair_table.h_ptr, self.pair_table.d_ptr),
+                tuple(ptr(x) for x in (self.mode, p.plan_of, p.wp_len, p.active, self.actor_out, self.stats, self.mode_log)),
+                self.log_modes, float(e.action_space.low[0]), float(e.action_space.high[0]))
+
+    def fused_step(self, chunk, ring):
+        """Enqueue ONE step for every env of every pair (four launches when every actor class is grouped)."""
+        from . import navigator as nav
+        env, b, lib = self.env, self.nav, _ffi.lib()
+        fb = b._fused_buffers(env.device)
+        d = env.obs_dim
+        with torch.cuda.device(env.device):
+            for way in self._actor_plan:
+                if way[0] == "many":
+                    di = way[2]
+                    _ffi.check(lib.ssc_actor_forward_many(di.h_ptr, di.d_ptr, di.n, env.n, _ffi.ptr(fb["plan"]),
+                                                          _ffi.ptr(self.actor_out), _ffi.stream()))
+                    continue
+                pr = self.pairs[way[1]]
+                rms, desc = getattr(pr.agent, "obs_rms", None), pr.acting_desc()
+                obs, out = fb["plan"].data_ptr() + 4 * d * pr.env0, self.actor_out.data_ptr() + 4 * pr.env0
+                if rms is None:
+                    _ffi.check(lib.ssc_actor_forward(ctypes.byref(desc), pr.n, obs, out, _ffi.stream()))
+                else:
+                    _ffi.check(lib.ssc_actor_forward_rms(ctypes.byref(desc), pr.n, obs, out, _ffi.stream(), _ffi.ptr(rms.block)))
+        sp = nav.mpc_sampling(b.N, b.low, b.high, b.seed, b.problem_id0, 0, t_base=fb["t"], active=self.mode)
+        S = b._simulate(fb["plan"], sp, A_out=fb["A"])
+        ss = self._step_struct(chunk.K if chunk is not None else 1)
+        t = self.pair_table
+        b._score_and_step(env, chunk, ring, S, lib.ssc_smartstart_rollout_step_many, ctypes.byref(ss), t.h_ptr, t.d_ptr, t.n,
+                          stats=self.stats)
+
+    def _state_tensors(self):
+        e, b = self.env, self.nav
+        fb = b._fused_buffers(e.device)
+        return [e.s0, e.s1, e.steps, e.ep_ret, e.ou_x, self.stats, self.pool.cur_idx, self.pool.plan_of, b.actions_done,
+                b.at_goal, self.mode, fb["plan"], fb["t"], fb["k"]]
+
+    def rollout(self, K, out, ring=None, graph=True):
+        """K steps of every env of every pair into the TransitionChunk ``out`` (one graph replay per step when ``graph``).
+        The pair table (eta, epsilon, OU process, pool triple of every pair) and the actor item tables are refreshed here,
+        outside the capture."""
+        env, b = self.env, self.nav
+        if env._needs_reset:
+            env.reset()
+        if (out.K, out.N, out.obs_dim) != (K, env.n, env.obs_dim):
+            raise ValueError("out chunk has the wrong shape")
+        out.step0, out.env_id0 = env.t, env.env_id0
+        b.begin_chunk(env)
+        self.sync_pair_table()
+        self.sync_actor_items()
+        if not graph:
+            for _ in range(K):
+                self.fused_step(out, ring)
+            env.t += K
+            return out
+        self._graphs.replay(K, env.device, lambda: self.graph_key(K, out, ring), lambda: self.fused_step(out, ring),
+                            self._state_tensors(), ring)
+        env.t += K
+        return out
