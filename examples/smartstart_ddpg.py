@@ -49,6 +49,9 @@ def main():
     ap.add_argument("--population", type=int, default=0, metavar="P",
                     help="vec mode: P SmartStart pairs of --envs envs each in ONE VecEnv, stepping from one captured graph "
                          "(VecSmartStartPopulation; sequential selection)")
+    ap.add_argument("--grouped-selection", action="store_true",
+                    help="with --population: select the smart starts of all pairs in one launch per stage with one host wait "
+                         "(default: the per-pair selection calls)")
     ap.add_argument("--eta", default="0.5", help="smart-start probability; with --population one value or a comma list, one per pair")
     ap.add_argument("--actor-hidden", default="64-32", help="actor h1-h2; with --population one value or a comma list, one per pair")
     ap.add_argument("--replay-capacity", type=int, default=None, help="records in the device ring (default: two full episodes per env)")
@@ -172,7 +175,7 @@ def vec_population(args, dyn_model):
                                         kde_max_states=args.kde_max_states or None)
     cap = args.replay_capacity or 2 * args.envs * args.max_steps
     kw = dict(chunk_steps=args.chunk_steps, train_iters=args.train_iters, replay_capacity=cap, refresh_every=args.refresh_every,
-              seed=[args.seed + p for p in range(P)])
+              seed=[args.seed + p for p in range(P)], grouped_selection=args.grouped_selection)
     ssc.rl_train_vec_smartstart_population(env, smart, 2, **kw)   # warm-up: allocations, graph capture
     torch.cuda.synchronize()
     t0 = time.perf_counter()

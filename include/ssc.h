@@ -776,6 +776,102 @@ int ssc_smartstart_rollout_step_many(const ssc_env_params *p, const ssc_mpc_prob
                                      uint64_t *d_t, int32_t *d_k, int32_t *d_ticket, float *d_plan_state, ssc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The smart-start SELECTION of a population of pairs, one launch per stage
+ *
+ * get_smart_start_path (smartexplorationcontinuous.py:223-305) for every pair at once: candidates, Scott bandwidth,
+ * V = Q(s, pi(s)), Gaussian KDE, UCB1 top-k, episodic paths.  ONE item table serves all six calls; grid row y is item y.
+ * The actor forward between the candidates and the critic goes through ssc_actor_forward_many on the pooled candidate
+ * matrix (d_cand of item y = pool + row0 * obs_dim).
+ * ------------------------------------------------------------------------------------- */
+
+/* One pair's selection.  Declared tag first like the other *_many items; tests/test_select_many_host.py holds the struct's
+ * size and offsets to the ctypes mirror.  The host keeps count, stride, n_data and scott current; nothing a launch needs
+ * depends on a device result.  size = min(count, ring.capacity).  An item with n_ss == 0 or count == 0 is EMPTY: it is
+ * skipped and nothing else of it is read. */
+struct ssc_select_many_item {
+    ssc_replay_ring ring;       /* with the episode index (ep_steps) */
+    int64_t  count;             /* records appended so far */
+    int64_t  n;                 /* envs per step of the appended chunks */
+    int32_t  n_ss;              /* candidate slots, <= 4096 */
+    int32_t  n_plans;           /* 1..64, <= n_ss not required */
+    uint64_t seed, counter;     /* the Philox key of ssc_replay_smart_start_indices */
+    int64_t  stride;            /* KDE data set: logical rows j * stride, j < n_data, of "ring states oldest first, then */
+    int64_t  n_data;            /*   the newest record's s2" (size + 1 rows); n_data = ceil((size + 1) / stride) */
+    double   scott;             /* (n_data ** (-1.0 / (d + 4))) ** 2, computed by the host */
+    ssc_actor_desc  actor;      /* the plain actor; read by the caller's ssc_actor_forward_many table, checked here for obs_dim */
+    ssc_critic_desc critic;
+    const double *d_rms;        /* the agent's RunningMeanStd block or NULL */
+    float    alpha, beta;       /* exploitation / exploration parameter */
+    double   volume;
+    int32_t  max_len;           /* paths keep at most the newest max_len steps */
+    int32_t  pad;
+    int64_t  row0;              /* the item's rows [row0, row0 + n_ss) of the call's action matrix (ssc_critic_forward_many) */
+    int32_t *d_idx;             /* [n_ss] buffer indices, unfilled slots -1 */
+    int32_t *d_n_cand;          /* [1] */
+    float   *d_cand;            /* [n_ss][obs_dim]; unfilled slots zero */
+    float   *d_wh;              /* [d * d] whitening, row-major */
+    double  *d_norm;            /* [1] */
+    int32_t *d_status;          /* [1] 0: bandwidth found; 1: n_data < 2 or a non-positive / non-finite pivot */
+    float   *d_value;           /* [n_ss] */
+    float   *d_pdf;             /* [n_ss] */
+    float   *d_ucb;             /* [n_ss]; unfilled slots NaN */
+    int32_t *d_chosen;          /* [n_plans] buffer indices, unused places -1 */
+    float   *d_path;            /* [n_plans][max_len + 1][obs_dim] */
+    int32_t *d_len;             /* [n_plans] rows of each path, 0: none */
+    void    *d_workspace;       /* ssc_replay_smart_start_workspace_bytes(n_ss) bytes, this item's own */
+    size_t   workspace_bytes;
+};
+typedef struct ssc_select_many_item ssc_select_many_item;
+
+/* Conventions of all six calls (those of the other *_many calls): the host array is validated completely before any HIP
+ * call, the caller's device copy of the same bytes must be complete on `stream`, the library copies and allocates nothing,
+ * item indices appear in ssc_last_error().  n_items 1..65535 (more: SSC_EUNSUPPORTED); NULL tables, n_items < 1: SSC_EINVAL.
+ * Every call checks of a non-empty item (SSC_EINVAL): ring.capacity > 0, ring.obs_dim in 1..SSC_MAX_STATE, count >= 0,
+ * n >= 1, size <= 2^31 - 1, n_ss in 0..4096, and the pointers the call itself reads or writes non-NULL.  Every item
+ * empty: SSC_OK without a launch.  Outputs of pair y in a call of P items equal, bit for bit, the call with that item
+ * alone. */
+
+/* ssc_replay_smart_start_indices per item (one workgroup each): d_idx and *d_n_cand bit for bit what the single call
+ * delivers for that ring and key.  Behind its last barrier the workgroup gathers d_cand[slot] = ring.s2[physical(idx[slot])]
+ * (zeros for idx = -1).  Also checks: ep_steps / s2 / d_idx / d_n_cand / d_cand non-NULL, workspace large enough. */
+int ssc_replay_smart_start_indices_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items,
+                                        ssc_stream_t stream);
+
+/* kde_scott_bandwidth per item on the device, in fp64: the two-pass covariance (ddof = 1) of the data set (read from the
+ * ring in place), cov *= scott, wh = chol(inv(cov))^T rounded to float, norm = 1 / (n_data * sqrt(det(2 pi cov))).  One
+ * workgroup per item; partial sums merged in a fixed order (wave shuffles, then waves in order): the same bits run to run.
+ * *d_status = 1 and nothing else is promised when n_data < 2 or a Cholesky pivot is non-positive or non-finite.
+ * Also checks: stride >= 1, n_data == ceil((size + 1) / stride), scott > 0 and finite, ring.s / s2 / d_wh / d_norm /
+ * d_status non-NULL. */
+int ssc_kde_scott_bandwidth_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items,
+                                 ssc_stream_t stream);
+
+/* ssc_critic_forward[_rms] per item: q of rows d_cand [n_ss][obs_dim] with the actions d_act + row0 * act_dim (d_act is
+ * [m][act_dim]) into d_value; blocks anchored at the item's first row; every row bit for bit the single call's.  Items with
+ * and without d_rms share the launch (each block runs its item's instantiation of the one body).  The single call's
+ * per-descriptor checks and codes apply; critic.obs_dim must equal ring.obs_dim; [row0, row0 + n_ss) inside [0, m). */
+int ssc_critic_forward_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items, int64_t m,
+                            const float *d_act, ssc_stream_t stream);
+
+/* ssc_kde_evaluate per item: d_pdf [n_ss] of the queries d_cand under the KDE of the item's data set, read from the ring in
+ * place (the same partition of the data onto threads and loop trips), with wh / norm read from d_wh / d_norm: bit for bit
+ * what ssc_kde_evaluate returns on the materialised data set with that whitening and norm.  One call serves ONE obs_dim
+ * (SSC_EUNSUPPORTED naming both items otherwise).  An item with *d_status != 0 writes nothing. */
+int ssc_kde_evaluate_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items,
+                          ssc_stream_t stream);
+
+/* UCB1 and the n_plans best per item (one workgroup each): d_ucb[i] by ssc_ucb_argmax's expression with buffer_len = size for
+ * live slots (idx >= 0; NaN for the others), then d_chosen = idx[slot] of the n_plans best live slots, unused places -1.
+ * Order: descending ucb, NaN below -inf, lowest slot first on ties -- for n_plans = 1 ssc_ucb_argmax's answer on the live
+ * slots.  An item with *d_status != 0 gets d_chosen = -1 throughout.  Also checks: n_plans in 1..64, volume > 0. */
+int ssc_ucb_topk_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items, ssc_stream_t stream);
+
+/* ssc_replay_episode_path for every (item, plan): d_path[plan] / d_len[plan] for buffer index d_chosen[plan]; -1, or an
+ * episode start that has left the ring, gives len = 0.  Also checks: max_len >= 1, n_plans in 1..64. */
+int ssc_replay_episode_path_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items,
+                                 ssc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * normalize_returns + enable_popart (ddpg_editted.py:129-133, 140-149, 201-217, 291-301; arXiv 1602.07714)
  * -------------------------------------------------------------------------------------
  * ret_rms is the same RunningMeanStd as above with one column: d_ret_rms = [sum | sumsq | count] in f64, caller-

@@ -14,7 +14,7 @@ from .rl_train import (Episode, PopulationMonitor, Summary, rlTrain, rl_train_ve
                        rl_train_vec_ddpg_population, rl_train_vec_smartstart,
                        rl_train_vec_smartstart_population)
 from .replay_buffer import DeviceReplayBuffer, DeviceReplayPopulation, ReplayBuffer, append_chunks  # noqa: F401,E402
-from .smartstart import SmartStartContinuous, VecSmartStart, VecSmartStartPopulation  # noqa: F401,E402
+from .smartstart import SmartStartContinuous, VecSmartStart, VecSmartStartPopulation, select_plans_many  # noqa: F401,E402
 from .agents import DDPGPopulation, train_dynamics_models  # noqa: F401,E402
 from .navigator import DynamicsModelPopulation  # noqa: F401,E402
 from .collect_samples import (CollectSamples, Policy_Random, TrainingSet, dataset_from_chunk,  # noqa: F401,E402

@@ -169,6 +169,16 @@ class ReplayRing(Structure):
                 ("ep_steps", c_void_p), ("ep_run", c_void_p)]
 
 
+class SelectManyItem(Structure):
+    _fields_ = [("ring", ReplayRing), ("count", c_int64), ("n", c_int64), ("n_ss", c_int32), ("n_plans", c_int32),
+                ("seed", c_uint64), ("counter", c_uint64), ("stride", c_int64), ("n_data", c_int64), ("scott", c_double),
+                ("actor", ActorDesc), ("critic", CriticDesc), ("d_rms", c_void_p), ("alpha", c_float), ("beta", c_float),
+                ("volume", c_double), ("max_len", c_int32), ("pad", c_int32), ("row0", c_int64), ("d_idx", c_void_p),
+                ("d_n_cand", c_void_p), ("d_cand", c_void_p), ("d_wh", c_void_p), ("d_norm", c_void_p), ("d_status", c_void_p),
+                ("d_value", c_void_p), ("d_pdf", c_void_p), ("d_ucb", c_void_p), ("d_chosen", c_void_p), ("d_path", c_void_p),
+                ("d_len", c_void_p), ("d_workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
 class DdpgManyItem(Structure):
     _fields_ = [("ddpg", DdpgDesc), ("replay", ReplayView), ("d_batch_idx", c_void_p), ("d_losses", c_void_p),
                 ("d_rms", c_void_p), ("n_iters", c_int32)]
@@ -252,7 +262,7 @@ STRUCTS = {
     "ssc_ddpg_stats_many_item": DdpgStatsManyItem, "ssc_param_noise_many_item": ParamNoiseManyItem,
     "ssc_param_noise_cursor": ParamNoiseCursor, "ssc_mlp_train_many_item": MlpTrainManyItem,
     "ssc_mpc_sim_many_item": MpcSimManyItem, "ssc_mpc_sim_many_mfma_item": MpcSimManyMfmaItem,
-    "ssc_actor_many_item": ActorManyItem, "ssc_smartstart_pair": SmartStartPair,
+    "ssc_actor_many_item": ActorManyItem, "ssc_smartstart_pair": SmartStartPair, "ssc_select_many_item": SelectManyItem,
 }
 
 # symbol -> (restype, argtypes); every function include/ssc.h declares must be listed here
@@ -403,6 +413,13 @@ _SIGNATURES = {
                                                  c_uint64, c_uint64, POINTER(RolloutState), POINTER(TransitionLog),
                                                  POINTER(EpisodeRing), c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
                                                  c_void_p, c_void_p]),
+    # the smart-start selection of a population, one launch per stage over ONE item table (host items + device copy)
+    "ssc_replay_smart_start_indices_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_kde_scott_bandwidth_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_critic_forward_many": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "ssc_kde_evaluate_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_ucb_topk_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "ssc_replay_episode_path_many": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "ssc_nav_compact": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ssc_mpc_score_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "ssc_mpc_score": (c_int, [POINTER(MpcProblems), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "select_many.h"
 #include "ssc_device.h"
 #include "ssc_host.h"
 
@@ -169,7 +170,7 @@ constexpr int kSmartBlock = 1024, kSmartMaxRounds = 64;
 // keys[h] = buffer index + 1 (0 = empty, claimed by atomicCAS), owners[h] = (round << 12 | slot) of the slot that
 // holds the key, lowered with atomicMin -- so of all the slots that want a key in a round the LOWEST owns it whatever
 // the thread order, and a key taken in an earlier round (smaller round field) can never be taken over.
-__global__ __launch_bounds__(kSmartBlock) void smart_start_indices_kernel(SmartStartArgs a, uint32_t *keys, uint32_t *owners) {
+static __device__ __forceinline__ void smart_start_indices_body(const SmartStartArgs &a, uint32_t *keys, uint32_t *owners) {
     constexpr int SPT = 4;  // slots per thread: n_ss <= 4096
     __shared__ int n_unresolved, n_done;
     const uint32_t mask = (uint32_t)a.tsize - 1u;
@@ -247,6 +248,41 @@ __global__ __launch_bounds__(kSmartBlock) void smart_start_indices_kernel(SmartS
     if (threadIdx.x == 0) *a.n_out = n_done;
 }
 
+__global__ __launch_bounds__(kSmartBlock) void smart_start_indices_kernel(SmartStartArgs a, uint32_t *keys, uint32_t *owners) {
+    smart_start_indices_body(a, keys, owners);
+}
+
+static __host__ __device__ __forceinline__ int smart_table_cells(int32_t n_ss) {
+    int t = 1024;
+    while (t < 4 * n_ss) t <<= 1;
+    return t;
+}
+
+// ssc_replay_smart_start_indices_many: grid row y = item y, one workgroup running the body above on the item's ring and key,
+// then -- every slot's index is written by the thread that reads it back here -- the gather of the candidate states.
+__global__ __launch_bounds__(kSmartBlock) void smart_start_indices_many_kernel(const ssc_select_many_item *items) {
+    const const_select_item it = (const_select_item)items + blockIdx.y;
+    const int32_t n_ss = it->n_ss;
+    const int64_t count = it->count;
+    if (n_ss == 0 || count == 0) return;      // an empty item: workgroup-uniform, no barrier yet
+    SmartStartArgs a;
+    a.ep_steps = it->ring.ep_steps; a.capacity = it->ring.capacity; a.count = count;
+    a.size = count < a.capacity ? count : a.capacity; a.n = it->n;
+    a.n_ss = n_ss; a.seed = it->seed; a.counter = it->counter; a.idx = it->d_idx; a.n_out = it->d_n_cand;
+    a.tsize = smart_table_cells(n_ss);
+    uint32_t *keys = static_cast<uint32_t *>(it->d_workspace);
+    smart_start_indices_body(a, keys, keys + a.tsize);
+    const int od = it->ring.obs_dim;
+    const float *s2 = it->ring.s2;
+    float *cand = it->d_cand;
+    const int64_t base = a.count - a.size;
+    for (int slot = threadIdx.x; slot < n_ss; slot += kSmartBlock) {
+        const int32_t i = a.idx[slot];
+        const int64_t row = i >= 0 ? (base + i) % a.capacity : 0;
+        for (int c = 0; c < od; ++c) cand[(int64_t)slot * od + c] = i >= 0 ? s2[row * od + c] : 0.0f;
+    }
+}
+
 struct EpisodePathArgs {
     ssc_replay_ring ring;
     int64_t count, size, n;
@@ -256,7 +292,8 @@ struct EpisodePathArgs {
     int32_t *len;
 };
 
-__global__ __launch_bounds__(kBlock) void episode_path_kernel(EpisodePathArgs a) {
+// blocks bx of nbx of one path
+static __device__ __forceinline__ void episode_path_body(const EpisodePathArgs &a, unsigned bx, unsigned nbx) {
     const int64_t i = *a.buffer_index;
     const int od = a.ring.obs_dim;
     int32_t rows = 0;
@@ -267,10 +304,10 @@ __global__ __launch_bounds__(kBlock) void episode_path_kernel(EpisodePathArgs a)
         L = a.ring.ep_steps[rec % a.ring.capacity];
         if (L >= 1 && rec - (int64_t)(L - 1) * a.n >= a.count - a.size) rows = (L < a.max_len ? L : a.max_len) + 1;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.len = rows;
+    if (bx == 0 && threadIdx.x == 0) *a.len = rows;
     if (rows == 0) return;
     const int32_t steps = rows - 1;   // the newest `steps` states of the prefix, oldest first, then s2 of the record
-    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < (int64_t)rows * od; e += (int64_t)gridDim.x * kBlock) {
+    for (int64_t e = (int64_t)bx * kBlock + threadIdx.x; e < (int64_t)rows * od; e += (int64_t)nbx * kBlock) {
         const int32_t m = (int32_t)(e / od), c = (int32_t)(e % od);
         if (m < steps) {
             const int64_t r = rec - (int64_t)(steps - 1 - m) * a.n;
@@ -279,6 +316,28 @@ __global__ __launch_bounds__(kBlock) void episode_path_kernel(EpisodePathArgs a)
             a.path[e] = a.ring.s2[(rec % a.ring.capacity) * od + c];
         }
     }
+}
+
+__global__ __launch_bounds__(kBlock) void episode_path_kernel(EpisodePathArgs a) {
+    episode_path_body(a, blockIdx.x, gridDim.x);
+}
+
+// ssc_replay_episode_path_many: grid row y = item y, grid z = plan; the path of buffer index d_chosen[plan]
+__global__ __launch_bounds__(kBlock) void episode_path_many_kernel(const ssc_select_many_item *items) {
+    const const_select_item it = (const_select_item)items + blockIdx.y;
+    const int64_t count = it->count;
+    if (it->n_ss == 0 || count == 0 || (int)blockIdx.z >= it->n_plans) return;
+    const int32_t max_len = it->max_len;
+    const int od = it->ring.obs_dim;
+    if ((int64_t)blockIdx.x * kBlock >= ((int64_t)max_len + 1) * od) return;    // (block 0 always stays: it writes len)
+    EpisodePathArgs a;
+    a.ring.s = it->ring.s; a.ring.s2 = it->ring.s2; a.ring.ep_steps = it->ring.ep_steps;
+    a.ring.capacity = it->ring.capacity; a.ring.obs_dim = od;
+    a.count = count; a.size = count < a.ring.capacity ? count : a.ring.capacity; a.n = it->n;
+    a.buffer_index = it->d_chosen + blockIdx.z; a.max_len = max_len;
+    a.path = it->d_path + (int64_t)blockIdx.z * ((int64_t)max_len + 1) * od;
+    a.len = it->d_len + blockIdx.z;
+    episode_path_body(a, blockIdx.x, gridDim.x);
 }
 
 // One wave per batch.  Slot i draws candidate (word0(Philox(seed; batch id, attempt << 8 | i)) * size) >> 32 in
@@ -522,11 +581,7 @@ int ssc_replay_append_many(const ssc_replay_append_item *h_items, const ssc_repl
     return launch_append_many(indexed, r0.obs_dim, d_items, d_cursors, n_pairs, work_max, as_stream(stream));
 }
 
-static int smart_table_size(int32_t n_ss) {
-    int t = 1024;
-    while (t < 4 * n_ss) t <<= 1;
-    return t;
-}
+static int smart_table_size(int32_t n_ss) { return smart_table_cells(n_ss); }
 
 size_t ssc_replay_smart_start_workspace_bytes(int32_t n_ss) {
     return n_ss > 0 ? (size_t)smart_table_size(n_ss) * 8 : 256;
@@ -572,6 +627,53 @@ int ssc_replay_episode_path(const ssc_replay_ring *ring, int64_t count, int64_t 
     if (blocks > 64) blocks = 64;
     hipLaunchKernelGGL(episode_path_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), a);
     return check_launch("ssc_replay_episode_path");
+}
+
+int ssc_replay_smart_start_indices_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items,
+                                        ssc_stream_t stream) {
+    const char *fn = "ssc_replay_smart_start_indices_many";
+    if (int rc = select_table_check(fn, h_items, d_items, n_items)) return rc;
+    bool work = false;
+    for (int i = 0; i < n_items; ++i) {
+        const ssc_select_many_item &it = h_items[i];
+        char who[72];
+        if (int rc = select_item_check(fn, i, it, who)) return rc;
+        if (select_item_empty(it)) continue;
+        SSC_REQUIRE(it.ring.ep_steps != nullptr, "%s: the ring keeps no episode index (ep_steps NULL)", who);
+        SSC_REQUIRE(it.ring.s2 && it.d_idx && it.d_n_cand && it.d_cand, "%s: NULL device pointer", who);
+        SSC_REQUIRE(it.d_workspace && it.workspace_bytes >= ssc_replay_smart_start_workspace_bytes(it.n_ss), "%s: workspace too small",
+                    who);
+        work = true;
+    }
+    if (!work) return SSC_OK;
+    hipLaunchKernelGGL(smart_start_indices_many_kernel, dim3(1, (unsigned)n_items), dim3(kSmartBlock), 0, as_stream(stream), d_items);
+    return check_launch(fn);
+}
+
+int ssc_replay_episode_path_many(const ssc_select_many_item *h_items, const ssc_select_many_item *d_items, int32_t n_items,
+                                 ssc_stream_t stream) {
+    const char *fn = "ssc_replay_episode_path_many";
+    if (int rc = select_table_check(fn, h_items, d_items, n_items)) return rc;
+    int64_t elems_max = 0;
+    int plans_max = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const ssc_select_many_item &it = h_items[i];
+        char who[72];
+        if (int rc = select_item_check(fn, i, it, who)) return rc;
+        if (select_item_empty(it)) continue;
+        SSC_REQUIRE(it.ring.ep_steps != nullptr, "%s: the ring keeps no episode index (ep_steps NULL)", who);
+        SSC_REQUIRE(it.max_len >= 1, "%s: max_len %d < 1", who, it.max_len);
+        SSC_REQUIRE(it.n_plans >= 1 && it.n_plans <= 64, "%s: n_plans %d not in 1..64", who, it.n_plans);
+        SSC_REQUIRE(it.ring.s && it.ring.s2 && it.d_chosen && it.d_path && it.d_len, "%s: NULL device pointer", who);
+        elems_max = std::max(elems_max, ((int64_t)it.max_len + 1) * it.ring.obs_dim);
+        plans_max = std::max(plans_max, (int)it.n_plans);
+    }
+    if (plans_max == 0) return SSC_OK;
+    int64_t blocks = blocks_for(elems_max);
+    if (blocks > 64) blocks = 64;
+    hipLaunchKernelGGL(episode_path_many_kernel, dim3((unsigned)blocks, (unsigned)n_items, (unsigned)plans_max), dim3(kBlock), 0,
+                       as_stream(stream), d_items);
+    return check_launch(fn);
 }
 
 int ssc_replay_sample(uint64_t seed, uint64_t counter0, int64_t size, int32_t n_batches, int32_t batch_size,

@@ -937,7 +937,7 @@ def rl_train_vec_smartstart(env, smart, num_chunks, chunk_steps=64, replay_capac
 def rl_train_vec_smartstart_population(env, smart_population, num_chunks, chunk_steps=64, replay_capacity=1 << 20,
                                        train_iters=None, replay_last_steps=None, seed=0, ring_capacity=1 << 20, refresh_every=1,
                                        graph=True, on_chunk=None, aggregate_every=0, aggregate_kwargs=None,
-                                       overlap_selection=False):
+                                       overlap_selection=False, grouped_selection=False):
     """The synchronous loop of :func:`rl_train_vec_smartstart` for ALL pairs of a :class:`smartstart.VecSmartStartPopulation`
     -- the seeds and hyper-parameters of SmartStart_DDPG_Baselines_experimenter.py -- on the ONE ``env`` that holds every
     pair's envs.  Per chunk: every pair's smart-start selection on its own ring (every ``refresh_every`` chunks; its
@@ -949,6 +949,10 @@ def rl_train_vec_smartstart_population(env, smart_population, num_chunks, chunk_
     replay ring, agent parameters and final eta / epsilon are those of its own ``rl_train_vec_smartstart`` run on
     ``VecEnv(n_p, env_id0 + env0_p)`` with the same arguments.  ``seed``: one replay seed for all pairs or one per pair.
     ``on_chunk(c, out, smart_population)``.  Not in this form: ``overlap_selection=True`` (NotImplementedError).
+    ``grouped_selection=True``: every due ``train_dynamics_model`` runs first (each touches only its own model, which the
+    selection does not read), then ONE ``smart_population.refresh_plans(replays)`` selects for all pairs in one launch per
+    stage with one host wait; the Scott bandwidth is then summed in the device's fixed order, so pdf, ucb and possibly the
+    chosen starts differ in the last bits from the default, which keeps the per-pair calls and their bits.
     Returns [(Summary, losses per chunk, replay)] per pair."""
     if overlap_selection:
         raise NotImplementedError("rl_train_vec_smartstart_population: overlap_selection=True is not part of the population loop; "
@@ -982,11 +986,18 @@ def rl_train_vec_smartstart_population(env, smart_population, num_chunks, chunk_
     kept = chunk_steps if replay_last_steps is None else min(int(replay_last_steps), chunk_steps)
     losses, generations = [[] for _ in pairs], [0.0] * P
     for c in range(num_chunks):
-        for p, pr in enumerate(pairs):
+        if grouped_selection:
             if aggregate_every and c > 0 and c % aggregate_every == 0:
-                pr.train_dynamics_model(replays[p], **(aggregate_kwargs or {}))
+                for p, pr in enumerate(pairs):
+                    pr.train_dynamics_model(replays[p], **(aggregate_kwargs or {}))
             if c % refresh_every == 0:
-                pr.refresh_plans(replays[p])
+                pop.refresh_plans(replays)
+        else:
+            for p, pr in enumerate(pairs):
+                if aggregate_every and c > 0 and c % aggregate_every == 0:
+                    pr.train_dynamics_model(replays[p], **(aggregate_kwargs or {}))
+                if c % refresh_every == 0:
+                    pr.refresh_plans(replays[p])
         out = pop.rollout(chunk_steps, chunk, ring=ring, graph=graph)
         for p, pr in enumerate(pairs):
             views[p].step0, views[p].env_id0 = out.step0, out.env_id0 + pr.env0

@@ -489,6 +489,221 @@ SMARTSTART_POPULATION_ACTOR_MIN_GROUP = 2
 SMARTSTART_POPULATION_ACTOR_MIN_GROUP_FEW_ROWS = 16
 
 
+# A population of at least this many pairs selects its smart starts through ``select_plans_many``
+# (``VecSmartStartPopulation.refresh_plans``); a smaller one runs the per-pair calls.  Measured on an MI355X
+# (tools/exp_smartstart_population_selection.py, profiles/smartstart_population/selection.json; P = 1, 2, 16, 64 pairs, rings
+# of 4 096, 65 536 and 500 000 states, 64-32 and 200-100 agents, n_ss 1000, n_plans 1 and 8; a case is won when the slowest
+# grouped window beats the fastest per-pair window, host geometry left out of both): every case with P >= 2 is won (x1.29 ..
+# x3.6 at 2 pairs, x3.3 .. x11.8 at 64); P = 1 LOSES on the 500 000-state rings with n_plans = 1 (x0.77 and x0.91: the
+# one-workgroup covariance scan costs more there than the host waits it saves), wins nine of the other ten by x1.09 .. x2.8 and misses the tenth by one slow window.
+SMARTSTART_POPULATION_SELECTION_MIN_GROUP = 2
+
+
+class _SelectManyBuffers:
+    """Device and pinned buffers of ``select_plans_many`` for one list of pairs: pooled per-slot arrays (row0 of pair p =
+    the slots of the pairs before it) and ONE byte block [chosen | len | status | n_cand | paths] that goes to the host in
+    one copy.  Rebuilt when a shape changes."""
+
+    def __init__(self, shapes, obs_dim, act_dim, device):
+        from .population import DeviceItems
+        self.shapes, self.obs_dim, self.act_dim, self.device = shapes, obs_dim, act_dim, device
+        P = len(shapes)
+        self.row0 = np.concatenate([[0], np.cumsum([s[0] for s in shapes])]).astype(np.int64)
+        self.plan0 = np.concatenate([[0], np.cumsum([s[1] for s in shapes])]).astype(np.int64)
+        path_elems = [s[1] * (s[2] + 1) * obs_dim for s in shapes]
+        self.path0 = np.concatenate([[0], np.cumsum(path_elems)]).astype(np.int64)
+        m, k = int(self.row0[-1]), int(self.plan0[-1])
+        self.m = m
+        lib = _ffi.lib()
+        ws = [int(lib.ssc_replay_smart_start_workspace_bytes(int(s[0]))) for s in shapes]
+        self.ws0 = np.concatenate([[0], np.cumsum(ws)]).astype(np.int64)
+        f = lambda n, dt: torch.zeros(max(int(n), 1), dtype=dt, device=device)
+        self.idx, self.cand, self.act = f(m, torch.int32), f(m * obs_dim, torch.float32), f(m * act_dim, torch.float32)
+        self.value, self.pdf, self.ucb = f(m, torch.float32), f(m, torch.float32), f(m, torch.float32)
+        self.wh, self.norm = f(P * obs_dim * obs_dim, torch.float32), f(P, torch.float64)
+        self.workspace = f(self.ws0[-1], torch.uint8)
+        # the block the host reads: int32 chosen [k] | len [k] | status [P] | n_cand [P] | float paths
+        self.o_len, self.o_status, self.o_ncand, self.o_path = 4 * k, 8 * k, 8 * k + 4 * P, 8 * k + 8 * P
+        nbytes = self.o_path + 4 * int(self.path0[-1])
+        self.block = f(nbytes, torch.uint8)
+        self.host = torch.zeros(max(nbytes, 1), dtype=torch.uint8).pin_memory()
+        self.items = DeviceItems(_ffi.SelectManyItem, P, device)
+        self.sent = None
+        self.actor_items, self.actor_sent = {}, {}
+        with torch.cuda.device(device):
+            self.done = torch.cuda.Event()
+
+
+def select_plans_many(pairs, replays):
+    """``SmartStartSelection.select_plans`` for all ``pairs`` (each on its own ring of ``replays``) in one launch per stage:
+    candidates + gather (``ssc_replay_smart_start_indices_many``), Scott bandwidth on the device
+    (``ssc_kde_scott_bandwidth_many``), the plain actors (``ssc_actor_forward_many`` per kernel class, by the population's
+    grouping rule), critics, KDE (the rings read in place), UCB1 top-k and the chosen paths -- then ONE device-to-host copy of
+    status, chosen indices, path lengths and paths into pinned memory and ONE wait, and ``plan_from_path`` per chosen path on
+    the host.  Returns per pair a plan list, or None where ``select_plans`` returns None (empty ring, ``n_ss <= 0``, no valid
+    candidate).  ``replay._queries`` and ``pair.last_chosen`` move as the per-pair calls move them.  A pair whose bandwidth
+    has no Cholesky factor raises ``numpy.linalg.LinAlgError`` naming the pair, after the read.  The bandwidth is the only
+    stage whose bits differ from ``kde_scott_bandwidth`` (its own fixed summation order); every other stage returns the
+    per-pair call's bits on the same input."""
+    pairs, replays = list(pairs), list(replays)
+    P = len(pairs)
+    if P == 0 or len(replays) != P:
+        raise ValueError("select_plans_many: one replay ring per pair, at least one pair")
+    for r in replays:
+        if not isinstance(r, DeviceReplayBuffer) or not r.track_episodes:
+            raise TypeError("select_plans_many needs DeviceReplayBuffer(track_episodes=True) rings")
+    dev = replays[0].device
+    od, ad = replays[0].obs_dim, pairs[0].agent.act_dim
+    if any(r.obs_dim != od or pr.agent.act_dim != ad for r, pr in zip(replays, pairs)):
+        raise ValueError("select_plans_many: the pairs of one call share obs_dim and act_dim")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("select_plans_many reads its results on the host; it cannot run inside a graph capture")
+    for pr in pairs:
+        if int(pr.n_ss) > 4096:
+            raise ValueError("n_ss <= 4096 on the device path")
+        if not 1 <= int(pr.n_plans) <= 64:
+            raise ValueError("select_plans_many: n_plans in 1..64")
+    shapes = tuple((max(int(pr.n_ss), 0), int(pr.n_plans), int(r.max_path_len)) for pr, r in zip(pairs, replays))
+    owner = pairs[0]
+    buf = getattr(owner, "_select_many", None)
+    if buf is None or buf.shapes != shapes or (buf.obs_dim, buf.act_dim, buf.device) != (od, ad, dev) or \
+            getattr(owner, "_select_many_pairs", None) != [id(pr) for pr in pairs]:
+        buf = owner._select_many = _SelectManyBuffers(shapes, od, ad, dev)
+        owner._select_many_pairs = [id(pr) for pr in pairs]
+    lib = _ffi.lib()
+    live = [len(r) > 0 and s[0] > 0 for r, s in zip(replays, shapes)]
+    fresh = (_ffi.SelectManyItem * P)()
+    base = buf.block.data_ptr()
+    for p, (it, pr, r) in enumerate(zip(fresh, pairs, replays)):
+        n_ss, n_plans, max_len = shapes[p]
+        size = len(r)
+        it.ring, it.count, it.n = r.ring_struct(), (r.count if live[p] else 0), r.n_envs
+        it.n_ss, it.n_plans, it.max_len = (n_ss if live[p] else 0), n_plans, max_len
+        if not live[p]:
+            continue
+        it.seed, it.counter = r.seed ^ 0x5353, r._queries
+        rows = size + 1
+        stride = 1
+        if pr.kde_max_states is not None and rows > pr.kde_max_states:
+            stride = -(-rows // int(pr.kde_max_states))
+        n_data = -(-rows // stride)
+        it.stride, it.n_data = stride, n_data
+        it.scott = (n_data ** (-1.0 / (od + 4))) ** 2
+        a = pr.agent
+        rms = getattr(a, "obs_rms", None)
+        it.actor, it.critic = a._desc, a._critic_desc
+        it.d_rms = None if rms is None else rms.block.data_ptr()
+        it.alpha, it.beta = float(pr.exploitation_param), float(pr.exploration_param)
+        it.volume = float(volume_of_n_dimensional_hyperellipsoid(pr.last_radii)) if pr.last_radii is not None else 1.0
+        r0, k0 = int(buf.row0[p]), int(buf.plan0[p])
+        it.row0 = r0
+        it.d_idx, it.d_cand = buf.idx.data_ptr() + 4 * r0, buf.cand.data_ptr() + 4 * r0 * od
+        it.d_value, it.d_pdf, it.d_ucb = (t.data_ptr() + 4 * r0 for t in (buf.value, buf.pdf, buf.ucb))
+        it.d_wh, it.d_norm = buf.wh.data_ptr() + 4 * p * od * od, buf.norm.data_ptr() + 8 * p
+        it.d_chosen, it.d_len = base + 4 * k0, base + buf.o_len + 4 * k0
+        it.d_status, it.d_n_cand = base + buf.o_status + 4 * p, base + buf.o_ncand + 4 * p
+        it.d_path = base + buf.o_path + 4 * int(buf.path0[p])
+        it.d_workspace, it.workspace_bytes = buf.workspace.data_ptr() + int(buf.ws0[p]), int(buf.ws0[p + 1] - buf.ws0[p])
+    if not any(live):
+        return [None] * P
+    image = bytes(fresh)
+    di = buf.items
+    with torch.cuda.device(dev):
+        st = _ffi.stream(dev)
+        if buf.sent != image:
+            di.wait()
+            ctypes.memmove(di.h_ptr, ctypes.addressof(fresh), len(image))
+            di.upload()
+            buf.sent = image
+        _ffi.check(lib.ssc_replay_smart_start_indices_many(di.h_ptr, di.d_ptr, P, st))
+        _ffi.check(lib.ssc_kde_scott_bandwidth_many(di.h_ptr, di.d_ptr, P, st))
+        _select_many_actors(buf, pairs, live, st)
+        _ffi.check(lib.ssc_critic_forward_many(di.h_ptr, di.d_ptr, P, buf.m, _ffi.ptr(buf.act), st))
+        _ffi.check(lib.ssc_kde_evaluate_many(di.h_ptr, di.d_ptr, P, st))
+        _ffi.check(lib.ssc_ucb_topk_many(di.h_ptr, di.d_ptr, P, st))
+        _ffi.check(lib.ssc_replay_episode_path_many(di.h_ptr, di.d_ptr, P, st))
+        chosen64 = buf.block[:buf.o_len].view(torch.int32).long()      # every pair's last_chosen is a slice of this
+        buf.host.copy_(buf.block, non_blocking=True)
+        buf.done.record()
+    for p, r in enumerate(replays):
+        if live[p]:
+            r._queries += 1
+    buf.done.synchronize()                                             # the ONE host wait of the refresh
+    h = buf.host.numpy()
+    K = int(buf.plan0[-1])
+    h_chosen, h_len = h[:4 * K].view(np.int32), h[buf.o_len:buf.o_len + 4 * K].view(np.int32)
+    h_status, h_ncand = h[buf.o_status:buf.o_status + 4 * P].view(np.int32), h[buf.o_ncand:buf.o_ncand + 4 * P].view(np.int32)
+    h_path = h[buf.o_path:].view(np.float32)
+    out = []
+    for p, pr in enumerate(pairs):
+        if not live[p] or h_ncand[p] == 0:
+            out.append(None)
+            continue
+        if h_status[p] != 0:
+            raise np.linalg.LinAlgError("select_plans_many: pair %d: the KDE covariance has no Cholesky factor" % p)
+        n_ss, n_plans, max_len = shapes[p]
+        k0 = int(buf.plan0[p])
+        n_chosen = int((h_chosen[k0:k0 + n_plans] >= 0).sum())
+        pr.last_chosen = chosen64[k0:k0 + n_chosen]
+        paths = h_path[int(buf.path0[p]):int(buf.path0[p + 1])].reshape(n_plans, max_len + 1, od)
+        plans = []
+        for j in range(n_chosen):
+            rows = int(h_len[k0 + j])
+            if rows == 0:
+                raise ValueError(": (   -   the episode start of this record is no longer in the ring")
+            if rows < 2:
+                continue
+            plans.append(pr.plan_from_path(paths[j, :rows].astype(np.float64)))
+        out.append(plans)
+    return out
+
+
+def _select_many_actors(buf, pairs, live, st):
+    """The plain actors on the pooled candidate matrix: one ``ssc_actor_forward_many`` per kernel class with enough pairs
+    (the population's grouping rule), the rest alone on their slices -- the same bits either way."""
+    from .population import DeviceItems
+    lib, groups = _ffi.lib(), {}
+    od, ad = buf.obs_dim, buf.act_dim
+    for p, pr in enumerate(pairs):
+        if not live[p]:
+            continue
+        rms = getattr(pr.agent, "obs_rms", None)
+        groups.setdefault(lib.ssc_actor_many_class(ctypes.byref(pr.agent._desc), int(rms is not None)), []).append(p)
+    for key in [k for k in buf.actor_items if k not in groups]:
+        del buf.actor_items[key]
+        buf.actor_sent.pop(key, None)
+    for cls, members in sorted(groups.items()):
+        few_rows = cls // 2 == 8 and all(buf.shapes[p][0] <= 32 for p in members)
+        need = SMARTSTART_POPULATION_ACTOR_MIN_GROUP_FEW_ROWS if few_rows else SMARTSTART_POPULATION_ACTOR_MIN_GROUP
+        if cls < 0 or len(members) < need:
+            for p in members:
+                a = pairs[p].agent
+                rms = getattr(a, "obs_rms", None)
+                r0, rows = int(buf.row0[p]), buf.shapes[p][0]
+                obs, out = buf.cand.data_ptr() + 4 * r0 * od, buf.act.data_ptr() + 4 * r0 * ad
+                if rms is None:
+                    _ffi.check(lib.ssc_actor_forward(ctypes.byref(a._desc), rows, obs, out, st))
+                else:
+                    _ffi.check(lib.ssc_actor_forward_rms(ctypes.byref(a._desc), rows, obs, out, st, _ffi.ptr(rms.block)))
+            continue
+        fresh = (_ffi.ActorManyItem * len(members))()
+        for it, p in zip(fresh, members):
+            rms = getattr(pairs[p].agent, "obs_rms", None)
+            it.actor, it.d_rms = pairs[p].agent._desc, (None if rms is None else rms.block.data_ptr())
+            it.row0, it.rows = int(buf.row0[p]), buf.shapes[p][0]
+        di = buf.actor_items.get(cls)
+        if di is None or di.n != len(members):
+            di = buf.actor_items[cls] = DeviceItems(_ffi.ActorManyItem, len(members), buf.device)
+            buf.actor_sent.pop(cls, None)
+        image = bytes(fresh)
+        if buf.actor_sent.get(cls) != image:
+            di.wait()
+            ctypes.memmove(di.h_ptr, ctypes.addressof(fresh), len(image))
+            di.upload()
+            buf.actor_sent[cls] = image
+        _ffi.check(lib.ssc_actor_forward_many(di.h_ptr, di.d_ptr, di.n, buf.m, _ffi.ptr(buf.cand), _ffi.ptr(buf.act), st))
+
+
 def _per_pair(value, n, what):
     if isinstance(value, (list, tuple, np.ndarray)):
         if len(value) != n:
@@ -652,6 +867,24 @@ class VecSmartStartPopulation:
             self._actor_sent.pop(key, None)
         self._actor_plan = plan
         return plan
+
+    # -------------------------------------------------------------------------- selection --
+    def refresh_plans(self, replays):
+        """``refresh_plans`` of every pair on its ring of ``replays``: ONE grouped selection (``select_plans_many``: one
+        launch per stage, one host wait for the whole population), then ``publish_plans`` pair by pair.  A population of
+        fewer than ``SMARTSTART_POPULATION_SELECTION_MIN_GROUP`` pairs runs the per-pair calls.  Returns every pair's
+        ``last_chosen`` (None where its ring holds no complete episode start yet)."""
+        replays = list(replays)
+        if len(replays) != len(self.pairs):
+            raise ValueError("VecSmartStartPopulation.refresh_plans: one replay ring per pair")
+        if len(self.pairs) < SMARTSTART_POPULATION_SELECTION_MIN_GROUP:
+            return [pr.refresh_plans(r) for pr, r in zip(self.pairs, replays)]
+        for pr in self.pairs:
+            pr.last_chosen = None
+        for pr, plans in zip(self.pairs, select_plans_many(self.pairs, replays)):
+            if plans is not None:
+                pr.publish_plans(plans)
+        return [pr.last_chosen for pr in self.pairs]
 
     # ------------------------------------------------------------------------------ steps --
     def _step_struct(self, chunk_k):
